@@ -265,6 +265,47 @@ int oneprot_transpose_cast_f32_to_bf16_batched(const float* src, void* dst, int 
 size_t oneprot_colsum_workspace(int N);
 int oneprot_colsum_bf16(const void* a, float* out, void* workspace, int64_t M, int N, int accumulate, void* stream);
 
+/* ---------------- packed (variable-length) batches ------------------------------------------------------------------
+ * A packed batch is a token stream: N sequences back to back, each with its own <cls> ... <eos>, in rows [cu_seqlens[b], cu_seqlens[b+1]) of
+ * ids int64 [T_pad]; rows [cu_seqlens[N], T_pad) (the tail) hold pad ids.  cu_seqlens is int32 [N + 1] on the device.  Every row-wise kernel above
+ * runs unchanged on the T_pad rows (the QKV GEMM with B = 1, L = T_pad, its rotary epilogue reading the per-token tables written below); these entry
+ * points replace the layout-dependent ones.  The reference pads each batch instead (ref struct_token_dataset.py:87-88, collate with padding=True). */
+/* embeddings (hf modeling_esm.py:224-271; ref sequence_encoder.py:78) with the token-dropout factor counted per sequence, kept per token in tok_scale
+   [T_pad] (0 on the tail), plus the rotary tables gathered per token: cos_out / sin_out [T_pad, half] = rope_cos / rope_sin [n_pos, half] at the
+   token's position within its sequence (hf modeling_esm.py:150-158 with positions restarting at 0 per sequence).  max_len <= n_pos. */
+int oneprot_esm_embed_packed_fwd(const int64_t* ids, const int* cu_seqlens, const float* table, const float* rope_cos, const float* rope_sin, float* x,
+                                 float* tok_scale, float* cos_out, float* sin_out, int N, int T_pad, int max_len, int d, int vocab, int half, int n_pos,
+                                 int pad_id, int mask_id, int token_dropout, void* stream);
+/* dtable (+)= per-token-scaled rows of dx; workspace: oneprot_esm_embed_bwd_workspace(T_pad, d, vocab).  Tail rows (pad ids) add nothing. */
+int oneprot_esm_embed_packed_bwd(const int64_t* ids, const float* dx, const float* tok_scale, float* dtable, void* workspace, int T_pad, int d, int vocab,
+                                 int pad_id, int mask_id, int token_dropout, int accumulate, void* stream);
+/* attention over segments (hf modeling_esm.py:292-317, one softmax per sequence): q/k/v bf16 [H, T_pad, hd] (the QKV GEMM's head-major output
+   with B = 1), work int32 [n_work][2] = (segment, 128-row block) items, longest segment first; ctx bf16 [T_pad, H*hd], lse fp32 [H, T_pad]
+   (natural log); tail rows are written as 0.  hd 16 / 32 / 64, segments of 1 .. 1026 tokens. */
+int oneprot_attn_varlen_fwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse,
+                            int N, int T_pad, int H, int hd, void* stream);
+size_t oneprot_attn_varlen_bwd_workspace(int H, int T_pad);
+/* dqkv bf16 [T_pad, 3*H*hd] as oneprot_attn_bwd, the inverse rotary through the per-token tables of oneprot_esm_embed_packed_fwd; tail rows 0.
+   Split dQ and dK/dV kernels, no atomics: deterministic. */
+int oneprot_attn_varlen_bwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
+                            const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
+                            void* workspace, int N, int T_pad, int H, int hd, void* stream);
+/* final LayerNorm fused with pooling per sequence (hf modeling_esm.py:552; ref base_encoder.py:109-126): mode 0 mean, 1 CLS; x fp32 [T_pad, d] ->
+   pooled [N, d]; mean / rstd / wrow per stream row (wrow = 0 on the tail), hidden_f32 [T_pad, d] optional. */
+int oneprot_lnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* gamma, const float* beta, float* pooled,
+                              float* mean, float* rstd, float* wrow, float* hidden_f32, int N, int T_pad, int d, float eps, int mode, void* stream);
+/* its backward: dx [T_pad, d] = LN'(dpooled[seq(t)] * wrow[t]) (exactly 0 on the tail), optional bf16 copy, dgamma / dbeta (workspace:
+   oneprot_layernorm_bwd_workspace(d)). */
+int oneprot_lnpool_packed_bwd(const float* dpooled, const int* cu_seqlens, const float* wrow, const float* x, const float* gamma, const float* mean,
+                              const float* rstd, float* dx, void* dx_bf16, float* dgamma, float* dbeta, void* workspace, int N, int T_pad, int d,
+                              void* stream);
+/* Attention1dPooling per sequence (ref base_encoder.py:88-103): x fp32 [T_pad, d] (the normalised hidden state), attn [T_pad]; every sequence <= max_len. */
+int oneprot_attnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* w, const float* bias, float* pooled,
+                                float* attn, int N, int max_len, int d, void* stream);
+/* its backward; dx (optional) [T_pad, d] with zero tail rows; workspace: oneprot_attnpool_bwd_workspace(N, d). */
+int oneprot_attnpool_packed_bwd(const float* x, const float* attn, const int* cu_seqlens, const float* w, const float* dpooled, float* dw, float* db,
+                                float* dx, void* workspace, int N, int T_pad, int max_len, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2492,3 +2492,353 @@ extern "C" int oneprot_attn_bwd(const void* q, const void* k, const void* v, con
     default: return OP_EINVAL;
   }
 }
+
+// =========================================================================================================
+// varlen (packed) attention: q / k / v bf16 [H, T_pad, hd] hold N segments back to back (cu_seqlens int32 [N + 1]); a segment's queries see
+// only that segment's keys.  Work items (segment, 128-row block) come from the host in `work` int32 [n_work][2], longest segment first, so that one
+// long segment does not finish alone at the end; work-group = item * H + head.  The tile steps are those of k_attn_fwd / k_attn_bwd_dq / dkv
+// above (per-tile running maximum in the forward: scores of +-400 stay exact); the segment end masks the last partial key tile (its zero-filled
+// rows get -inf in the extra k-step), so there is no key-bias tensor.  ctx / dctx are [T_pad, H*hd], lse / delta [H, T_pad], dqkv [T_pad, 3*H*hd];
+// rows past cu_seqlens[N] (the tail) are written as zeros by k_varlen_tail_zero.
+// =========================================================================================================
+struct VarSeg { int start, n, blk; };
+__device__ __forceinline__ bool varlen_item(const int* __restrict__ cu, const int* __restrict__ work, int N, int T_pad, int H, int& head, VarSeg& sg) {
+  const int item = blockIdx.x / H;
+  head = blockIdx.x - item * H;
+  const int seg = work[2 * item], blk = work[2 * item + 1];
+  if (seg < 0 || seg >= N) return false;
+  sg.start = cu[seg];
+  sg.n = cu[seg + 1] - sg.start;
+  sg.blk = blk;
+  return sg.start >= 0 && sg.n > 0 && sg.start + sg.n <= T_pad && blk >= 0 && blk * 128 < sg.n;
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) k_attn_varlen_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                         const int* __restrict__ cu, const int* __restrict__ work, bf16_t* __restrict__ ctx,
+                                                         float* __restrict__ lse_out, int N, int T_pad, int H) {
+  typedef Cfg<HD> C;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* sK = smem;
+  unsigned char* sV = sK + KC * C::ROWB;
+  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);
+  int head;
+  VarSeg sg;
+  if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
+  const int L = sg.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+  const int qidx = sg.blk * 128 + wave * 32 + (lane & 31);
+  const int qrow = qidx < L ? qidx : L - 1;
+  const size_t slab = (size_t)head * T_pad + sg.start;          // row of position 0 of this (segment, head) in q / k / v / lse
+  const bf16_t* qbase = q + slab * HD;
+  const bf16_t* kbase = k + slab * HD;
+  const bf16_t* vbase = v + slab * HD;
+  bf8_t qf[C::KSTEPS];
+#pragma unroll
+  for (int st = 0; st < C::KSTEPS; ++st) qf[st] = *reinterpret_cast<const bf8_t*>(qbase + (size_t)qrow * HD + 16 * st + 8 * h);
+  float m = 0.f, l = 0.f;
+  u32x4 qe = {0u, 0u, 0u, 0u};
+  if (h == 0) { qe.x = 0u; qe.y = 0x3F800000u; }
+  const u32x4 ones = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
+  f32x16 acc[C::DBLK], lacc = zero16();
+#pragma unroll
+  for (int d = 0; d < C::DBLK; ++d) acc[d] = zero16();
+  bool first = true;
+  for (int kc0 = 0; kc0 < L; kc0 += KC) {
+    const int nkeys = min(KC, L - kc0);
+    const int nrows = (nkeys + 31) & ~31;
+    __syncthreads();
+    load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
+    for (int i = threadIdx.x; i <= KC; i += 256) {
+      u32x4 e = {0u, 0u, 0u, 0u};
+      if (i < nrows) {
+        const float bv = i < nkeys ? 0.f : -INFINITY;            // the segment end
+        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
+      }
+      sE[i] = e;
+    }
+    __syncthreads();
+    for (int t = 0; t < nrows / 32; ++t) {
+      const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
+      f32x16 s = MFMA32(__builtin_bit_cast(bf8_t, ke), __builtin_bit_cast(bf8_t, qe), zero16());
+#pragma unroll
+      for (int st = 0; st < C::KSTEPS; ++st) s = MFMA32(rd_row<HD>(sK, t * 32 + (lane & 31), st, h), qf[st], s);
+      float mx = fmaxf(fmaxf(s[0], s[1]), s[2]);
+#pragma unroll
+      for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[r]), s[r + 1]);
+      mx = fmaxf(mx, s[15]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      if (first || __any(mx > RESCALE_THR * LOG2E)) {
+        float dlt = first ? mx : fmaxf(mx, 0.f);
+        if (!(dlt > -1e30f)) dlt = 0.f;
+        const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-dlt);
+        l = (l + lacc[0]) * alpha;
+        lacc = zero16();
+#pragma unroll
+        for (int d = 0; d < C::DBLK; ++d)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[d][r] *= alpha;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] -= dlt;
+        m += dlt;
+        if (h == 0) {
+          const float nm = -m;
+          const unsigned w0 = pack2bf(nm, 0.f); const float r1 = nm - bflo(w0);
+          const unsigned w1 = pack2bf(r1, 0.f); const float r2 = r1 - bflo(w1);
+          qe.x = (w0 & 0xffffu) | (w1 << 16); qe.y = pack2bf(r2, 1.0f);
+        }
+        first = false;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+        const bf8_t pf = pack8(s, sb);
+        lacc = MFMA32(__builtin_bit_cast(bf8_t, ones), pf, lacc);
+#pragma unroll
+        for (int d = 0; d < C::DBLK; ++d) acc[d] = MFMA32(rd_tr<HD>(sV, t * 32, sb, d, lane), pf, acc[d]);
+      }
+    }
+  }
+  const float lt = l + lacc[0];
+  const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+  if (qidx < L) {
+    bf16_t* dst = ctx + ((size_t)sg.start + qidx) * (H * HD) + head * HD;
+#pragma unroll
+    for (int d = 0; d < C::DBLK; ++d)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int dd = 32 * d + 8 * g + 4 * h;
+        if (dd < HD) {
+          u32x2 w; w.x = pack2bf(acc[d][4 * g] * inv, acc[d][4 * g + 1] * inv); w.y = pack2bf(acc[d][4 * g + 2] * inv, acc[d][4 * g + 3] * inv);
+          *reinterpret_cast<u32x2*>(dst + dd) = w;
+        }
+      }
+    if (lse_out && h == 0) lse_out[slab + qidx] = (m + __log2f(lt)) * 0.6931471805599453f;
+  }
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                            const int* __restrict__ cu, const int* __restrict__ work, const bf16_t* __restrict__ ctx,
+                                                            const bf16_t* __restrict__ dctx, const float* __restrict__ lse, float* __restrict__ delta,
+                                                            const float* __restrict__ cosT, const float* __restrict__ sinT, float q_scale,
+                                                            bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
+  typedef Cfg<HD> C;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* sK = smem;
+  unsigned char* sV = sK + KC * C::ROWB;
+  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);
+  int head;
+  VarSeg sg;
+  if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
+  const int L = sg.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+  const int qidx = sg.blk * 128 + wave * 32 + (lane & 31);
+  const int qrow = qidx < L ? qidx : L - 1;
+  const int dm = H * HD;
+  const size_t slab = (size_t)head * T_pad + sg.start;
+  const size_t tok = (size_t)sg.start + qrow;                    // token row of this lane's query
+  const bf16_t* kbase = k + slab * HD;
+  const bf16_t* vbase = v + slab * HD;
+  bf8_t qf[C::KSTEPS], dof[C::KSTEPS];
+#pragma unroll
+  for (int st = 0; st < C::KSTEPS; ++st) {
+    qf[st] = *reinterpret_cast<const bf8_t*>(q + (slab + qrow) * HD + 16 * st + 8 * h);
+    dof[st] = *reinterpret_cast<const bf8_t*>(dctx + tok * dm + head * HD + 16 * st + 8 * h);
+  }
+  const float lse_q = lse[slab + qrow] * LOG2E;
+  float delta_q = 0.f;
+#pragma unroll
+  for (int st = 0; st < C::KSTEPS; ++st) {
+    const u32x4 x = *reinterpret_cast<const u32x4*>(ctx + tok * dm + head * HD + 16 * st + 8 * h), y = __builtin_bit_cast(u32x4, dof[st]);
+    delta_q += bflo(x.x) * bflo(y.x) + bfhi(x.x) * bfhi(y.x) + bflo(x.y) * bflo(y.y) + bfhi(x.y) * bfhi(y.y) + bflo(x.z) * bflo(y.z) + bfhi(x.z) * bfhi(y.z) +
+               bflo(x.w) * bflo(y.w) + bfhi(x.w) * bfhi(y.w);
+  }
+  delta_q += __shfl_xor(delta_q, 32, 64);
+  if (h == 0 && qidx < L) delta[slab + qidx] = delta_q;
+  u32x4 qe = {0u, 0u, 0u, 0u}, de = {0u, 0u, 0u, 0u}, ones3 = {0u, 0u, 0u, 0u};
+  if (h == 0) {
+    unsigned w01, w2;
+    split3_bf16(-lse_q, w01, w2); qe.x = w01; qe.y = w2 | 0x3F800000u;
+    split3_bf16(-delta_q, w01, w2); de.x = w01; de.y = w2;
+    ones3.x = 0x3F803F80u; ones3.y = 0x00003F80u;
+  }
+  f32x16 acc[C::DBLK];
+#pragma unroll
+  for (int d = 0; d < C::DBLK; ++d) acc[d] = zero16();
+  for (int kc0 = 0; kc0 < L; kc0 += KC) {
+    const int nkeys = min(KC, L - kc0);
+    const int nrows = (nkeys + 31) & ~31;
+    __syncthreads();
+    load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
+    for (int i = threadIdx.x; i <= KC; i += 256) {
+      u32x4 e = {0u, 0u, 0u, 0u};
+      if (i < nrows) {
+        const float bv = i < nkeys ? 0.f : -INFINITY;
+        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
+      }
+      sE[i] = e;
+    }
+    __syncthreads();
+    for (int t = 0; t < nrows / 32; ++t) {
+      const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
+      f32x16 s = MFMA32(__builtin_bit_cast(bf8_t, ke), __builtin_bit_cast(bf8_t, qe), zero16());
+      f32x16 dp = MFMA32(__builtin_bit_cast(bf8_t, ones3), __builtin_bit_cast(bf8_t, de), zero16());
+#pragma unroll
+      for (int st = 0; st < C::KSTEPS; ++st) {
+        s = MFMA32(rd_row<HD>(sK, t * 32 + (lane & 31), st, h), qf[st], s);
+        dp = MFMA32(rd_row<HD>(sV, t * 32 + (lane & 31), st, h), dof[st], dp);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]) * dp[r];
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+        const bf8_t dsf = pack8(s, sb);
+#pragma unroll
+        for (int d = 0; d < C::DBLK; ++d) acc[d] = MFMA32(rd_tr<HD>(sK, t * 32, sb, d, lane), dsf, acc[d]);
+      }
+    }
+  }
+  // the gathered rotary tables are per token: row = the token's row in the stream
+  if (qidx < L) unrope_store<HD>(acc, cosT, sinT, sg.start + qidx, h, q_scale, cosT != nullptr, dqkv + ((size_t)sg.start + qidx) * (3 * dm) + head * HD);
+}
+
+template <int HD>
+__global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dkv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                             const int* __restrict__ cu, const int* __restrict__ work, const bf16_t* __restrict__ dctx,
+                                                             const float* __restrict__ lse, const float* __restrict__ delta, const float* __restrict__ cosT,
+                                                             const float* __restrict__ sinT, bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
+  typedef Cfg<HD> C;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* sQ = smem;
+  unsigned char* sdO = sQ + KC * C::ROWB;
+  u32x4* sQE = reinterpret_cast<u32x4*>(sdO + KC * C::ROWB);
+  int head;
+  VarSeg sg;
+  if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
+  const int L = sg.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+  const int kidx = sg.blk * 128 + wave * 32 + (lane & 31);
+  const int krow = kidx < L ? kidx : L - 1;
+  const int dm = H * HD;
+  const size_t slab = (size_t)head * T_pad + sg.start;
+  bf8_t kf[C::KSTEPS], vf[C::KSTEPS];
+#pragma unroll
+  for (int st = 0; st < C::KSTEPS; ++st) {
+    kf[st] = *reinterpret_cast<const bf8_t*>(k + (slab + krow) * HD + 16 * st + 8 * h);
+    vf[st] = *reinterpret_cast<const bf8_t*>(v + (slab + krow) * HD + 16 * st + 8 * h);
+  }
+  const float bias_k = kidx < L ? 0.f : -INFINITY;
+  u32x4 kS = {0u, 0u, 0u, 0u}, kD = {0u, 0u, 0u, 0u};
+  if (h == 0) { kS.x = 0x3F803F80u; kS.y = 0x3F80u | (pack2bf(bias_k, 0.f) << 16); kD.z = 0x3F803F80u; kD.w = 0x00003F80u; }
+  f32x16 adk[C::DBLK], adv[C::DBLK];
+#pragma unroll
+  for (int d = 0; d < C::DBLK; ++d) { adk[d] = zero16(); adv[d] = zero16(); }
+  for (int qc0 = 0; qc0 < L; qc0 += KC) {
+    const int nq = min(KC, L - qc0);
+    const int nrows = (nq + 31) & ~31;
+    __syncthreads();
+    load_tile_pair<HD>(sQ, q + (slab + qc0) * HD, HD, sdO, dctx + ((size_t)sg.start + qc0) * dm + head * HD, dm, nq, nrows);
+    for (int i = threadIdx.x; i <= KC; i += 256) {
+      u32x4 e = {0u, 0u, 0u, 0u};
+      if (i < nrows) {
+        unsigned w01, w2;
+        split3_bf16(i < nq ? -lse[slab + qc0 + i] * LOG2E : -1.0e30f, w01, w2);
+        e.x = w01; e.y = w2 | 0x3F800000u;
+        split3_bf16(i < nq ? -delta[slab + qc0 + i] : 0.f, w01, w2);
+        e.z = w01; e.w = w2;
+      }
+      sQE[i] = e;
+    }
+    __syncthreads();
+    for (int t = 0; t < nrows / 32; ++t) {
+      const bf8_t qe_row = __builtin_bit_cast(bf8_t, sQE[h ? KC : t * 32 + (lane & 31)]);
+      f32x16 s = MFMA32(qe_row, __builtin_bit_cast(bf8_t, kS), zero16());
+      f32x16 dp = MFMA32(qe_row, __builtin_bit_cast(bf8_t, kD), zero16());
+#pragma unroll
+      for (int st = 0; st < C::KSTEPS; ++st) {
+        s = MFMA32(rd_row<HD>(sQ, t * 32 + (lane & 31), st, h), kf[st], s);
+        dp = MFMA32(rd_row<HD>(sdO, t * 32 + (lane & 31), st, h), vf[st], dp);
+      }
+      f32x16 p;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r]); s[r] = p[r] * dp[r]; }
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+        const bf8_t pf = pack8(p, sb), dsf = pack8(s, sb);
+#pragma unroll
+        for (int d = 0; d < C::DBLK; ++d) {
+          adv[d] = MFMA32(rd_tr<HD>(sdO, t * 32, sb, d, lane), pf, adv[d]);
+          adk[d] = MFMA32(rd_tr<HD>(sQ, t * 32, sb, d, lane), dsf, adk[d]);
+        }
+      }
+    }
+  }
+  if (kidx < L) {
+    bf16_t* row = dqkv + ((size_t)sg.start + kidx) * (3 * dm) + head * HD;
+    unrope_store<HD>(adk, cosT, sinT, sg.start + kidx, h, 0.6931471805599453f, cosT != nullptr, row + dm);
+    unrope_store<HD>(adv, cosT, sinT, sg.start + kidx, h, 1.0f, false, row + 2 * dm);
+  }
+}
+
+// rows [cu[N], T_pad) of a bf16 [T_pad, width] tensor (width % 8 == 0) and, optionally, of the H rows of an fp32 [H, T_pad] tensor are set to zero
+__global__ void __launch_bounds__(256) k_varlen_tail_zero(const int* __restrict__ cu, int N, int T_pad, bf16_t* __restrict__ rows, int width,
+                                                          float* __restrict__ per_head, int H) {
+  const int t0 = min(max(cu[N], 0), T_pad);
+  const size_t nvec = (size_t)(T_pad - t0) * (width / 8);
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256)
+    reinterpret_cast<u32x4*>(rows + (size_t)t0 * width)[i] = z;
+  if (per_head) {
+    const size_t n = (size_t)(T_pad - t0) * H;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+      const size_t hh = i / (T_pad - t0), t = i - hh * (T_pad - t0);
+      per_head[hh * T_pad + t0 + t] = 0.f;
+    }
+  }
+}
+
+static bool varlen_args_ok(const void* cu, const void* work, int n_work, int N, int T_pad, int H) {
+  return cu && work && n_work > 0 && N > 0 && H > 0 && T_pad > 0 && (T_pad % 8) == 0 && (long)n_work * H < 0x7fffffffL;
+}
+
+extern "C" int oneprot_attn_varlen_fwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse,
+                                       int N, int T_pad, int H, int hd, void* stream) {
+  if (!q || !k || !v || !ctx || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H)) return OP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_varlen_tail_zero, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, (bf16_t*)ctx, H * hd, lse, H);
+  const dim3 grid((unsigned)(n_work * H));
+  switch (hd) {
+#define VL_FWD(D) case D: hipLaunchKernelGGL(k_attn_varlen_fwd<D>, grid, dim3(256), fwd_lds<D>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, \
+                                             cu_seqlens, work, (bf16_t*)ctx, lse, N, T_pad, H); break;
+    VL_FWD(16) VL_FWD(32) VL_FWD(64)
+#undef VL_FWD
+    default: return OP_EINVAL;
+  }
+  return launch_status();
+}
+
+extern "C" size_t oneprot_attn_varlen_bwd_workspace(int H, int T_pad) { return (size_t)H * T_pad * sizeof(float); }
+
+extern "C" int oneprot_attn_varlen_bwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
+                                       const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
+                                       void* workspace, int N, int T_pad, int H, int hd, void* stream) {
+  if (!q || !k || !v || !ctx || !dctx || !lse || !dqkv || !workspace || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H)) return OP_EINVAL;
+  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return OP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* delta = (float*)workspace;
+  hipLaunchKernelGGL(k_varlen_tail_zero, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, (bf16_t*)dqkv, 3 * H * hd, (float*)nullptr, H);
+  const dim3 grid((unsigned)(n_work * H));
+  switch (hd) {
+#define VL_BWD(D) case D: { const size_t lds = fwd_lds<D>();                                                                                      \
+      hipLaunchKernelGGL(k_attn_varlen_bwd_dq<D>, grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens, work,      \
+                         (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, rope_cos, rope_sin, q_scale, (bf16_t*)dqkv, N, T_pad, H);                 \
+      hipLaunchKernelGGL(k_attn_varlen_bwd_dkv<D>, grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens, work,     \
+                         (const bf16_t*)dctx, lse, (const float*)delta, rope_cos, rope_sin, (bf16_t*)dqkv, N, T_pad, H); } break;
+    VL_BWD(16) VL_BWD(32) VL_BWD(64)
+#undef VL_BWD
+    default: return OP_EINVAL;
+  }
+  return launch_status();
+}

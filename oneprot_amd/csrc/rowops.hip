@@ -67,6 +67,83 @@ extern "C" int oneprot_esm_embed_fwd(const int64_t* ids, const float* table, flo
   return launch_status();
 }
 
+// Packed embedding (the same arithmetic per sequence; sequence b = rows [cu[b], cu[b+1]) of the stream, work-group row N = the tail, whose pad ids give
+// zero rows and tok_scale 0).  The token-dropout factor is counted per sequence and kept per token (tok_scale [T_pad]: the row_scale of the backward
+// with L = 1).  Also gathers the rotary tables per token: cos_out[t] = rope_cos[position of t within its sequence] ([T_pad, half]; tail rows take
+// position 0), the form the QKV GEMM's rotary epilogue reads with B = 1, L = T_pad.
+__global__ void __launch_bounds__(256) k_embed_packed_fwd(const long long* __restrict__ ids, const int* __restrict__ cu, const float* __restrict__ W,
+                                                          const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, float* __restrict__ x,
+                                                          float* __restrict__ tok_scale, float* __restrict__ cos_out, float* __restrict__ sin_out, int N, int T_pad,
+                                                          int d, int vocab, int half, int n_pos, int pad_id, int mask_id, int token_dropout, int tok_per_block) {
+  const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+  const bool tail = b == N;
+  const int base = cu[b], L = (tail ? T_pad : cu[b + 1]) - base;
+  if (L <= 0 || base < 0 || base + L > T_pad) return;
+  __shared__ float s_cnt[2][4];
+  __shared__ float s_scale;
+  float nvalid = 0.f, nmask = 0.f;
+  for (int l = tid; l < L; l += 256) {
+    const long long id = ids[(size_t)base + l];
+    nvalid += (id != pad_id);
+    nmask += (id == mask_id);
+  }
+  nvalid = wave_sum(nvalid); nmask = wave_sum(nmask);
+  if ((tid & 63) == 0) { s_cnt[0][tid >> 6] = nvalid; s_cnt[1][tid >> 6] = nmask; }
+  __syncthreads();
+  if (tid == 0) {
+    const float nv = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
+    const float nm = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
+    float sc = 1.0f;
+    if (token_dropout && nv > 0.f) sc = (1.0f - 0.15f * 0.8f) / (1.0f - nm / nv);
+    s_scale = tail ? 0.f : sc;
+  }
+  __syncthreads();
+  const float sc = s_scale;
+  const int nv4 = d >> 2;
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int l0 = chunk * tok_per_block; l0 < L; l0 += gridDim.x * tok_per_block)      // (the tail may be longer than max_len)
+  for (int l = l0 + wave; l < min(L, l0 + tok_per_block); l += 4) {
+    const size_t t = (size_t)base + l;
+    const long long id = ids[t];
+    const bool zero = (id == pad_id) || (token_dropout && id == mask_id) || id < 0 || id >= vocab;
+    const float4* src = reinterpret_cast<const float4*>(W + (size_t)(zero ? 0 : id) * d);
+    float4* dst = reinterpret_cast<float4*>(x + t * d);
+    for (int v = lane; v < nv4; v += 64) {
+      float4 e = src[v];
+      if (zero) e = make_float4(0.f, 0.f, 0.f, 0.f);
+      else { e.x *= sc; e.y *= sc; e.z *= sc; e.w *= sc; }
+      dst[v] = e;
+    }
+    const int pos = tail ? 0 : min(l, n_pos - 1);
+    for (int j = lane; j < half; j += 64) {
+      cos_out[t * half + j] = rope_cos[(size_t)pos * half + j];
+      sin_out[t * half + j] = rope_sin[(size_t)pos * half + j];
+    }
+    if (lane == 0) tok_scale[t] = sc;
+  }
+}
+
+extern "C" int oneprot_esm_embed_packed_fwd(const int64_t* ids, const int* cu_seqlens, const float* table, const float* rope_cos, const float* rope_sin, float* x,
+                                            float* tok_scale, float* cos_out, float* sin_out, int N, int T_pad, int max_len, int d, int vocab, int half, int n_pos,
+                                            int pad_id, int mask_id, int token_dropout, void* stream) {
+  if (!ids || !cu_seqlens || !table || !rope_cos || !rope_sin || !x || !tok_scale || !cos_out || !sin_out || N <= 0 || T_pad <= 0 || max_len <= 0 ||
+      max_len > n_pos || d <= 0 || (d & 3) || half <= 0)
+    return OP_EINVAL;
+  const int tpb = 32;
+  dim3 grid((max_len + tpb - 1) / tpb, N + 1);
+  hipLaunchKernelGGL(k_embed_packed_fwd, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)ids, cu_seqlens, table, rope_cos, rope_sin, x, tok_scale,
+                     cos_out, sin_out, N, T_pad, d, vocab, half, n_pos, pad_id, mask_id, token_dropout, tpb);
+  return launch_status();
+}
+
+// dtable[id] (+)= sum over the stream of tok_scale[t] * dx[t] for valid, non-mask tokens (the padded kernel with L = 1: the scale is per token; the tail's
+// pad ids are skipped).  Workspace: oneprot_esm_embed_bwd_workspace(T_pad, d, vocab).
+extern "C" int oneprot_esm_embed_packed_bwd(const int64_t* ids, const float* dx, const float* tok_scale, float* dtable, void* workspace, int T_pad, int d, int vocab,
+                                            int pad_id, int mask_id, int token_dropout, int accumulate, void* stream) {
+  if (!tok_scale) return OP_EINVAL;
+  return oneprot_esm_embed_bwd(ids, dx, tok_scale, dtable, workspace, T_pad, 1, d, vocab, pad_id, mask_id, token_dropout, accumulate, stream);
+}
+
 // Embedding backward for small vocabularies (ESM: 33 / 54 rows): per-block private accumulators in LDS
 // (one thread per column => no atomics), partial tables to a workspace, then k_colsum_partials reduces.
 // dW[id] += row_scale[b] * dx[b,l,:]  for valid, non-mask tokens.
@@ -243,7 +320,8 @@ extern "C" int oneprot_layernorm_fwd(const void* x, int x_is_bf16, const float* 
 template <int DY_MODE, int X_BF16, int NV>
 __global__ void __launch_bounds__(256) k_layernorm_bwd(const void* __restrict__ dy, const float* __restrict__ wrow, int L, const void* __restrict__ x,
                                                        const float* __restrict__ gamma, const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                                                       const float* add_to, float* dx_out, bf16_t* __restrict__ dx_bf16, float* __restrict__ partial, int T, int d) {
+                                                       const float* add_to, float* dx_out, bf16_t* __restrict__ dx_bf16, float* __restrict__ partial, int T, int d,
+                                                       const int* __restrict__ cu = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float s_part[];     // [4 waves][2][d]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv4 = d >> 2;
@@ -257,7 +335,13 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const void* __restrict__ 
   for (int row = blockIdx.x * ROWS_PER_BLOCK + wave; row < T; row += gridDim.x * ROWS_PER_BLOCK) {
     const float mean = mean_in[row], rstd = rstd_in[row];
     float w = 1.0f;
-    if (DY_MODE == 2) w = wrow[row];
+    size_t dyrow = (size_t)row / (DY_MODE == 2 ? L : 1);
+    if (DY_MODE >= 2) w = wrow[row];
+    if (DY_MODE == 3) {                  // packed stream: the sequence of `row` by bisection of cu_seqlens [L + 1] (tail rows: weight 0, any sequence)
+      int lo = 0, hi = L - 1;
+      while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (cu[mid] <= row) lo = mid; else hi = mid - 1; }
+      dyrow = lo;
+    }
     float4 xh[NV], g[NV];
 #ifndef LN_BWD_LATE_ADD
     // the residual-gradient rows are requested together with x and dy: one exposed round trip per row instead of two (they are only needed after
@@ -290,7 +374,7 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const void* __restrict__ 
         } else if (DY_MODE == 1) {
           dyv = reinterpret_cast<const float4*>((const float*)dy + (size_t)row * d)[c];
         } else {
-          dyv = reinterpret_cast<const float4*>((const float*)dy + (size_t)(row / L) * d)[c];
+          dyv = reinterpret_cast<const float4*>((const float*)dy + dyrow * d)[c];
           dyv.x *= w; dyv.y *= w; dyv.z *= w; dyv.w *= w;
         }
         xh[i] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
@@ -395,6 +479,29 @@ extern "C" int oneprot_layernorm_bwd(const void* dy, int dy_mode, const float* w
   return launch_status();
 }
 
+// Packed stream (oneprot_lnpool_packed_fwd): the final LayerNorm's backward from the pooled gradient, dy[t] = dpooled[seq(t)] * wrow[t] (seq(t) by
+// bisection of cu_seqlens; the tail rows carry wrow = 0, so their dx rows are exactly zero).  x fp32 [T_pad, d].
+extern "C" int oneprot_lnpool_packed_bwd(const float* dpooled, const int* cu_seqlens, const float* wrow, const float* x, const float* gamma, const float* mean,
+                                         const float* rstd, float* dx, void* dx_bf16, float* dgamma, float* dbeta, void* workspace, int N, int T_pad, int d,
+                                         void* stream) {
+  if (!dpooled || !cu_seqlens || !wrow || !x || !gamma || !mean || !rstd || !dx || N <= 0 || T_pad <= 0 || (d & 3) || d > MAXV * 256) return OP_EINVAL;
+  if ((dgamma || dbeta) && !(dgamma && dbeta && workspace)) return OP_EINVAL;
+  int blocks = (T_pad + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+  if (blocks > LN_BWD_BLOCKS) blocks = LN_BWD_BLOCKS;
+  float* partial = dgamma ? (float*)workspace : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const int nv = (d / 4 + 63) / 64;
+  const size_t lds = partial ? (size_t)4 * 2 * d * sizeof(float) : 0;
+  if (lds > 64 * 1024) return OP_EINVAL;
+#define LAUNCH_LNP(NV) hipLaunchKernelGGL((k_layernorm_bwd<3, 0, NV>), dim3(blocks), dim3(256), lds, s, dpooled, wrow, N, x, gamma, mean, rstd, (const float*)nullptr, dx, \
+                                          (bf16_t*)dx_bf16, partial, T_pad, d, cu_seqlens)
+  if (nv <= 1) LAUNCH_LNP(1); else if (nv == 2) LAUNCH_LNP(2); else if (nv == 3) LAUNCH_LNP(3); else if (nv == 4) LAUNCH_LNP(4); else if (nv == 5) LAUNCH_LNP(5); else LAUNCH_LNP(8);
+#undef LAUNCH_LNP
+  if (dgamma)
+    hipLaunchKernelGGL(k_ln_reduce, dim3((2 * d + 15) / 16), dim3(1024), 0, s, (const float*)workspace, dgamma, dbeta, blocks, d, 0);
+  return launch_status();
+}
+
 // --------------------------------------------------------------------------------------------------------
 // Fused final LayerNorm + pooling forward (hf modeling_esm.py:552 + ref base_encoder.py:109-126).
 //   mode 0 (mean): pooled[b] = sum_l valid[b,l] * LN(x[b,l]) / n_valid[b]   -- CLS/EOS included
@@ -403,17 +510,29 @@ extern "C" int oneprot_layernorm_bwd(const void* dy, int dy_mode, const float* w
 // accumulators are combined through LDS.  Also emits mean/rstd per token and wrow[t] = valid/n_valid (mode 0) or [l==0]
 // (mode 1), which is exactly the pooled-gradient broadcast weight used by oneprot_layernorm_bwd(dy_mode=2).
 // --------------------------------------------------------------------------------------------------------
+// VAR (packed stream, oneprot_lnpool_packed_fwd): sequence b is rows [cu[b], cu[b+1]) of the stream; work-group N is the tail [cu[N], T_pad): its rows get
+// their statistics and hidden state (finite: pad embeddings) with weight 0, and no pooled row.
+template <bool VAR>
 __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, int pad_id, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float* __restrict__ pooled, float* __restrict__ mean_out,
                                                     float* __restrict__ rstd_out, float* __restrict__ wrow, bf16_t* __restrict__ hidden_bf16,
-                                                    float* __restrict__ hidden_f32, int L, int d, float eps, int mode) {
+                                                    float* __restrict__ hidden_f32, int L, int d, float eps, int mode, const int* __restrict__ cu = nullptr,
+                                                    int N = 0) {
   extern __shared__ __attribute__((aligned(16))) float s_pool[];    // [8][d]
   __shared__ float s_n[8];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv4 = d >> 2;
   const float inv_d = 1.0f / (float)d;
+  size_t base = (size_t)b * L;                       // stream row of the sequence's first token
+  bool tail = false;
+  if constexpr (VAR) {                               // (L is T_pad here)
+    tail = b == N;
+    base = (size_t)cu[b];
+    L = (tail ? L : cu[b + 1]) - cu[b];
+    if (L <= 0) return;
+  }
   float cnt = 0.f;
-  for (int l = threadIdx.x; l < L; l += 512) cnt += (ids[(size_t)b * L + l] != pad_id);
+  for (int l = threadIdx.x; l < L; l += 512) cnt += (ids[base + l] != pad_id);
   cnt = wave_sum(cnt);
   if (lane == 0) s_n[wave] = cnt;
   __syncthreads();
@@ -423,14 +542,14 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
   float4 acc[MAXV];
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) acc[i] = make_float4(0, 0, 0, 0);
-  const int lend = (mode == 1 && !hidden_bf16 && !hidden_f32 && !mean_out) ? 1 : L;
+  const int lend = (mode == 1 && !hidden_bf16 && !hidden_f32 && !mean_out && !tail) ? 1 : L;
   // the NEXT row of the wave is requested before this row's two wave reductions (a wave walks 64 rows of its sequence one after the other: without
   // the prefetch every row paid a memory round trip on top of the reductions -- 260 us per launch at cfg-2)
   float4 vn[MAXV];
   bool validn = false;
   auto request = [&](int l) {
     if (l < lend) {
-      const size_t row = (size_t)b * L + l;
+      const size_t row = base + l;
       validn = ids[row] != pad_id;
 #pragma unroll
       for (int i = 0; i < MAXV; ++i) {
@@ -441,9 +560,10 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
   };
   request(wave);
   for (int l = wave; l < lend; l += 8) {
-    const size_t row = (size_t)b * L + l;
+    const size_t row = base + l;
     const bool valid = validn;
-    const float wt = (mode == 0) ? (valid ? inv_n : 0.f) : (l == 0 ? 1.f : 0.f);
+    float wt = (mode == 0) ? (valid ? inv_n : 0.f) : (l == 0 ? 1.f : 0.f);
+    if (VAR && tail) wt = 0.f;
     float4 v[MAXV];
     float s = 0.f;
 #pragma unroll
@@ -486,6 +606,7 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
     if (c < nv4) reinterpret_cast<float4*>(s_pool + (size_t)wave * d)[c] = acc[i];
   }
   __syncthreads();
+  if (VAR && tail) return;
   for (int j = threadIdx.x; j < d; j += 512) {
     float s = 0.f;
 #pragma unroll
@@ -497,8 +618,18 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
 extern "C" int oneprot_lnpool_fwd(const float* x, const int64_t* ids, int pad_id, const float* gamma, const float* beta, float* pooled, float* mean,
                                   float* rstd, float* wrow, void* hidden_bf16, float* hidden_f32, int B, int L, int d, float eps, int mode, void* stream) {
   if (!x || !ids || !gamma || !beta || !pooled || (d & 3) || d > MAXV * 256 || mode < 0 || mode > 1) return OP_EINVAL;
-  hipLaunchKernelGGL(k_lnpool_fwd, dim3(B), dim3(512), (size_t)8 * d * sizeof(float), (hipStream_t)stream, x, (const long long*)ids, pad_id, gamma, beta, pooled,
+  hipLaunchKernelGGL(k_lnpool_fwd<false>, dim3(B), dim3(512), (size_t)8 * d * sizeof(float), (hipStream_t)stream, x, (const long long*)ids, pad_id, gamma, beta, pooled,
                      mean, rstd, wrow, (bf16_t*)hidden_bf16, hidden_f32, L, d, eps, mode);
+  return launch_status();
+}
+
+// Packed stream: N sequences in rows [cu[b], cu[b+1]) of x fp32 [T_pad, d], ids int64 [T_pad]; work-group N handles the tail rows (statistics, wrow = 0,
+// no pooled row).  mean / rstd / wrow are per stream row, the inputs of oneprot_lnpool_packed_bwd.
+extern "C" int oneprot_lnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* gamma, const float* beta, float* pooled,
+                                         float* mean, float* rstd, float* wrow, float* hidden_f32, int N, int T_pad, int d, float eps, int mode, void* stream) {
+  if (!x || !ids || !cu_seqlens || !gamma || !beta || !pooled || N <= 0 || T_pad <= 0 || (d & 3) || d > MAXV * 256 || mode < 0 || mode > 1) return OP_EINVAL;
+  hipLaunchKernelGGL(k_lnpool_fwd<true>, dim3(N + 1), dim3(512), (size_t)8 * d * sizeof(float), (hipStream_t)stream, x, (const long long*)ids, pad_id, gamma, beta,
+                     pooled, mean, rstd, wrow, (bf16_t*)nullptr, hidden_f32, T_pad, d, eps, mode, cu_seqlens, N);
   return launch_status();
 }
 
@@ -758,13 +889,21 @@ __device__ __forceinline__ float ap_block_sum(float v, float* s_red, int lane, i
   return t;
 }
 
+// VAR (oneprot_attnpool_packed_fwd / _bwd): sequence b is rows [cu[b], cu[b+1]) of a packed stream; the LDS is sized for the longest (L = max_len)
+template <bool VAR>
 __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, int pad_id, const float* __restrict__ w,
-                                                                const float* __restrict__ bias, float* __restrict__ pooled, float* __restrict__ attn, int L, int d) {
+                                                                const float* __restrict__ bias, float* __restrict__ pooled, float* __restrict__ attn, int L, int d,
+                                                                const int* __restrict__ cu = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float s_a[];      // [L rounded to 4] weights, then [groups][d] partial sums
   __shared__ float s_red[AP_WAVES];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* xb = x + (size_t)b * L * d;
-  const long long* idb = ids + (size_t)b * L;
+  size_t base = (size_t)b * L;
+  if constexpr (VAR) {
+    base = (size_t)cu[b];
+    L = min(cu[b + 1] - cu[b], L);
+  }
+  const float* xb = x + base * d;
+  const long long* idb = ids + base;
   const float bs = bias[0];
   ap_row_dots(xb, w, L, d, lane, wave, [&](int l, float s) { s_a[l] = (idb[l] != pad_id) ? s + bs : -INFINITY; });
   __syncthreads();
@@ -778,27 +917,33 @@ __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_fwd(const float* __r
   float se = 0.f;
   for (int l = threadIdx.x; l < L; l += AP_WAVES * 64) { const float e = __expf(s_a[l] - mx); s_a[l] = e; se += e; }
   const float inv = 1.0f / ap_block_sum(se, s_red, lane, wave);
-  for (int l = threadIdx.x; l < L; l += AP_WAVES * 64) { const float a = s_a[l] * inv; s_a[l] = a; if (attn) attn[(size_t)b * L + l] = a; }
+  for (int l = threadIdx.x; l < L; l += AP_WAVES * 64) { const float a = s_a[l] * inv; s_a[l] = a; if (attn) attn[base + l] = a; }
   __syncthreads();
   ap_weighted_sum<false>(xb, s_a, s_a + ((L + 3) & ~3), pooled + (size_t)b * d, L, d, lane, wave, nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int oneprot_attnpool_fwd(const float* x, const int64_t* ids, int pad_id, const float* w, const float* bias, float* pooled, float* attn, int B, int L,
                                     int d, void* stream) {
   if (!x || !ids || !w || !bias || !pooled || B <= 0 || L <= 0 || (d & 3) || ap_lds_bytes(L, d) > 60 * 1024) return OP_EINVAL;
-  hipLaunchKernelGGL(k_attnpool_fwd, dim3(B), dim3(AP_WAVES * 64), ap_lds_bytes(L, d), (hipStream_t)stream, x, (const long long*)ids, pad_id, w, bias, pooled, attn, L, d);
+  hipLaunchKernelGGL(k_attnpool_fwd<false>, dim3(B), dim3(AP_WAVES * 64), ap_lds_bytes(L, d), (hipStream_t)stream, x, (const long long*)ids, pad_id, w, bias, pooled, attn, L, d);
   return launch_status();
 }
 // backward: da_l = x_l . dp ; ds = a * (da - sum a da) ; dw_partial[b] = sum_l ds_l x_l ; db_partial[b] = sum_l ds_l ;
 //           dx_l = a_l dp + ds_l w (optional)
+template <bool VAR>
 __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_bwd(const float* __restrict__ x, const float* __restrict__ attn, const float* __restrict__ w,
                                                                 const float* __restrict__ dpooled, float* __restrict__ dw_part, float* __restrict__ db_part,
-                                                                float* __restrict__ dx, int L, int d) {
+                                                                float* __restrict__ dx, int L, int d, const int* __restrict__ cu = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float s_ds[];     // [L rounded to 4], then [groups][d] partial sums
   __shared__ float s_red[AP_WAVES];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* xb = x + (size_t)b * L * d;
+  size_t base = (size_t)b * L;
+  if constexpr (VAR) {
+    base = (size_t)cu[b];
+    L = min(cu[b + 1] - cu[b], L);
+  }
+  const float* xb = x + base * d;
   const float* dp = dpooled + (size_t)b * d;
-  const float* ab = attn + (size_t)b * L;
+  const float* ab = attn + base;
   ap_row_dots(xb, dp, L, d, lane, wave, [&](int l, float s) { s_ds[l] = s; });
   __syncthreads();
   float dot = 0.f;
@@ -809,19 +954,49 @@ __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_bwd(const float* __r
   dbs = ap_block_sum(dbs, s_red, lane, wave);                       // (its barriers also publish s_ds)
   if (threadIdx.x == 0) db_part[b] = dbs;
   float* part = s_ds + ((L + 3) & ~3);
-  if (dx) ap_weighted_sum<true>(xb, s_ds, part, dw_part + (size_t)b * d, L, d, lane, wave, ab, dp, w, dx + (size_t)b * L * d);
+  if (dx) ap_weighted_sum<true>(xb, s_ds, part, dw_part + (size_t)b * d, L, d, lane, wave, ab, dp, w, dx + base * d);
   else    ap_weighted_sum<false>(xb, s_ds, part, dw_part + (size_t)b * d, L, d, lane, wave, nullptr, nullptr, nullptr, nullptr);
 }
 extern "C" int oneprot_attnpool_bwd(const float* x, const float* attn, const float* w, const float* dpooled, float* dw, float* db, float* dx, void* workspace,
                                     int B, int L, int d, void* stream) {
   if (!x || !attn || !w || !dpooled || !dw || !db || !workspace || B <= 0 || L <= 0 || (d & 3) || ap_lds_bytes(L, d) > 60 * 1024) return OP_EINVAL;
   float* part = (float*)workspace;              // [B][d] dw partials then [B] db partials
-  hipLaunchKernelGGL(k_attnpool_bwd, dim3(B), dim3(AP_WAVES * 64), ap_lds_bytes(L, d), (hipStream_t)stream, x, attn, w, dpooled, part, part + (size_t)B * d, dx, L, d);
+  hipLaunchKernelGGL(k_attnpool_bwd<false>, dim3(B), dim3(AP_WAVES * 64), ap_lds_bytes(L, d), (hipStream_t)stream, x, attn, w, dpooled, part, part + (size_t)B * d, dx, L, d);
   hipLaunchKernelGGL(k_reduce_partials, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)part, dw, B, (size_t)d, 0);
   hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)(part + (size_t)B * d), db, B, (size_t)1, 0);
   return launch_status();
 }
 extern "C" size_t oneprot_attnpool_bwd_workspace(int B, int d) { return ((size_t)B * d + B) * sizeof(float); }
+
+// Packed stream: sequence b = rows [cu[b], cu[b+1]) of x / attn / dx ([T_pad, d], [T_pad], [T_pad, d]); max_len bounds every sequence (LDS size).
+// The backward writes zeros into the tail rows of dx [cu[N], T_pad).  Workspace: oneprot_attnpool_bwd_workspace(N, d).
+__global__ void __launch_bounds__(256) k_zero_tail_rows_f32(const int* __restrict__ cu, int N, int T_pad, float* __restrict__ x, int d) {
+  const int t0 = min(max(cu[N], 0), T_pad);
+  const size_t n4 = (size_t)(T_pad - t0) * (d / 4);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+    reinterpret_cast<float4*>(x + (size_t)t0 * d)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+extern "C" int oneprot_attnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* w, const float* bias, float* pooled,
+                                           float* attn, int N, int max_len, int d, void* stream) {
+  if (!x || !ids || !cu_seqlens || !w || !bias || !pooled || N <= 0 || max_len <= 0 || (d & 3) || ap_lds_bytes(max_len, d) > 60 * 1024) return OP_EINVAL;
+  hipLaunchKernelGGL(k_attnpool_fwd<true>, dim3(N), dim3(AP_WAVES * 64), ap_lds_bytes(max_len, d), (hipStream_t)stream, x, (const long long*)ids, pad_id, w, bias,
+                     pooled, attn, max_len, d, cu_seqlens);
+  return launch_status();
+}
+extern "C" int oneprot_attnpool_packed_bwd(const float* x, const float* attn, const int* cu_seqlens, const float* w, const float* dpooled, float* dw, float* db,
+                                           float* dx, void* workspace, int N, int T_pad, int max_len, int d, void* stream) {
+  if (!x || !attn || !cu_seqlens || !w || !dpooled || !dw || !db || !workspace || N <= 0 || T_pad <= 0 || max_len <= 0 || (d & 3) ||
+      ap_lds_bytes(max_len, d) > 60 * 1024)
+    return OP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  if (dx) hipLaunchKernelGGL(k_zero_tail_rows_f32, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, dx, d);
+  hipLaunchKernelGGL(k_attnpool_bwd<true>, dim3(N), dim3(AP_WAVES * 64), ap_lds_bytes(max_len, d), s, x, attn, w, dpooled, part, part + (size_t)N * d, dx, max_len, d,
+                     cu_seqlens);
+  hipLaunchKernelGGL(k_reduce_partials, dim3((d + 255) / 256), dim3(256), 0, s, (const float*)part, dw, N, (size_t)d, 0);
+  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, s, (const float*)(part + (size_t)N * d), db, N, (size_t)1, 0);
+  return launch_status();
+}
 
 // --------------------------------------------------------------------------------------------------------
 // casts / fills / column sums

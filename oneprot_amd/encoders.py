@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import hip
 from .esm import EsmTransformer, resolve_config, ModelConfig
+from .packing import PackedTokens
 
 
 # ------------------------------------------------------------------------------------------------- small modules
@@ -305,6 +306,8 @@ class _EncodeFn(torch.autograd.Function):
         if need_tr_grad:
             tr._live_apps = getattr(tr, "_live_apps", 0) + 1       # applications awaiting their backward (see backward: overlap guard)
         x, saved = tr.run_layers(ids, save=need_tr_grad)
+        if isinstance(ids, PackedTokens):
+            return _EncodeFn._forward_packed(ctx, enc, tr, ids, x, saved, need_tr_grad, need_any, n_extra, params)
         B, L = ids.shape
         d = tr.d
         dev = ids.device
@@ -347,6 +350,40 @@ class _EncodeFn(torch.autograd.Function):
         return feat
 
     @staticmethod
+    def _forward_packed(ctx, enc, tr, p, x, saved, need_tr_grad, need_any, n_extra, params):
+        """the pooling end of the forward on a packed stream: final LayerNorm + pooling per segment (pooled [N, d] in segment order)"""
+        N, T, d, dev = len(p), p.T_pad, tr.d, p.device
+        cfg = tr.config
+        pooled = torch.empty(N, d, device=dev)
+        mode = enc.pooling.mode
+        mean, rstd, wrow = (torch.empty(T, device=dev) for _ in range(3)) if need_tr_grad else (None, None, None)
+        hidden = attn = None
+        lnw, lnb = tr.view("encoder.emb_layer_norm_after.weight"), tr.view("encoder.emb_layer_norm_after.bias")
+        if mode == 2:
+            pw = enc.pooling.layer.weight
+            if pw.numel() != d:
+                raise RuntimeError(f"Attention1dPooling was built for hidden size {pw.numel()} but the encoder width is {d} "
+                                   "(the reference hard-codes 1280: base_encoder.py:180)")
+            hidden = torch.empty(T, d, device=dev)
+            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, hidden, N, T, d, cfg.layer_norm_eps, 0)
+            attn = torch.empty(T, device=dev)
+            hip.call("oneprot_attnpool_packed_fwd", hidden, p.ids, p.cu_seqlens, cfg.pad_token_id, pw, enc.pooling.layer.bias, pooled, attn, N, p.max_len, d)
+        else:
+            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, None, N, T, d, cfg.layer_norm_eps, mode)
+        learn = len(enc.norm) > 1 and enc.norm[1].learnable
+        scale_t, dscale_t = enc.norm[1].scale_device() if learn else (None, None)
+        scale = 1.0 if learn else enc.logit_scale_value()
+        feat, hst = _Head.forward(pooled, enc.proj, scale, need_any, scale_t)
+        ctx.enc, ctx.saved, ctx.hst, ctx.scale = enc, saved, hst, scale
+        ctx.scale_t, ctx.dscale_t = scale_t, dscale_t
+        ctx.fin = (mean, rstd, wrow)
+        ctx.pool = (hidden, attn) if (mode == 2 and need_any) else None
+        ctx.need_tr_grad = need_tr_grad
+        ctx.n_extra, ctx.n_params = n_extra, len(params)
+        ctx.ids = p
+        return feat
+
+    @staticmethod
     def backward(ctx, dfeat):
         enc, tr = ctx.enc, ctx.enc.transformer
         dev = dfeat.device
@@ -355,7 +392,17 @@ class _EncodeFn(torch.autograd.Function):
         extra_grads = []
         dhidden = None
         mode = enc.pooling.mode
-        if mode == 2:
+        packed = isinstance(ctx.ids, PackedTokens)
+        if mode == 2 and packed:
+            hidden, attn = ctx.pool
+            p, (T, d) = ctx.ids, hidden.shape
+            dw, db = torch.empty(d, device=dev), torch.empty(1, device=dev)
+            if ctx.need_tr_grad:
+                dhidden = torch.empty(T, d, device=dev)
+            hip.call("oneprot_attnpool_packed_bwd", hidden, attn, p.cu_seqlens, enc.pooling.layer.weight, dpooled, dw, db, dhidden,
+                     _ws(hip.query("oneprot_attnpool_bwd_workspace", len(p), d), dev), len(p), T, p.max_len, d)
+            extra_grads += [dw.view_as(enc.pooling.layer.weight), db]
+        elif mode == 2:
             hidden, attn = ctx.pool
             B, L, d = hidden.shape
             dw, db = torch.empty(d, device=dev), torch.empty(1, device=dev)
@@ -390,6 +437,9 @@ class _EncodeFn(torch.autograd.Function):
                     g.copy_(dhidden.view(B * L, d))
                 else:
                     hip.call("oneprot_pool_bwd", dpooled, ctx.ids, tr.config.pad_token_id, g, g16, B, L, d, mode)
+            elif packed and mode != 2:      # dy[t] = dpooled[segment of t] * wrow[t]
+                hip.call("oneprot_lnpool_packed_bwd", dpooled, ctx.ids.cu_seqlens, wrow, saved["x_final"], tr.view("encoder.emb_layer_norm_after.weight"), mean, rstd,
+                         g, g16, lnw, lnb, ws, len(ctx.ids), B * L, d)
             elif mode == 2:
                 hip.call("oneprot_layernorm_bwd", dhidden, 1, None, 0, saved["x_final"], 0, tr.view("encoder.emb_layer_norm_after.weight"), mean, rstd, None, g, g16,
                          lnw, lnb, ws, B * L, d, 0)
@@ -551,6 +601,9 @@ class BaseEncoder(nn.Module):
         return ps
 
     def encode(self, input_ids):
+        if isinstance(input_ids, PackedTokens) and not isinstance(self.transformer, EsmTransformer):
+            raise NotImplementedError(f"{type(self).__name__}: packed input is built for the ESM towers only (packed BERT -- absolute positions, token "
+                                      "types, post-LN -- is not); pass padded [B, L] ids")
         extra = self._extra_params()
         head_params = [p for p in self.proj.parameters()]
         return _EncodeFn.apply(self, input_ids, self.transformer.flat, len(extra), *extra, *head_params)
@@ -613,6 +666,8 @@ class StructEncoder(BaseEncoder):
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, batch):
+        if isinstance(batch, PackedTokens):
+            raise NotImplementedError("StructEncoder: packed token streams are an ESM-tower input; the graph encoder takes its own batch type")
         encoded = self.encoder(batch)
         encoded = self.dropout(encoded)
         return self.apply_head(encoded)

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .packing import PackedTokens
 
 KNOWN_ESM = {   # public facts of the ESM-2 checkpoints (SURVEY.md section 8 header)
     "esm2_t6_8M_UR50D": dict(num_hidden_layers=6, hidden_size=320, intermediate_size=1280),
@@ -477,6 +478,86 @@ class ArenaModule(nn.Module):
         save_file(sd, os.path.join(path, "model.safetensors"))
 
 
+class _PaddedLayout:
+    """The three layout-dependent stages of an ESM tower on a padded [B, L] batch: embedding (token-dropout factor per row), rotary tables (positions
+    0..L-1, the GEMM epilogue reads row % L) and attention (key-padding bias).  Everything else runs row-wise on the B*L rows."""
+    packed = False
+
+    def __init__(self, tr, ids):
+        self.ids = ids.contiguous()
+        self.B, self.L = ids.shape
+        self.T = self.B * self.L
+        self.cos, self.sin = tr._rope(self.L)
+
+    def embed(self, tr, x):
+        cfg, dev = tr.config, x.device
+        self.key_bias = torch.empty(self.B, self.L, device=dev)
+        hip.call("oneprot_key_padding_bias", self.ids, self.key_bias, self.T, cfg.pad_token_id)
+        self.row_scale = torch.empty(self.B, device=dev)
+        hip.call("oneprot_esm_embed_fwd", self.ids, tr.view("embeddings.word_embeddings.weight"), x, self.row_scale, self.B, self.L, tr.d, cfg.vocab_size,
+                 cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0)
+
+    def attn_fwd(self, q, k, v, ctx, lse, H, hd):
+        hip.call("oneprot_attn_fwd", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd)
+
+    def attn_workspace(self, H, dev):
+        return torch.empty(hip.query("oneprot_attn_bwd_workspace", self.B, H, self.L), dtype=torch.uint8, device=dev)
+
+    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd):
+        hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], self.cos, self.sin, q_scale, dqkv, ws, self.B, H, self.L, hd)
+
+    def embed_bwd(self, tr, g, dtable):
+        cfg, V = tr.config, tr.config.vocab_size
+        ws = torch.empty(hip.query("oneprot_esm_embed_bwd_workspace", self.T, tr.d, V), dtype=torch.uint8, device=g.device)
+        hip.call("oneprot_esm_embed_bwd", self.ids, g, self.row_scale, dtable, ws, self.B, self.L, tr.d, V, cfg.pad_token_id, cfg.mask_token_id,
+                 1 if cfg.token_dropout else 0, 0)
+
+
+class _PackedLayout:
+    """The same three stages on a packed token stream (oneprot_amd.packing): the row-wise stages see ONE sequence of T_pad rows (B = 1, L = T_pad:
+    q / k / v come out of the QKV GEMM as [H, T_pad, hd], its rotary epilogue reads row t of per-token tables); the embedding counts the
+    token-dropout factor per segment and gathers those tables, attention runs per segment (varlen kernels).  Tail rows are pad tokens: finite
+    activations, exactly zero gradient rows."""
+    packed = True
+
+    def __init__(self, tr, packed):
+        self.p = packed
+        self.ids = packed.ids
+        self.cu = packed.cu_seqlens
+        self.N, self.B, self.L = len(packed), 1, packed.T_pad
+        self.T = packed.T_pad
+        self.work = packed.attn_work()
+
+    def embed(self, tr, x):
+        cfg, dev = tr.config, x.device
+        cos_t, sin_t = tr._rope(tr.MAX_POSITIONS)
+        half = cos_t.shape[1]
+        self.tok_scale = torch.empty(self.T, device=dev)
+        self.cos, self.sin = torch.empty(self.T, half, device=dev), torch.empty(self.T, half, device=dev)
+        hip.call("oneprot_esm_embed_packed_fwd", self.ids, self.cu, tr.view("embeddings.word_embeddings.weight"), cos_t, sin_t, x, self.tok_scale, self.cos, self.sin,
+                 self.N, self.T, self.p.max_len, tr.d, cfg.vocab_size, half, cos_t.shape[0], cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0)
+
+    def attn_fwd(self, q, k, v, ctx, lse, H, hd):
+        hip.call("oneprot_attn_varlen_fwd", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd)
+
+    def attn_workspace(self, H, dev):
+        return torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, self.T), dtype=torch.uint8, device=dev)
+
+    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd):
+        hip.call("oneprot_attn_varlen_bwd", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], self.cos, self.sin,
+                 q_scale, dqkv, ws, self.N, self.T, H, hd)
+
+    def embed_bwd(self, tr, g, dtable):
+        cfg, V = tr.config, tr.config.vocab_size
+        ws = torch.empty(hip.query("oneprot_esm_embed_bwd_workspace", self.T, tr.d, V), dtype=torch.uint8, device=g.device)
+        hip.call("oneprot_esm_embed_packed_bwd", self.ids, g, self.tok_scale, dtable, ws, self.T, tr.d, V, cfg.pad_token_id, cfg.mask_token_id,
+                 1 if cfg.token_dropout else 0, 0)
+
+
+def _layout(tr, ids):
+    return _PackedLayout(tr, ids) if isinstance(ids, PackedTokens) else _PaddedLayout(tr, ids)
+
+
 class EsmTransformer(ArenaModule):
     """EsmModel replacement.  `add_pooling_layer` only controls whether the (unused) HF pooler parameters exist,
     as in the reference (SequenceEncoder: False, StructTokenEncoder: True)."""
@@ -653,6 +734,8 @@ class EsmTransformer(ArenaModule):
         ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
         return self._bf16[o:o + n], self.flat.data[ob:ob + nb], self._w16(p + "attention.output.dense.weight")
 
+    MAX_POSITIONS = 1026      # rows of the rotary tables a packed batch gathers from (ESM-2's max_position_embeddings; PackedTokens enforces it)
+
     def _rope(self, L):
         key = (L, self.flat.device)
         if key not in self._rope_cache:
@@ -668,26 +751,23 @@ class EsmTransformer(ArenaModule):
 
     # ----------------------------------------------------------------------------------------- forward / backward
     def run_layers(self, ids, save):
-        """Embedding + n layers.  Returns (x_final fp32 [T,d], saved-dict or None)."""
+        """Embedding + n layers on padded ids [B, L] or a PackedTokens stream (B = 1, L = T_pad for every row-wise stage).
+        Returns (x_final fp32 [T,d], saved-dict or None)."""
         if not ids.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
         self._refresh_bf16()
         cfg = self.config
-        B, L = ids.shape
-        T, d, f, H, hd, dp = B * L, self.d, self.f, self.H, self.hdp, self.dp        # hd: kernel (padded) head dim
+        lay = _layout(self, ids)
+        B, L, T = lay.B, lay.L, lay.T
+        d, f, H, hd, dp = self.d, self.f, self.H, self.hdp, self.dp        # hd: kernel (padded) head dim
         q_scale = self.hd ** -0.5
         dev = ids.device
-        ids = ids.contiguous()
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-        cos, sin = self._rope(L)
-        key_bias = f32(B, L)
-        hip.call("oneprot_key_padding_bias", ids, key_bias, T, cfg.pad_token_id)
         x = f32(T, d)
-        row_scale = f32(B)
-        hip.call("oneprot_esm_embed_fwd", ids, self.view("embeddings.word_embeddings.weight"), x, row_scale, B, L, d, cfg.vocab_size,
-                 cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0)
-        saved = dict(ids=ids, key_bias=key_bias, row_scale=row_scale, layers=[], B=B, L=L) if save else None
+        lay.embed(self, x)
+        cos, sin = lay.cos, lay.sin
+        saved = dict(layout=lay, layers=[], B=B, L=L) if save else None
         h = b16(T, d)
         q, k, v = b16(B, H, L, hd), b16(B, H, L, hd), b16(B, H, L, hd)
         ctx_ = b16(T, dp)
@@ -733,7 +813,7 @@ class EsmTransformer(ArenaModule):
                     st["lora_u"] = lora_u
             else:
                 hip.call("oneprot_gemm_bf16_nt", h1, w_qkv, T, 3 * dp, d, d, d, hip.EPI_QKV_ROPE, b_qkv, q, k, v, None, cos, sin, q_scale * hip.LOG2E, L, H, hd)
-            hip.call("oneprot_attn_fwd", q, k, v, key_bias, ctx_, lse, B, H, L, hd)
+            lay.attn_fwd(q, k, v, ctx_, lse, H, hd)
             x_mid = f32(T, d) if save else x
             if fused_ln:
                 # out-projection + bias + residual AND the FFN's pre-LayerNorm in one full-row kernel: x_mid is not read back by a LayerNorm launch
@@ -782,12 +862,10 @@ class EsmTransformer(ArenaModule):
         gflat: fp32 arena gradient (written).  on_ready(lo, hi): called as soon as the arena-gradient range [lo, hi) is final
         (the arena is laid out embeddings | layer 0 .. n-1 | final LayerNorm, and the backward walks the layers downwards), so the
         data-parallel all-reduce of the upper layers runs under the backward of the lower ones."""
-        B, L = saved["B"], saved["L"]
-        T, d, f, H, hd, dp = B * L, self.d, self.f, self.H, self.hdp, self.dp
+        lay = saved["layout"]
+        T, d, f, H, hd, dp = lay.T, self.d, self.f, self.H, self.hdp, self.dp
         q_scale = self.hd ** -0.5
         dev = g.device
-        cfg = self.config
-        cos, sin = self._rope(L)
         gv = lambda name: self.view(name, gflat)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
         ws_ln = torch.empty(hip.query("oneprot_layernorm_bwd_workspace", d), dtype=torch.uint8, device=dev)
@@ -797,7 +875,7 @@ class EsmTransformer(ArenaModule):
             lora_raw = self._lora_raw = self._lora_raw_buffers(dev)
             tn_shapes += ((3 * d, self._lora_ops["Rp"]), (self._lora_ops["rp"], d))
         ws_tn = self._tn_workspace(tn_shapes, dev)
-        ws_at = torch.empty(hip.query("oneprot_attn_bwd_workspace", B, H, L), dtype=torch.uint8, device=dev)
+        ws_at = lay.attn_workspace(H, dev)
         dz = b16(T, f)
         dh = b16(T, d)
         dctx = b16(T, dp) if self._padded else dh
@@ -824,7 +902,7 @@ class EsmTransformer(ArenaModule):
                      gv(p + "attention.output.dense.bias"), ws_tn, ws_tn.numel(), 0)
             hip.call("oneprot_gemm_bf16_nt", g16, self._bf16_T[(i, "o")], T, dp, d, d, d, hip.EPI_BF16, None, dctx, None, None, None, None, None, 1.0, 0, 0, 0)
             # ---- attention
-            hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], saved["key_bias"], st["ctx"], dctx, st["lse"], cos, sin, q_scale, dqkv, ws_at, B, H, L, hd)
+            lay.attn_bwd(st, dctx, q_scale, dqkv, ws_at, H, hd)
             # ---- QKV projection
             o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
             ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
@@ -846,18 +924,22 @@ class EsmTransformer(ArenaModule):
                 lo = self._spec[f"encoder.layer.{i}.attention.self.query.weight"][0]
                 on_ready(lo, ready_hi)
                 ready_hi = lo
-        V = cfg.vocab_size
-        ws_e = torch.empty(hip.query("oneprot_esm_embed_bwd_workspace", T, d, V), dtype=torch.uint8, device=dev)
-        hip.call("oneprot_esm_embed_bwd", saved["ids"], g, saved["row_scale"], gv("embeddings.word_embeddings.weight"), ws_e, B, L, d, V,
-                 cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0, 0)
+        lay.embed_bwd(self, g, gv("embeddings.word_embeddings.weight"))
         if on_ready is not None:
             on_ready(0, ready_hi)
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, **_):
         """EsmModel-compatible call returning .last_hidden_state (no autograd; the trainable path is
-        oneprot_amd.encoders' fused encode)."""
+        oneprot_amd.encoders' fused encode).  Packed input: last_hidden_state is the stream's [T_pad, d] (tail rows: the pad embedding's)."""
         x, _ = self.run_layers(input_ids, save=False)
+        if isinstance(input_ids, PackedTokens):
+            p, d = input_ids, self.d
+            hidden = torch.empty(p.T_pad, d, device=x.device)
+            pooled = torch.empty(len(p), d, device=x.device)
+            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, self.config.pad_token_id, self.view("encoder.emb_layer_norm_after.weight"),
+                     self.view("encoder.emb_layer_norm_after.bias"), pooled, None, None, None, hidden, len(p), p.T_pad, d, self.config.layer_norm_eps, 0)
+            return _Out(hidden)
         B, L = input_ids.shape
         hidden = torch.empty(B, L, self.d, device=x.device)
         pooled = torch.empty(B, self.d, device=x.device)

@@ -107,6 +107,15 @@ _SIGS = {
     "oneprot_transpose_cast_f32_to_bf16_batched": (I, [P, P, I, I, L64, L64, I, P]),
     "oneprot_colsum_workspace": (SZ, [I]),
     "oneprot_colsum_bf16": (I, [P, P, P, L64, I, I, P]),
+    "oneprot_esm_embed_packed_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    "oneprot_esm_embed_packed_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "oneprot_attn_varlen_fwd": (I, [P, P, P, P, P, I, P, P, I, I, I, I, P]),
+    "oneprot_attn_varlen_bwd_workspace": (SZ, [I, I]),
+    "oneprot_attn_varlen_bwd": (I, [P, P, P, P, P, I, P, P, P, P, P, F, P, P, I, I, I, I, P]),
+    "oneprot_lnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, P, P, P, I, I, I, F, I, P]),
+    "oneprot_lnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "oneprot_attnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
+    "oneprot_attnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
 }
 
 # Expected element type of every pointer argument, in order (f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a
@@ -121,6 +130,9 @@ _PTR_DTYPES = {
     "oneprot_ce_fwd_bwd": "fff", "oneprot_siglip_fwd_bwd": "fff", "oneprot_siglip_fwd_bwd_dev": "ffff", "oneprot_diag_rank": "fii", "oneprot_abs_sum": "ffb", "oneprot_dot_f32": "fffb", "oneprot_l1_bwd": "fff",
     "oneprot_scale_by_device_scalar": "ff", "oneprot_key_padding_bias": "lf", "oneprot_dropout_bf16": "hh", "oneprot_dropout_bwd_add_bf16": "hh", "oneprot_dropout_bwd_add_f32": "hf", "oneprot_dropout_f32": "ff", "oneprot_dropout_add_f32": "fff", "oneprot_dropout_add_layernorm_fwd": "fffffhfff", "oneprot_attn_fwd_dropout": "hhhfhf", "oneprot_attn_dropout_keep": "b", "oneprot_sumsq": "ffb", "oneprot_clip_coef": "fffb", "oneprot_adam_step": "fffff",
     "oneprot_cast_f32_to_bf16": "fh", "oneprot_transpose_cast_f32_to_bf16": "fh", "oneprot_transpose_cast_f32_to_bf16_batched": "fh", "oneprot_colsum_bf16": "hfb",
+    "oneprot_esm_embed_packed_fwd": "lifffffff", "oneprot_esm_embed_packed_bwd": "lfffb", "oneprot_attn_varlen_fwd": "hhhiihf",
+    "oneprot_attn_varlen_bwd": "hhhiihhfffhb", "oneprot_lnpool_packed_fwd": "flifffffff", "oneprot_lnpool_packed_bwd": "fiffffffhffb",
+    "oneprot_attnpool_packed_fwd": "fliffff", "oneprot_attnpool_packed_bwd": "ffifffffb",
 }
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 
