@@ -119,8 +119,9 @@ def _cfg2_reference(B, lens, seed, frozen_seq, seq_ids, st_ids, sd_seq, sd_st):
     return dict(full, grads=grads, grad_total_norm=total)
 
 
-def _cfg2_case(B, lens, frozen_seq, seed=1881):
-    """ESM-2-150M x2 at L=512, output_dim 1024: one sub-step on the HIP path and on the oracle from the same state dicts and ids."""
+def _cfg2_case(B, lens, frozen_seq, seed=1881, before_step=None):
+    """ESM-2-150M x2 at L=512, output_dim 1024: one sub-step on the HIP path and on the oracle from the same state dicts and ids.
+    before_step(module, seq_ids, st_ids), if given, runs after the feature checks and before the sub-step."""
     _env()
     from src.models.components.sequence_encoder import SequenceEncoder
     from src.models.components.struct_token_encoder import StructTokenEncoder
@@ -147,6 +148,8 @@ def _cfg2_case(B, lens, frozen_seq, seed=1881):
         mf = module(st_ids.to(DEV), "struct_token").cpu()
     assert torch.nn.functional.cosine_similarity(sf, ref["sequence_features"], dim=-1).min() > 0.999
     assert torch.nn.functional.cosine_similarity(mf, ref["modality_features"], dim=-1).min() > 0.999
+    if before_step is not None:
+        before_step(module, seq_ids, st_ids)
     loss, gn, grads = _run_substep(module, "struct_token", seq_ids, st_ids, ["sequence", "struct_token"])
     return loss, gn, grads, ref
 
@@ -204,6 +207,53 @@ def test_cfg2_shape_150m_batch16_loss_delta_reported(frozen_seq):
         json.dump(rec, f, indent=1)
     assert rec["rel_loss_delta"] < 1e-3, rec
     assert rec["rel_grad_norm_delta"] < 2e-2, rec
+
+
+def test_cfg2_batch16_under_the_multi_rank_defaults(monkeypatch):
+    """The defaults of a process with WORLD_SIZE > 1 -- work queues on (ONEPROT_DYNAMIC_TILES) and 16 CUs left to the all-reduce (ONEPROT_CU_RESERVE: the TN
+    weight-gradient GEMMs cut the tokens into other splits, another summation order) -- on the 16-pair cfg-2 sub-step of the test above, against the same
+    oracle run (_cfg2_reference's cache), with its gates.  Set both in the environment (hip.sched_workspace reads it again whenever it grows the workspace)
+    and on the current workspace."""
+    from oneprot_amd import hip
+    was_dyn, was_reserve = hip.dynamic_tiles_wanted(), hip.cu_reserve_wanted()
+    monkeypatch.setenv("ONEPROT_DYNAMIC_TILES", "1")
+    monkeypatch.setenv("ONEPROT_CU_RESERVE", "16")
+    lens = [512, 389, 512, 131, 480, 77, 512, 300, 256, 512, 33, 401, 512, 190, 505, 64]
+    epochs = {}
+
+    def queues_on_and_proven(module, seq_ids, st_ids):
+        # Proof that the queue path runs, not only that it is switched on.  The workspace's epoch counts every launch that leaves through sw_leave: with
+        # static lists only the FFN-2 / out-projection + LayerNorm GEMMs (oneprot_gemm_bf16_nt_resid_ln8, forced on by _env) do; with queues on, every
+        # 8-phase NT GEMM with K >= 256 (gemm_nt8.hip launch_cfg: a.dyn) and the persistent attention forward (attention.hip, its sched argument)
+        # leave through it as well.  So the same forward advances the epoch by strictly more with queues on than with them off.
+        ws = hip.sched_workspace(seq_ids.numel())
+
+        def fwd_epochs(dyn):
+            hip.query("oneprot_dynamic_tiles", ws[0] if dyn else None, ws[1])
+            torch.cuda.synchronize()
+            e0 = hip.query("oneprot_sched_epoch", ws[0])
+            with torch.no_grad():
+                module(st_ids.to(DEV), "struct_token")
+            torch.cuda.synchronize()
+            assert hip.sched_ptr_or_none() == ws[0], "the workspace was replaced during the probe"
+            return hip.query("oneprot_sched_epoch", ws[0]) - e0
+        epochs["off"] = fwd_epochs(False)
+        epochs["on"] = fwd_epochs(True)                   # (leaves the queues on for the sub-step)
+        hip.query("oneprot_cu_reserve", 16)
+
+    try:
+        loss, gn, grads, ref = _cfg2_case(16, lens, False, seed=1882, before_step=queues_on_and_proven)
+        assert hip.sched_late_draws() == 0 and hip.sched_error() == 0
+    finally:
+        ws = hip.sched_workspace()
+        hip.query("oneprot_dynamic_tiles", ws[0] if was_dyn else None, ws[1])
+        hip.query("oneprot_cu_reserve", was_reserve)
+    assert epochs["on"] > epochs["off"] > 0, epochs
+    rl, rg = float(ref["loss"]), float(ref["grad_total_norm"])
+    assert abs(loss - rl) / rl < 1e-3, (loss, rl)
+    assert abs(gn - rg) / rg < 2e-2, (gn, rg)
+    _check_arena_grads(grads["struct_token"], ref["grads"], "mod.")
+    _check_arena_grads(grads["sequence"], ref["grads"], "seq.", whole=0.99985)
 
 
 def _oracle_features_in_micro_batches(spec, ids, sd, cfg, mb=16):
