@@ -183,26 +183,50 @@ static int attn_drop_make(float p, uint64_t seed, uint64_t stream_id, AttnDrop& 
   return OP_OK;
 }
 
-template <int HD, bool DROP = false>
-__global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-                                                  const float* __restrict__ key_bias, bf16_t* __restrict__ ctx, float* __restrict__ lse_out, int B, int H,
-                                                  int L, int nqb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+// One work-group's share of a split kernel: one (sequence, head) and one 128-row block of it.  The padded kernels fill it from decode_block, the
+// packed (varlen) kernels from varlen_item; the three bodies (attn_fwd_body, attn_bwd_dq_body, attn_bwd_dkv_body) index through it alone.
+struct AttnSlab {
+  int L, blk, head;          // sequence length, 128-row block, head
+  size_t hrow;               // row of position 0 in q / k / v / lse / delta  (padded: bh * L; packed: head * T_pad + start)
+  size_t trow;               // row of position 0 in ctx / dctx / dqkv        (padded: b * L;  packed: start)
+  const float* bias;         // this sequence's key-bias row, or null         (packed: null -- the segment end is the only mask)
+  int rope0;                 // rotary-table row of position 0                (padded: 0;      packed: start -- the tables are gathered per token)
+  int bh;                    // dropout stream b * H + head                   (read under DROP only)
+};
+__device__ __forceinline__ AttnSlab padded_slab(const float* key_bias, int bh, int blk, int H, int L) {
+  const int b = bh / H;
+  return AttnSlab{L, blk, bh - b * H, (size_t)bh * L, (size_t)b * L, key_bias ? key_bias + (size_t)b * L : nullptr, 0, bh};
+}
+
+// key side of the extra k-step for the chunk of keys at kc0, per key: bf16 [1, 1, 1, bias | -inf past the end, 0, 0, 0, 0]; slot KC = zeros.
+// (The bias index stays 64-bit: with an int index hipcc gives k_attn_bwd_dq<32> 129 VGPRs instead of 119, one wave per SIMD less.)
+__device__ __forceinline__ void fill_key_entries(u32x4* sE, const float* bias, int kc0, int nkeys, int nrows) {
+  for (int i = threadIdx.x; i <= KC; i += 256) {
+    u32x4 e = {0u, 0u, 0u, 0u};
+    if (i < nrows) {
+      const float bv = i < nkeys ? (bias ? bias[(size_t)kc0 + i] : 0.f) : -INFINITY;
+      e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
+    }
+    sE[i] = e;
+  }
+}
+
+template <int HD, bool DROP>
+__device__ __forceinline__ void attn_fwd_body(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, bf16_t* __restrict__ ctx,
+                                              float* __restrict__ lse_out, int H, const AttnSlab& sl, const AttnDrop& dr) {
   typedef Cfg<HD> C;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sK = smem;
   unsigned char* sV = sK + KC * C::ROWB;
-  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);       // per key: bf16 [1, 1, 1, bias, 0, 0, 0, 0]; slot KC = zeros
-  int bh, qb;
-  decode_block(nqb, B * H, bh, qb);
-  if (bh >= B * H) return;
-  const int b = bh / H, head = bh - b * H;
+  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);       // fill_key_entries
+  const int L = sl.L;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int q0 = qb * 128 + wave * 32;
+  const int q0 = sl.blk * 128 + wave * 32;
   const int qidx = q0 + (lane & 31);
   const int qrow = qidx < L ? qidx : L - 1;
-  const bf16_t* qbase = q + (size_t)bh * L * HD;
-  const bf16_t* kbase = k + (size_t)bh * L * HD;
-  const bf16_t* vbase = v + (size_t)bh * L * HD;
+  const bf16_t* qbase = q + sl.hrow * HD;
+  const bf16_t* kbase = k + sl.hrow * HD;
+  const bf16_t* vbase = v + sl.hrow * HD;
   bf8_t qf[C::KSTEPS];
 #pragma unroll
   for (int st = 0; st < C::KSTEPS; ++st) qf[st] = *reinterpret_cast<const bf8_t*>(qbase + (size_t)qrow * HD + 16 * st + 8 * h);
@@ -222,14 +246,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ 
     const int nrows = (nkeys + 31) & ~31;
     __syncthreads();
     load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
-    for (int i = threadIdx.x; i <= KC; i += 256) {
-      u32x4 e = {0u, 0u, 0u, 0u};
-      if (i < nrows) {
-        const float bv = i < nkeys ? (key_bias ? key_bias[(size_t)b * L + kc0 + i] : 0.f) : -INFINITY;
-        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
-      }
-      sE[i] = e;
-    }
+    fill_key_entries(sE, sl.bias, kc0, nkeys, nrows);
     __syncthreads();
     for (int t = 0; t < nrows / 32; ++t) {
       const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
@@ -268,7 +285,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ 
       for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
       f32x16 sd = s;
       if constexpr (DROP) {
-        const unsigned bits = attn_keep_bits_q(qidx, kc0 + t * 32, h, bh, dr);
+        const unsigned bits = attn_keep_bits_q(qidx, kc0 + t * 32, h, sl.bh, dr);
 #pragma unroll
         for (int r = 0; r < 16; ++r) sd[r] = ((bits >> r) & 1u) ? s[r] : 0.f;
       }
@@ -286,7 +303,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ 
   float inv = lt > 0.f ? 1.0f / lt : 0.f;
   if constexpr (DROP) inv *= dr.scale;
   if (qidx < L) {
-    bf16_t* dst = ctx + ((size_t)b * L + qidx) * (H * HD) + head * HD;
+    bf16_t* dst = ctx + (sl.trow + qidx) * (H * HD) + sl.head * HD;
 #pragma unroll
     for (int d = 0; d < C::DBLK; ++d)
 #pragma unroll
@@ -297,27 +314,28 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ 
           *reinterpret_cast<u32x2*>(dst + dd) = w;
         }
       }
-    if (lse_out && h == 0) lse_out[(size_t)bh * L + qidx] = (m + __log2f(lt)) * 0.6931471805599453f;
+    if (lse_out && h == 0) lse_out[sl.hrow + qidx] = (m + __log2f(lt)) * 0.6931471805599453f;
   }
 }
 
-template <int HD> static size_t fwd_lds() { return (size_t)2 * KC * Cfg<HD>::ROWB + (KC + 1) * 16; }
-
-template <int HD>
-static int launch_fwd(const void* q, const void* k, const void* v, const float* key_bias, void* ctx, float* lse, int B, int H, int L, hipStream_t s) {
-  const int nqb = (L + 127) / 128;
-  const int nbh8 = ((B * H + 7) / 8) * 8;
-  hipLaunchKernelGGL(k_attn_fwd<HD>, dim3(nbh8 * nqb), dim3(256), fwd_lds<HD>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
-                     (bf16_t*)ctx, lse, B, H, L, nqb);
-  return launch_status();
+template <int HD, bool DROP = false>
+__global__ void __launch_bounds__(256, 2) k_attn_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                  const float* __restrict__ key_bias, bf16_t* __restrict__ ctx, float* __restrict__ lse_out, int B, int H,
+                                                  int L, int nqb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+  int bh, qb;
+  decode_block(nqb, B * H, bh, qb);
+  if (bh >= B * H) return;
+  attn_fwd_body<HD, DROP>(q, k, v, ctx, lse_out, H, padded_slab(key_bias, bh, qb, H, L), dr);
 }
 
-template <int HD>
-static int launch_fwd_dropout(const void* q, const void* k, const void* v, const float* key_bias, void* ctx, float* lse, int B, int H, int L, const AttnDrop& dr,
-                              hipStream_t s) {
+template <int HD> static size_t fwd_lds() { return (size_t)2 * KC * Cfg<HD>::ROWB + (KC + 1) * 16; }      // two KC-row tiles + the extra-k-step entries: every split kernel
+
+template <int HD, bool DROP = false>
+static int launch_fwd(const void* q, const void* k, const void* v, const float* key_bias, void* ctx, float* lse, int B, int H, int L, hipStream_t s,
+                      const AttnDrop& dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
   const int nqb = (L + 127) / 128;
   const int nbh8 = ((B * H + 7) / 8) * 8;
-  hipLaunchKernelGGL((k_attn_fwd<HD, true>), dim3(nbh8 * nqb), dim3(256), fwd_lds<HD>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
+  hipLaunchKernelGGL((k_attn_fwd<HD, DROP>), dim3(nbh8 * nqb), dim3(256), fwd_lds<HD>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
                      (bf16_t*)ctx, lse, B, H, L, nqb, dr);
   return launch_status();
 }
@@ -1530,9 +1548,9 @@ extern "C" int oneprot_attn_fwd_dropout(const void* q, const void* k, const void
   if (!q || !k || !v || !ctx || B <= 0 || H <= 0 || L <= 0 || attn_drop_make(p, seed, stream_id, dr) != OP_OK) return OP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   switch (hd) {
-    case 16: return launch_fwd_dropout<16>(q, k, v, key_bias, ctx, lse, B, H, L, dr, s);
-    case 32: return launch_fwd_dropout<32>(q, k, v, key_bias, ctx, lse, B, H, L, dr, s);
-    case 64: return launch_fwd_dropout<64>(q, k, v, key_bias, ctx, lse, B, H, L, dr, s);
+    case 16: return launch_fwd<16, true>(q, k, v, key_bias, ctx, lse, B, H, L, s, dr);
+    case 32: return launch_fwd<32, true>(q, k, v, key_bias, ctx, lse, B, H, L, s, dr);
+    case 64: return launch_fwd<64, true>(q, k, v, key_bias, ctx, lse, B, H, L, s, dr);
     default: return OP_EINVAL;
   }
 }
@@ -1588,44 +1606,41 @@ __device__ __forceinline__ void unrope_store(f32x16 (&acc)[Cfg<HD>::DBLK], const
 // ---- dQ: one wave = 32 queries, loops over all keys -------------------------------------------------------------
 // DROP (both split kernels): the forward ran with probability dropout, O = (keep * P / keep_prob) V.  Then dV = (keep * P / keep_prob)^T dO and
 // dS = P * (keep * dP / keep_prob - delta) with the SAME delta = rowsum(dO * O); the mask is regenerated from (seed, stream, b*H+h, q, k).
-template <int HD, bool DROP = false>
-__global__ void __launch_bounds__(256, 2) k_attn_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-                                                     const float* __restrict__ key_bias, const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx,
-                                                     const float* __restrict__ lse, float* __restrict__ delta, const float* __restrict__ cosT, const float* __restrict__ sinT,
-                                                     float q_scale, bf16_t* __restrict__ dqkv, int B, int H, int L, int nqb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+template <int HD, bool DROP>
+__device__ __forceinline__ void attn_bwd_dq_body(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                 const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx, const float* __restrict__ lse,
+                                                 float* __restrict__ delta, const float* __restrict__ cosT, const float* __restrict__ sinT, float q_scale,
+                                                 bf16_t* __restrict__ dqkv, int H, const AttnSlab& sl, const AttnDrop& dr) {
   typedef Cfg<HD> C;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sK = smem;
   unsigned char* sV = sK + KC * C::ROWB;
-  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);       // per key: bf16 [1, 1, 1, bias, 0, 0, 0, 0]; slot KC = zeros (as in the forward)
-  int bh, qb;
-  decode_block(nqb, B * H, bh, qb);
-  if (bh >= B * H) return;
-  const int b = bh / H, head = bh - b * H;
+  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);       // fill_key_entries, as in the forward
+  const int L = sl.L;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int qidx = qb * 128 + wave * 32 + (lane & 31);
+  const int qidx = sl.blk * 128 + wave * 32 + (lane & 31);
   const int qrow = qidx < L ? qidx : L - 1;
   const int dm = H * HD;
-  const bf16_t* kbase = k + (size_t)bh * L * HD;
-  const bf16_t* vbase = v + (size_t)bh * L * HD;
+  const bf16_t* kbase = k + sl.hrow * HD;
+  const bf16_t* vbase = v + sl.hrow * HD;
   bf8_t qf[C::KSTEPS], dof[C::KSTEPS];
 #pragma unroll
   for (int st = 0; st < C::KSTEPS; ++st) {
-    qf[st] = *reinterpret_cast<const bf8_t*>(q + ((size_t)bh * L + qrow) * HD + 16 * st + 8 * h);
-    dof[st] = *reinterpret_cast<const bf8_t*>(dctx + ((size_t)b * L + qrow) * dm + head * HD + 16 * st + 8 * h);
+    qf[st] = *reinterpret_cast<const bf8_t*>(q + (sl.hrow + qrow) * HD + 16 * st + 8 * h);
+    dof[st] = *reinterpret_cast<const bf8_t*>(dctx + (sl.trow + qrow) * dm + sl.head * HD + 16 * st + 8 * h);
   }
-  const float lse_q = lse[(size_t)bh * L + qrow] * LOG2E;      // scores are in log2 units (q stored x log2 e)
+  const float lse_q = lse[sl.hrow + qrow] * LOG2E;      // scores are in log2 units (q stored x log2 e)
   // delta[query] = sum_d dO[query, d] * O[query, d]: each lane holds 8 of every 16 head-dim columns of its query's dO; formed here (one
   // lane^32 exchange) and published for the dK/dV kernel, which runs after this one on the same stream
   float delta_q = 0.f;
 #pragma unroll
   for (int st = 0; st < C::KSTEPS; ++st) {
-    const u32x4 x = *reinterpret_cast<const u32x4*>(ctx + ((size_t)b * L + qrow) * dm + head * HD + 16 * st + 8 * h), y = __builtin_bit_cast(u32x4, dof[st]);
+    const u32x4 x = *reinterpret_cast<const u32x4*>(ctx + (sl.trow + qrow) * dm + sl.head * HD + 16 * st + 8 * h), y = __builtin_bit_cast(u32x4, dof[st]);
     delta_q += bflo(x.x) * bflo(y.x) + bfhi(x.x) * bfhi(y.x) + bflo(x.y) * bflo(y.y) + bfhi(x.y) * bfhi(y.y) + bflo(x.z) * bflo(y.z) + bfhi(x.z) * bfhi(y.z) +
                bflo(x.w) * bflo(y.w) + bfhi(x.w) * bfhi(y.w);
   }
   delta_q += __shfl_xor(delta_q, 32, 64);
-  if (h == 0 && qidx < L) delta[(size_t)bh * L + qidx] = delta_q;
+  if (h == 0 && qidx < L) delta[sl.hrow + qidx] = delta_q;
   // row constants through one extra MFMA k-step each (no per-element VALU): S' = K Q^T + [1,1,1,bias_key] . [-lse split, 1],
   // dP' = V dO^T + [1,1,1,0] . [-delta split, 0]
   u32x4 qe = {0u, 0u, 0u, 0u}, de = {0u, 0u, 0u, 0u}, ones3 = {0u, 0u, 0u, 0u};
@@ -1643,14 +1658,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dq(const bf16_t* __restrict
     const int nrows = (nkeys + 31) & ~31;
     __syncthreads();
     load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
-    for (int i = threadIdx.x; i <= KC; i += 256) {
-      u32x4 e = {0u, 0u, 0u, 0u};
-      if (i < nrows) {
-        const float bv = i < nkeys ? (key_bias ? key_bias[(size_t)b * L + kc0 + i] : 0.f) : -INFINITY;
-        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
-      }
-      sE[i] = e;
-    }
+    fill_key_entries(sE, sl.bias, kc0, nkeys, nrows);
     __syncthreads();
     for (int t = 0; t < nrows / 32; ++t) {
       const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
@@ -1662,7 +1670,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dq(const bf16_t* __restrict
         dp = MFMA32(rd_row<HD>(sV, t * 32 + (lane & 31), st, h), dof[st], dp);
       }
       if constexpr (DROP) {
-        const unsigned bits = attn_keep_bits_q(qidx, kc0 + t * 32, h, bh, dr);
+        const unsigned bits = attn_keep_bits_q(qidx, kc0 + t * 32, h, sl.bh, dr);
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[r] = (((bits >> r) & 1u) ? dp[r] * dr.scale : 0.f) - delta_q;
       }
@@ -1676,35 +1684,43 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dq(const bf16_t* __restrict
       }
     }
   }
-  if (qidx < L) unrope_store<HD>(acc, cosT, sinT, qidx, h, q_scale, cosT != nullptr, dqkv + ((size_t)b * L + qidx) * (3 * dm) + head * HD);
+  if (qidx < L) unrope_store<HD>(acc, cosT, sinT, sl.rope0 + qidx, h, q_scale, cosT != nullptr, dqkv + (sl.trow + qidx) * (3 * dm) + sl.head * HD);
+}
+
+template <int HD, bool DROP = false>
+__global__ void __launch_bounds__(256, 2) k_attn_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                     const float* __restrict__ key_bias, const bf16_t* __restrict__ ctx, const bf16_t* __restrict__ dctx,
+                                                     const float* __restrict__ lse, float* __restrict__ delta, const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                     float q_scale, bf16_t* __restrict__ dqkv, int B, int H, int L, int nqb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+  int bh, qb;
+  decode_block(nqb, B * H, bh, qb);
+  if (bh >= B * H) return;
+  attn_bwd_dq_body<HD, DROP>(q, k, v, ctx, dctx, lse, delta, cosT, sinT, q_scale, dqkv, H, padded_slab(key_bias, bh, qb, H, L), dr);
 }
 
 // ---- dK, dV: one wave = 32 keys, loops over all queries -----------------------------------------------------------
-template <int HD, bool DROP = false>
-__global__ void __launch_bounds__(256, 2) k_attn_bwd_dkv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-                                                      const float* __restrict__ key_bias, const bf16_t* __restrict__ dctx, const float* __restrict__ lse,
-                                                      const float* __restrict__ delta, const float* __restrict__ cosT, const float* __restrict__ sinT,
-                                                      bf16_t* __restrict__ dqkv, int B, int H, int L, int nkb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+template <int HD, bool DROP>
+__device__ __forceinline__ void attn_bwd_dkv_body(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                  const bf16_t* __restrict__ dctx, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                  const float* __restrict__ cosT, const float* __restrict__ sinT, bf16_t* __restrict__ dqkv, int H,
+                                                  const AttnSlab& sl, const AttnDrop& dr) {
   typedef Cfg<HD> C;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sQ = smem;
   unsigned char* sdO = sQ + KC * C::ROWB;
   u32x4* sQE = reinterpret_cast<u32x4*>(sdO + KC * C::ROWB);    // per query: bf16 [-lse split in 3, 1, -delta split in 3, 0]; slot KC = zeros
-  int bh, kb;
-  decode_block(nkb, B * H, bh, kb);
-  if (bh >= B * H) return;
-  const int b = bh / H, head = bh - b * H;
+  const int L = sl.L;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int kidx = kb * 128 + wave * 32 + (lane & 31);
+  const int kidx = sl.blk * 128 + wave * 32 + (lane & 31);
   const int krow = kidx < L ? kidx : L - 1;
   const int dm = H * HD;
   bf8_t kf[C::KSTEPS], vf[C::KSTEPS];
 #pragma unroll
   for (int st = 0; st < C::KSTEPS; ++st) {
-    kf[st] = *reinterpret_cast<const bf8_t*>(k + ((size_t)bh * L + krow) * HD + 16 * st + 8 * h);
-    vf[st] = *reinterpret_cast<const bf8_t*>(v + ((size_t)bh * L + krow) * HD + 16 * st + 8 * h);
+    kf[st] = *reinterpret_cast<const bf8_t*>(k + (sl.hrow + krow) * HD + 16 * st + 8 * h);
+    vf[st] = *reinterpret_cast<const bf8_t*>(v + (sl.hrow + krow) * HD + 16 * st + 8 * h);
   }
-  const float bias_k = kidx < L ? (key_bias ? key_bias[(size_t)b * L + kidx] : 0.f) : -INFINITY;
+  const float bias_k = kidx < L ? (sl.bias ? sl.bias[kidx] : 0.f) : -INFINITY;
   // key-side operands of the extra k-step: [1,1,1,bias_key,0,0,0,0] picks (-lse + bias) for S, [0,0,0,0,1,1,1,0] picks -delta for dP
   u32x4 kS = {0u, 0u, 0u, 0u}, kD = {0u, 0u, 0u, 0u};
   if (h == 0) { kS.x = 0x3F803F80u; kS.y = 0x3F80u | (pack2bf(bias_k, 0.f) << 16); kD.z = 0x3F803F80u; kD.w = 0x00003F80u; }
@@ -1715,14 +1731,14 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dkv(const bf16_t* __restric
     const int nq = min(KC, L - qc0);
     const int nrows = (nq + 31) & ~31;
     __syncthreads();
-    load_tile_pair<HD>(sQ, q + ((size_t)bh * L + qc0) * HD, HD, sdO, dctx + ((size_t)b * L + qc0) * dm + head * HD, dm, nq, nrows);
+    load_tile_pair<HD>(sQ, q + (sl.hrow + qc0) * HD, HD, sdO, dctx + (sl.trow + qc0) * dm + sl.head * HD, dm, nq, nrows);
     for (int i = threadIdx.x; i <= KC; i += 256) {
       u32x4 e = {0u, 0u, 0u, 0u};
       if (i < nrows) {
         unsigned w01, w2;
-        split3_bf16(i < nq ? -lse[(size_t)bh * L + qc0 + i] * LOG2E : -1.0e30f, w01, w2);       // log2 units; finite for padding rows (-inf x 0 in the dP pick would be NaN)
+        split3_bf16(i < nq ? -lse[sl.hrow + qc0 + i] * LOG2E : -1.0e30f, w01, w2);       // log2 units; finite for padding rows (-inf x 0 in the dP pick would be NaN)
         e.x = w01; e.y = w2 | 0x3F800000u;
-        split3_bf16(i < nq ? -delta[(size_t)bh * L + qc0 + i] : 0.f, w01, w2);
+        split3_bf16(i < nq ? -delta[sl.hrow + qc0 + i] : 0.f, w01, w2);
         e.z = w01; e.w = w2;
       }
       sQE[i] = e;
@@ -1741,7 +1757,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dkv(const bf16_t* __restric
       }
       f32x16 p, pm;
       if constexpr (DROP) {
-        const unsigned bits = attn_keep_bits_k(kidx, qc0 + t * 32, h, bh, dr);
+        const unsigned bits = attn_keep_bits_k(kidx, qc0 + t * 32, h, sl.bh, dr);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const bool kp = (bits >> r) & 1u;
@@ -1765,10 +1781,21 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_dkv(const bf16_t* __restric
     }
   }
   if (kidx < L) {
-    bf16_t* row = dqkv + ((size_t)b * L + kidx) * (3 * dm) + head * HD;
-    unrope_store<HD>(adk, cosT, sinT, kidx, h, 0.6931471805599453f, cosT != nullptr, row + dm);      // q is stored x log2(e): dK = ln2 * dS^T q
-    unrope_store<HD>(adv, cosT, sinT, kidx, h, 1.0f, false, row + 2 * dm);
+    bf16_t* row = dqkv + (sl.trow + kidx) * (3 * dm) + sl.head * HD;
+    unrope_store<HD>(adk, cosT, sinT, sl.rope0 + kidx, h, 0.6931471805599453f, cosT != nullptr, row + dm);      // q is stored x log2(e): dK = ln2 * dS^T q
+    unrope_store<HD>(adv, cosT, sinT, sl.rope0 + kidx, h, 1.0f, false, row + 2 * dm);
   }
+}
+
+template <int HD, bool DROP = false>
+__global__ void __launch_bounds__(256, 2) k_attn_bwd_dkv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+                                                      const float* __restrict__ key_bias, const bf16_t* __restrict__ dctx, const float* __restrict__ lse,
+                                                      const float* __restrict__ delta, const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                                      bf16_t* __restrict__ dqkv, int B, int H, int L, int nkb, const AttnDrop dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+  int bh, kb;
+  decode_block(nkb, B * H, bh, kb);
+  if (bh >= B * H) return;
+  attn_bwd_dkv_body<HD, DROP>(q, k, v, dctx, lse, delta, cosT, sinT, dqkv, H, padded_slab(key_bias, bh, kb, H, L), dr);
 }
 
 // ---- fused backward for short sequences (L <= 512, hd <= 32): one 1024-thread work-group per (b, h) ---------------------------------
@@ -2405,6 +2432,20 @@ extern "C" void oneprot_attn_debug_ablate(int mask) { g_attn_bwd_ablate = mask; 
 static constexpr int g_attn_bwd_ablate = 0;
 #endif
 
+// the split pair: dQ (which also publishes delta) and then dK / dV on the same stream
+template <int HD, bool DROP = false>
+static int launch_bwd_split(const void* q, const void* k, const void* v, const float* key_bias, const void* ctx, const void* dctx, const float* lse, float* delta,
+                            const float* cosT, const float* sinT, float q_scale, void* dqkv, int B, int H, int L, hipStream_t s,
+                            const AttnDrop& dr = AttnDrop{0u, 0u, 0u, 1.0f}) {
+  const int nb = (L + 127) / 128;
+  const int nbh8 = ((B * H + 7) / 8) * 8;
+  hipLaunchKernelGGL((k_attn_bwd_dq<HD, DROP>), dim3(nbh8 * nb), dim3(256), fwd_lds<HD>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
+                     (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, cosT, sinT, q_scale, (bf16_t*)dqkv, B, H, L, nb, dr);
+  hipLaunchKernelGGL((k_attn_bwd_dkv<HD, DROP>), dim3(nbh8 * nb), dim3(256), fwd_lds<HD>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
+                     (const bf16_t*)dctx, lse, (const float*)delta, cosT, sinT, (bf16_t*)dqkv, B, H, L, nb, dr);
+  return launch_status();
+}
+
 template <int HD>
 static int launch_bwd(const void* q, const void* k, const void* v, const float* key_bias, const void* ctx, const void* dctx, const float* lse, float* delta,
                       const float* cosT, const float* sinT, float q_scale, void* dqkv, int B, int H, int L, hipStream_t s) {
@@ -2437,31 +2478,11 @@ static int launch_bwd(const void* q, const void* k, const void* v, const float* 
       }
     }
   }
-  const int nb = (L + 127) / 128;
-  const int nbh8 = ((B * H + 7) / 8) * 8;
-  const size_t lds_q = (size_t)2 * KC * Cfg<HD>::ROWB + (KC + 1) * 16;
-  const size_t lds_kv = (size_t)2 * KC * Cfg<HD>::ROWB + (KC + 1) * 16;
-  hipLaunchKernelGGL(k_attn_bwd_dq<HD>, dim3(nbh8 * nb), dim3(256), lds_q, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
-                     (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, cosT, sinT, q_scale, (bf16_t*)dqkv, B, H, L, nb);
-  hipLaunchKernelGGL(k_attn_bwd_dkv<HD>, dim3(nbh8 * nb), dim3(256), lds_kv, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
-                     (const bf16_t*)dctx, lse, (const float*)delta, cosT, sinT, (bf16_t*)dqkv, B, H, L, nb);
-  return launch_status();
+  return launch_bwd_split<HD>(q, k, v, key_bias, ctx, dctx, lse, delta, cosT, sinT, q_scale, dqkv, B, H, L, s);
 }
 
 extern "C" size_t oneprot_attn_bwd_workspace(int B, int H, int L) { return (size_t)B * H * L * sizeof(float); }
 
-template <int HD>
-static int launch_bwd_dropout(const void* q, const void* k, const void* v, const float* key_bias, const void* ctx, const void* dctx, const float* lse, float* delta,
-                              const float* cosT, const float* sinT, float q_scale, void* dqkv, int B, int H, int L, const AttnDrop& dr, hipStream_t s) {
-  const int nb = (L + 127) / 128;
-  const int nbh8 = ((B * H + 7) / 8) * 8;
-  const size_t lds = (size_t)2 * KC * Cfg<HD>::ROWB + (KC + 1) * 16;
-  hipLaunchKernelGGL((k_attn_bwd_dq<HD, true>), dim3(nbh8 * nb), dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
-                     (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, cosT, sinT, q_scale, (bf16_t*)dqkv, B, H, L, nb, dr);
-  hipLaunchKernelGGL((k_attn_bwd_dkv<HD, true>), dim3(nbh8 * nb), dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_bias,
-                     (const bf16_t*)dctx, lse, (const float*)delta, cosT, sinT, (bf16_t*)dqkv, B, H, L, nb, dr);
-  return launch_status();
-}
 extern "C" int oneprot_attn_bwd_dropout(const void* q, const void* k, const void* v, const float* key_bias, const void* ctx, const void* dctx, const float* lse,
                                         const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv, void* workspace, int B, int H, int L, int hd,
                                         float p, uint64_t seed, uint64_t stream_id, void* stream) {
@@ -2471,9 +2492,9 @@ extern "C" int oneprot_attn_bwd_dropout(const void* q, const void* k, const void
   hipStream_t s = (hipStream_t)stream;
   float* delta = (float*)workspace;
   switch (hd) {
-    case 16: return launch_bwd_dropout<16>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, dr, s);
-    case 32: return launch_bwd_dropout<32>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, dr, s);
-    case 64: return launch_bwd_dropout<64>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, dr, s);
+    case 16: return launch_bwd_split<16, true>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, s, dr);
+    case 32: return launch_bwd_split<32, true>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, s, dr);
+    case 64: return launch_bwd_split<64, true>(q, k, v, key_bias, ctx, dctx, lse, delta, rope_cos, rope_sin, q_scale, dqkv, B, H, L, s, dr);
     default: return OP_EINVAL;
   }
 }
@@ -2496,10 +2517,16 @@ extern "C" int oneprot_attn_bwd(const void* q, const void* k, const void* v, con
 // =========================================================================================================
 // varlen (packed) attention: q / k / v bf16 [H, T_pad, hd] hold N segments back to back (cu_seqlens int32 [N + 1]); a segment's queries see
 // only that segment's keys.  Work items (segment, 128-row block) come from the host in `work` int32 [n_work][2], longest segment first, so that one
-// long segment does not finish alone at the end; work-group = item * H + head.  The tile steps are those of k_attn_fwd / k_attn_bwd_dq / dkv
-// above (per-tile running maximum in the forward: scores of +-400 stay exact); the segment end masks the last partial key tile (its zero-filled
-// rows get -inf in the extra k-step), so there is no key-bias tensor.  ctx / dctx are [T_pad, H*hd], lse / delta [H, T_pad], dqkv [T_pad, 3*H*hd];
-// rows past cu_seqlens[N] (the tail) are written as zeros by k_varlen_tail_zero.
+// long segment does not finish alone at the end; work-group = item * H + head.  The kernels run the bodies of k_attn_fwd / k_attn_bwd_dq / dkv
+// (attn_fwd_body, attn_bwd_dq_body, attn_bwd_dkv_body; per-tile running maximum in the forward: scores of +-400 stay exact) behind their own
+// decoder, varlen_item.  A packed slab differs from a padded one in what it puts into the AttnSlab, nowhere else:
+//   L     = the segment's length;
+//   hrow  = head * T_pad + start   (q / k / v are [H, T_pad, hd], lse / delta [H, T_pad]);
+//   trow  = start                  (ctx / dctx are [T_pad, H*hd], dqkv [T_pad, 3*H*hd]);
+//   bias  = null: the segment end masks the last partial key tile (its zero-filled rows get -inf in the extra k-step), there is no key-bias tensor;
+//   rope0 = start: the rotary tables are gathered per token, row = the token's row in the stream;
+//   DROP  = false, with a default AttnDrop (the packed towers, ESM, have no probability dropout).
+// Rows past cu_seqlens[N] (the tail) are written as zeros by k_varlen_tail_zero.
 // =========================================================================================================
 struct VarSeg { int start, n, blk; };
 __device__ __forceinline__ bool varlen_item(const int* __restrict__ cu, const int* __restrict__ work, int N, int T_pad, int H, int& head, VarSeg& sg) {
@@ -2513,109 +2540,18 @@ __device__ __forceinline__ bool varlen_item(const int* __restrict__ cu, const in
   return sg.start >= 0 && sg.n > 0 && sg.start + sg.n <= T_pad && blk >= 0 && blk * 128 < sg.n;
 }
 
+__device__ __forceinline__ AttnSlab packed_slab(const VarSeg& sg, int head, int T_pad) {
+  return AttnSlab{sg.n, sg.blk, head, (size_t)head * T_pad + sg.start, (size_t)sg.start, nullptr, sg.start, 0};
+}
+
 template <int HD>
 __global__ void __launch_bounds__(256, 2) k_attn_varlen_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                          const int* __restrict__ cu, const int* __restrict__ work, bf16_t* __restrict__ ctx,
                                                          float* __restrict__ lse_out, int N, int T_pad, int H) {
-  typedef Cfg<HD> C;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sK = smem;
-  unsigned char* sV = sK + KC * C::ROWB;
-  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  const int L = sg.n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int qidx = sg.blk * 128 + wave * 32 + (lane & 31);
-  const int qrow = qidx < L ? qidx : L - 1;
-  const size_t slab = (size_t)head * T_pad + sg.start;          // row of position 0 of this (segment, head) in q / k / v / lse
-  const bf16_t* qbase = q + slab * HD;
-  const bf16_t* kbase = k + slab * HD;
-  const bf16_t* vbase = v + slab * HD;
-  bf8_t qf[C::KSTEPS];
-#pragma unroll
-  for (int st = 0; st < C::KSTEPS; ++st) qf[st] = *reinterpret_cast<const bf8_t*>(qbase + (size_t)qrow * HD + 16 * st + 8 * h);
-  float m = 0.f, l = 0.f;
-  u32x4 qe = {0u, 0u, 0u, 0u};
-  if (h == 0) { qe.x = 0u; qe.y = 0x3F800000u; }
-  const u32x4 ones = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-  f32x16 acc[C::DBLK], lacc = zero16();
-#pragma unroll
-  for (int d = 0; d < C::DBLK; ++d) acc[d] = zero16();
-  bool first = true;
-  for (int kc0 = 0; kc0 < L; kc0 += KC) {
-    const int nkeys = min(KC, L - kc0);
-    const int nrows = (nkeys + 31) & ~31;
-    __syncthreads();
-    load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
-    for (int i = threadIdx.x; i <= KC; i += 256) {
-      u32x4 e = {0u, 0u, 0u, 0u};
-      if (i < nrows) {
-        const float bv = i < nkeys ? 0.f : -INFINITY;            // the segment end
-        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
-      }
-      sE[i] = e;
-    }
-    __syncthreads();
-    for (int t = 0; t < nrows / 32; ++t) {
-      const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
-      f32x16 s = MFMA32(__builtin_bit_cast(bf8_t, ke), __builtin_bit_cast(bf8_t, qe), zero16());
-#pragma unroll
-      for (int st = 0; st < C::KSTEPS; ++st) s = MFMA32(rd_row<HD>(sK, t * 32 + (lane & 31), st, h), qf[st], s);
-      float mx = fmaxf(fmaxf(s[0], s[1]), s[2]);
-#pragma unroll
-      for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[r]), s[r + 1]);
-      mx = fmaxf(mx, s[15]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      if (first || __any(mx > RESCALE_THR * LOG2E)) {
-        float dlt = first ? mx : fmaxf(mx, 0.f);
-        if (!(dlt > -1e30f)) dlt = 0.f;
-        const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-dlt);
-        l = (l + lacc[0]) * alpha;
-        lacc = zero16();
-#pragma unroll
-        for (int d = 0; d < C::DBLK; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[d][r] *= alpha;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] -= dlt;
-        m += dlt;
-        if (h == 0) {
-          const float nm = -m;
-          const unsigned w0 = pack2bf(nm, 0.f); const float r1 = nm - bflo(w0);
-          const unsigned w1 = pack2bf(r1, 0.f); const float r2 = r1 - bflo(w1);
-          qe.x = (w0 & 0xffffu) | (w1 << 16); qe.y = pack2bf(r2, 1.0f);
-        }
-        first = false;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const bf8_t pf = pack8(s, sb);
-        lacc = MFMA32(__builtin_bit_cast(bf8_t, ones), pf, lacc);
-#pragma unroll
-        for (int d = 0; d < C::DBLK; ++d) acc[d] = MFMA32(rd_tr<HD>(sV, t * 32, sb, d, lane), pf, acc[d]);
-      }
-    }
-  }
-  const float lt = l + lacc[0];
-  const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-  if (qidx < L) {
-    bf16_t* dst = ctx + ((size_t)sg.start + qidx) * (H * HD) + head * HD;
-#pragma unroll
-    for (int d = 0; d < C::DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 32 * d + 8 * g + 4 * h;
-        if (dd < HD) {
-          u32x2 w; w.x = pack2bf(acc[d][4 * g] * inv, acc[d][4 * g + 1] * inv); w.y = pack2bf(acc[d][4 * g + 2] * inv, acc[d][4 * g + 3] * inv);
-          *reinterpret_cast<u32x2*>(dst + dd) = w;
-        }
-      }
-    if (lse_out && h == 0) lse_out[slab + qidx] = (m + __log2f(lt)) * 0.6931471805599453f;
-  }
+  attn_fwd_body<HD, false>(q, k, v, ctx, lse_out, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
 }
 
 template <int HD>
@@ -2624,84 +2560,10 @@ __global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dq(const bf16_t* __r
                                                             const bf16_t* __restrict__ dctx, const float* __restrict__ lse, float* __restrict__ delta,
                                                             const float* __restrict__ cosT, const float* __restrict__ sinT, float q_scale,
                                                             bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
-  typedef Cfg<HD> C;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sK = smem;
-  unsigned char* sV = sK + KC * C::ROWB;
-  u32x4* sE = reinterpret_cast<u32x4*>(sV + KC * C::ROWB);
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  const int L = sg.n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int qidx = sg.blk * 128 + wave * 32 + (lane & 31);
-  const int qrow = qidx < L ? qidx : L - 1;
-  const int dm = H * HD;
-  const size_t slab = (size_t)head * T_pad + sg.start;
-  const size_t tok = (size_t)sg.start + qrow;                    // token row of this lane's query
-  const bf16_t* kbase = k + slab * HD;
-  const bf16_t* vbase = v + slab * HD;
-  bf8_t qf[C::KSTEPS], dof[C::KSTEPS];
-#pragma unroll
-  for (int st = 0; st < C::KSTEPS; ++st) {
-    qf[st] = *reinterpret_cast<const bf8_t*>(q + (slab + qrow) * HD + 16 * st + 8 * h);
-    dof[st] = *reinterpret_cast<const bf8_t*>(dctx + tok * dm + head * HD + 16 * st + 8 * h);
-  }
-  const float lse_q = lse[slab + qrow] * LOG2E;
-  float delta_q = 0.f;
-#pragma unroll
-  for (int st = 0; st < C::KSTEPS; ++st) {
-    const u32x4 x = *reinterpret_cast<const u32x4*>(ctx + tok * dm + head * HD + 16 * st + 8 * h), y = __builtin_bit_cast(u32x4, dof[st]);
-    delta_q += bflo(x.x) * bflo(y.x) + bfhi(x.x) * bfhi(y.x) + bflo(x.y) * bflo(y.y) + bfhi(x.y) * bfhi(y.y) + bflo(x.z) * bflo(y.z) + bfhi(x.z) * bfhi(y.z) +
-               bflo(x.w) * bflo(y.w) + bfhi(x.w) * bfhi(y.w);
-  }
-  delta_q += __shfl_xor(delta_q, 32, 64);
-  if (h == 0 && qidx < L) delta[slab + qidx] = delta_q;
-  u32x4 qe = {0u, 0u, 0u, 0u}, de = {0u, 0u, 0u, 0u}, ones3 = {0u, 0u, 0u, 0u};
-  if (h == 0) {
-    unsigned w01, w2;
-    split3_bf16(-lse_q, w01, w2); qe.x = w01; qe.y = w2 | 0x3F800000u;
-    split3_bf16(-delta_q, w01, w2); de.x = w01; de.y = w2;
-    ones3.x = 0x3F803F80u; ones3.y = 0x00003F80u;
-  }
-  f32x16 acc[C::DBLK];
-#pragma unroll
-  for (int d = 0; d < C::DBLK; ++d) acc[d] = zero16();
-  for (int kc0 = 0; kc0 < L; kc0 += KC) {
-    const int nkeys = min(KC, L - kc0);
-    const int nrows = (nkeys + 31) & ~31;
-    __syncthreads();
-    load_tile_pair<HD>(sK, kbase + (size_t)kc0 * HD, HD, sV, vbase + (size_t)kc0 * HD, HD, nkeys, nrows);
-    for (int i = threadIdx.x; i <= KC; i += 256) {
-      u32x4 e = {0u, 0u, 0u, 0u};
-      if (i < nrows) {
-        const float bv = i < nkeys ? 0.f : -INFINITY;
-        e.x = 0x3F803F80u; e.y = 0x3F80u | (pack2bf(bv, 0.f) << 16);
-      }
-      sE[i] = e;
-    }
-    __syncthreads();
-    for (int t = 0; t < nrows / 32; ++t) {
-      const u32x4 ke = sE[h ? KC : t * 32 + (lane & 31)];
-      f32x16 s = MFMA32(__builtin_bit_cast(bf8_t, ke), __builtin_bit_cast(bf8_t, qe), zero16());
-      f32x16 dp = MFMA32(__builtin_bit_cast(bf8_t, ones3), __builtin_bit_cast(bf8_t, de), zero16());
-#pragma unroll
-      for (int st = 0; st < C::KSTEPS; ++st) {
-        s = MFMA32(rd_row<HD>(sK, t * 32 + (lane & 31), st, h), qf[st], s);
-        dp = MFMA32(rd_row<HD>(sV, t * 32 + (lane & 31), st, h), dof[st], dp);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]) * dp[r];
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const bf8_t dsf = pack8(s, sb);
-#pragma unroll
-        for (int d = 0; d < C::DBLK; ++d) acc[d] = MFMA32(rd_tr<HD>(sK, t * 32, sb, d, lane), dsf, acc[d]);
-      }
-    }
-  }
-  // the gathered rotary tables are per token: row = the token's row in the stream
-  if (qidx < L) unrope_store<HD>(acc, cosT, sinT, sg.start + qidx, h, q_scale, cosT != nullptr, dqkv + ((size_t)sg.start + qidx) * (3 * dm) + head * HD);
+  attn_bwd_dq_body<HD, false>(q, k, v, ctx, dctx, lse, delta, cosT, sinT, q_scale, dqkv, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
 }
 
 template <int HD>
@@ -2709,77 +2571,10 @@ __global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dkv(const bf16_t* __
                                                              const int* __restrict__ cu, const int* __restrict__ work, const bf16_t* __restrict__ dctx,
                                                              const float* __restrict__ lse, const float* __restrict__ delta, const float* __restrict__ cosT,
                                                              const float* __restrict__ sinT, bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
-  typedef Cfg<HD> C;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sQ = smem;
-  unsigned char* sdO = sQ + KC * C::ROWB;
-  u32x4* sQE = reinterpret_cast<u32x4*>(sdO + KC * C::ROWB);
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  const int L = sg.n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  const int kidx = sg.blk * 128 + wave * 32 + (lane & 31);
-  const int krow = kidx < L ? kidx : L - 1;
-  const int dm = H * HD;
-  const size_t slab = (size_t)head * T_pad + sg.start;
-  bf8_t kf[C::KSTEPS], vf[C::KSTEPS];
-#pragma unroll
-  for (int st = 0; st < C::KSTEPS; ++st) {
-    kf[st] = *reinterpret_cast<const bf8_t*>(k + (slab + krow) * HD + 16 * st + 8 * h);
-    vf[st] = *reinterpret_cast<const bf8_t*>(v + (slab + krow) * HD + 16 * st + 8 * h);
-  }
-  const float bias_k = kidx < L ? 0.f : -INFINITY;
-  u32x4 kS = {0u, 0u, 0u, 0u}, kD = {0u, 0u, 0u, 0u};
-  if (h == 0) { kS.x = 0x3F803F80u; kS.y = 0x3F80u | (pack2bf(bias_k, 0.f) << 16); kD.z = 0x3F803F80u; kD.w = 0x00003F80u; }
-  f32x16 adk[C::DBLK], adv[C::DBLK];
-#pragma unroll
-  for (int d = 0; d < C::DBLK; ++d) { adk[d] = zero16(); adv[d] = zero16(); }
-  for (int qc0 = 0; qc0 < L; qc0 += KC) {
-    const int nq = min(KC, L - qc0);
-    const int nrows = (nq + 31) & ~31;
-    __syncthreads();
-    load_tile_pair<HD>(sQ, q + (slab + qc0) * HD, HD, sdO, dctx + ((size_t)sg.start + qc0) * dm + head * HD, dm, nq, nrows);
-    for (int i = threadIdx.x; i <= KC; i += 256) {
-      u32x4 e = {0u, 0u, 0u, 0u};
-      if (i < nrows) {
-        unsigned w01, w2;
-        split3_bf16(i < nq ? -lse[slab + qc0 + i] * LOG2E : -1.0e30f, w01, w2);
-        e.x = w01; e.y = w2 | 0x3F800000u;
-        split3_bf16(i < nq ? -delta[slab + qc0 + i] : 0.f, w01, w2);
-        e.z = w01; e.w = w2;
-      }
-      sQE[i] = e;
-    }
-    __syncthreads();
-    for (int t = 0; t < nrows / 32; ++t) {
-      const bf8_t qe_row = __builtin_bit_cast(bf8_t, sQE[h ? KC : t * 32 + (lane & 31)]);
-      f32x16 s = MFMA32(qe_row, __builtin_bit_cast(bf8_t, kS), zero16());
-      f32x16 dp = MFMA32(qe_row, __builtin_bit_cast(bf8_t, kD), zero16());
-#pragma unroll
-      for (int st = 0; st < C::KSTEPS; ++st) {
-        s = MFMA32(rd_row<HD>(sQ, t * 32 + (lane & 31), st, h), kf[st], s);
-        dp = MFMA32(rd_row<HD>(sdO, t * 32 + (lane & 31), st, h), vf[st], dp);
-      }
-      f32x16 p;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r]); s[r] = p[r] * dp[r]; }
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const bf8_t pf = pack8(p, sb), dsf = pack8(s, sb);
-#pragma unroll
-        for (int d = 0; d < C::DBLK; ++d) {
-          adv[d] = MFMA32(rd_tr<HD>(sdO, t * 32, sb, d, lane), pf, adv[d]);
-          adk[d] = MFMA32(rd_tr<HD>(sQ, t * 32, sb, d, lane), dsf, adk[d]);
-        }
-      }
-    }
-  }
-  if (kidx < L) {
-    bf16_t* row = dqkv + ((size_t)sg.start + kidx) * (3 * dm) + head * HD;
-    unrope_store<HD>(adk, cosT, sinT, sg.start + kidx, h, 0.6931471805599453f, cosT != nullptr, row + dm);
-    unrope_store<HD>(adv, cosT, sinT, sg.start + kidx, h, 1.0f, false, row + 2 * dm);
-  }
+  attn_bwd_dkv_body<HD, false>(q, k, v, dctx, lse, delta, cosT, sinT, dqkv, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
 }
 
 // rows [cu[N], T_pad) of a bf16 [T_pad, width] tensor (width % 8 == 0) and, optionally, of the H rows of an fp32 [H, T_pad] tensor are set to zero

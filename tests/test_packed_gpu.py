@@ -163,6 +163,59 @@ def test_varlen_attention_backward(hd):
         assert (got - r).abs().max() < 0.05 * r.abs().max(), i
 
 
+@pytest.mark.parametrize("lengths", [[1], [33], [130], [257], [130, 130]], ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("hd", [16, 32, 64])
+def test_split_kernels_padded_equals_packed(hd, lengths):
+    """the padded and the packed split kernels are one body behind two decoders: the same sequences give the same bits through either.
+    1: a single row; 33: a partial 32-key tile; 130: a second 128-row block; 257: a second 256-key chunk holding one key; [130, 130]: the second
+    sequence (b = 1, start = 130) tells the head-major row, the token-major row and the rotary row of position 0 apart"""
+    torch.manual_seed(100 * hd + sum(lengths))
+    H, B, L = 2, len(lengths), lengths[0]
+    assert all(n == L for n in lengths)
+    n_real = B * L
+    p, T, cu = _pack_shape(lengths)
+    cos_pk, sin_pk = _gathered_tables(lengths, T, hd)
+    cos_pad, sin_pad = _rope_half(L, hd)
+    for a in cu[:-1]:
+        assert torch.equal(cos_pk[a:a + L], cos_pad) and torch.equal(sin_pk[a:a + L], sin_pad)
+    scale = hd ** -0.5
+    q = (_rot(torch.randn(H, T, hd), cos_pk, sin_pk) * scale * hip.LOG2E).to(torch.bfloat16).to(DEV)
+    k = _rot(torch.randn(H, T, hd), cos_pk, sin_pk).to(torch.bfloat16).to(DEV)
+    v = torch.randn(H, T, hd).to(torch.bfloat16).to(DEV)
+    dctx = torch.randn(T, H * hd).to(torch.bfloat16).to(DEV)
+    to_padded = lambda x: x[:, :n_real].reshape(H, B, L, -1).transpose(0, 1).contiguous()      # [H, T, *] -> [B, H, L, *]
+    q_pad, k_pad, v_pad = to_padded(q), to_padded(k), to_padded(v)
+    dctx_pad = dctx[:n_real].contiguous()
+    # packed
+    ctx_pk = torch.empty(T, H * hd, dtype=torch.bfloat16, device=DEV)
+    lse_pk = torch.empty(H, T, device=DEV)
+    dqkv_pk = torch.empty(T, 3 * H * hd, dtype=torch.bfloat16, device=DEV)
+    w = p.attn_work()
+    hip.call("oneprot_attn_varlen_fwd", q, k, v, p.cu_seqlens, w, w.shape[0], ctx_pk, lse_pk, len(p), T, H, hd)
+    ws = torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, T), dtype=torch.uint8, device=DEV)
+    hip.call("oneprot_attn_varlen_bwd", q, k, v, p.cu_seqlens, w, w.shape[0], ctx_pk, dctx, lse_pk, cos_pk.to(DEV), sin_pk.to(DEV), scale, dqkv_pk, ws,
+             len(p), T, H, hd)
+    # padded, through the split kernels
+    ctx_pad = torch.empty(n_real, H * hd, dtype=torch.bfloat16, device=DEV)
+    lse_pad = torch.empty(B, H, L, device=DEV)
+    dqkv_pad = torch.empty(n_real, 3 * H * hd, dtype=torch.bfloat16, device=DEV)
+    ws_pad = torch.empty(hip.query("oneprot_attn_bwd_workspace", B, H, L), dtype=torch.uint8, device=DEV)
+    try:
+        hip.query("oneprot_attn_force_fwd_path", 0)
+        hip.query("oneprot_attn_force_bwd_path", 0)
+        hip.call("oneprot_attn_fwd", q_pad, k_pad, v_pad, None, ctx_pad, lse_pad, B, H, L, hd)
+        hip.call("oneprot_attn_bwd", q_pad, k_pad, v_pad, None, ctx_pad, dctx_pad, lse_pad, cos_pad.to(DEV), sin_pad.to(DEV), scale, dqkv_pad, ws_pad,
+                 B, H, L, hd)
+    finally:
+        hip.query("oneprot_attn_force_fwd_path", -1)
+        hip.query("oneprot_attn_force_bwd_path", -1)
+    torch.cuda.synchronize()
+    assert torch.isfinite(ctx_pad.float()).all() and torch.isfinite(dqkv_pad.float()).all() and dqkv_pad.float().abs().max() > 0
+    assert torch.equal(ctx_pk[:n_real], ctx_pad)
+    assert torch.equal(to_padded(lse_pk[:, :, None])[..., 0], lse_pad)
+    assert torch.equal(dqkv_pk[:n_real], dqkv_pad)
+
+
 # ------------------------------------------------------------------------------------------------------------------ 3. packed embedding
 def test_packed_embedding_forward_backward():
     torch.manual_seed(4)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Runs a handful of attention forward + backward launches at the cfg-2 shape (for rocprofv3 passes) and prints their event-timed durations.
-usage: attn_only.py [iters] [B]"""
+usage: attn_only.py [iters] [B]      (ATTN_L, ATTN_H, ATTN_HD: sequence length, heads, head dim -- default 512, 20, 32; hd 64 always takes the split backward)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,7 +8,7 @@ from oneprot_amd import hip
 if os.environ.get("G8_LIB"): hip.LIB_PATH = os.path.abspath(os.environ["G8_LIB"])
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-L, H, hd = int(os.environ.get("ATTN_L", "512")), 20, 32
+L, H, hd = int(os.environ.get("ATTN_L", "512")), int(os.environ.get("ATTN_H", "20")), int(os.environ.get("ATTN_HD", "32"))
 g = torch.Generator(device="cuda").manual_seed(0)
 mk = lambda: (torch.randn(B, H, L, hd, device="cuda", generator=g) * 0.7).to(torch.bfloat16)
 q, k, v = mk(), mk(), mk()
