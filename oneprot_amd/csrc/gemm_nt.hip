@@ -118,7 +118,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[MT
       if (half > 0 || pass > 0) {            // 8 rows further than the previous pass
         const int hh = p.hd >> 1;
         rp_l += 8; rp_off += (size_t)8 * p.hd; rp_cos += 8 * hh; rp_sin += 8 * hh;
-        if (rp_l >= p.L) { rp_l -= p.L; rp_off += (size_t)(p.H - 1) * p.L * p.hd; rp_cos -= (size_t)p.L * hh; rp_sin -= (size_t)p.L * hh; }
+        // (a loop: with L < 8 one step of 8 rows crosses several sequence boundaries; for L >= 8 it runs once at the most)
+        while (rp_l >= p.L) { rp_l -= p.L; rp_off += (size_t)(p.H - 1) * p.L * p.hd; rp_cos -= (size_t)p.L * hh; rp_sin -= (size_t)p.L * hh; }
       }
     }
     if (!FULL && gm >= p.M) continue;

@@ -619,7 +619,8 @@ def test_gemm_tn(M, N, K, tn_variant):
     assert_close(db, dY.float().sum(0), 1e-4, 1e-2, "tn fused bias grad")
     hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, None, w, w.numel(), 1)
     assert_close(dW, 2 * ref, 1e-4, 4e-3 * math.sqrt(M / 64), "tn accumulate")
-    # strided views: columns [N0:N0+n) of a wider matrix
+    # (leading dimensions that differ from the logical width -- column slices of wider matrices -- and the narrow adapter shapes:
+    # tests/test_gemm_small_shapes_gpu.py, test_gemm_tn_narrow_and_strided)
     cs = torch.full((N,), -1.0, device=DEV)
     w2 = ws(hip.query("oneprot_colsum_workspace", N))
     hip.call("oneprot_colsum_bf16", dY, cs, w2, M, N, 0)
