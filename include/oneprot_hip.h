@@ -306,6 +306,22 @@ int oneprot_attnpool_packed_fwd(const float* x, const int64_t* ids, const int* c
 int oneprot_attnpool_packed_bwd(const float* x, const float* attn, const int* cu_seqlens, const float* w, const float* dpooled, float* dw, float* db,
                                 float* dx, void* workspace, int N, int T_pad, int max_len, int d, void* stream);
 
+/* ---------------- retrieval without the N x N matrix (ref retrieval_metric.py:83-102, eval.py:158-184) --------------------------------------
+ * S, M, Q, Db: fp32 row-major [rows, D], any D >= 1.  Every similarity is the k-ordered fp32 chain acc = fmaf(a_k, b_k, acc) from k = 0 (formed by
+ * the fp32-input MFMA): the values of oneprot_sgemm with alpha = 1, bit for bit, so the ranks below equal those of oneprot_sgemm + oneprot_diag_rank. */
+/* diag[i] = S_i . M_i, bit-equal to element (i, i) of the tiles of oneprot_sim_rank (ref retrieval_metric.py:86: the matching pair's similarity). */
+int oneprot_sim_pair_dot(const float* S, const float* M, float* diag, int N, int D, void* stream);
+/* The row slab [row0, row0 + rows) of S against all N rows of M (ref retrieval_metric.py:83-102: sort + position of the diagonal, here counted):
+   rank_row[i] += #{ j : S_i . M_j > diag[i] } (complete for the slab's rows); rank_col[j] += #{ i in slab : S_i . M_j > diag[j] } (partial: summed over
+   the slabs of a whole pass it is complete).  Strict >, int32 counts added with integer atomics (deterministic); the caller zeroes both before the first slab. */
+int oneprot_sim_rank(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, void* stream);
+/* The k largest Q_i . Db_j over the N database rows for each of the nq queries (ref eval.py:158-184 ranks every row the same way): scores fp32 [nq, k]
+   descending, indices int64 [nq, k]; equal scores in ascending database index.  1 <= k <= min(N, 256); finite inputs.  workspace: at least
+   oneprot_sim_topk_workspace(nq, N, k) bytes (0 for invalid arguments), 8-byte aligned: [splits, nq, k] partial lists, never O(nq * N). */
+size_t oneprot_sim_topk_workspace(int nq, int N, int k);
+int oneprot_sim_topk(const float* Q, const float* Db, int nq, int N, int D, int k, float* scores, int64_t* indices, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

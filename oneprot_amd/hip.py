@@ -116,6 +116,10 @@ _SIGS = {
     "oneprot_lnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
     "oneprot_attnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
     "oneprot_attnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "oneprot_sim_pair_dot": (I, [P, P, P, I, I, P]),
+    "oneprot_sim_rank": (I, [P, P, P, I, I, I, I, P, P, P]),
+    "oneprot_sim_topk_workspace": (SZ, [I, I, I]),
+    "oneprot_sim_topk": (I, [P, P, I, I, I, I, P, P, P, SZ, P]),
 }
 
 # Expected element type of every pointer argument, in order (f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a
@@ -133,6 +137,7 @@ _PTR_DTYPES = {
     "oneprot_esm_embed_packed_fwd": "lifffffff", "oneprot_esm_embed_packed_bwd": "lfffb", "oneprot_attn_varlen_fwd": "hhhiihf",
     "oneprot_attn_varlen_bwd": "hhhiihhfffhb", "oneprot_lnpool_packed_fwd": "flifffffff", "oneprot_lnpool_packed_bwd": "fiffffffhffb",
     "oneprot_attnpool_packed_fwd": "fliffff", "oneprot_attnpool_packed_bwd": "ffifffffb",
+    "oneprot_sim_pair_dot": "fff", "oneprot_sim_rank": "fffii", "oneprot_sim_topk": "ffflb",
 }
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 

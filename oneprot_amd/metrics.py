@@ -1,16 +1,41 @@
 """RetrievalMetric on the device (replaces ref src/models/components/retrieval_metric.py for the validation / test hooks of
 OneProtLitModule).  Same interface (`update(sequence_features, modality_features)`, `compute() -> dict`,
 `reset()`, keys `{seq_to_mod,mod_to_seq}_{median_rank,R@k}`), but the N x N similarity matrix stays on the GPU and the rank of each
-matching pair is COUNTED (entries beating the diagonal) by one kernel instead of argsorting every row on the CPU."""
-import numpy as np
+matching pair is COUNTED (entries beating the diagonal) by one kernel instead of argsorting every row on the CPU.
+
+Two paths give the same ranks bit for bit: up to `max_logits_bytes` of similarity matrix (1 GiB: N = 16 384) the matrix is written by `oneprot_sgemm` and
+counted by `oneprot_diag_rank`; beyond it the streaming kernels of oneprot_amd.retrieval count tile by tile and never hold the matrix.
+ONEPROT_RETRIEVAL_STREAM=1 / 0 forces the streaming / the matrix path; ONEPROT_RETRIEVAL_LOGITS_BYTES sets the default threshold."""
+import os
+
 import torch
 
-from . import hip
+from . import hip, retrieval
+
+DEFAULT_MAX_LOGITS_BYTES = 1 << 30
+
+
+def _ranks_matrix(s, m):
+    """(rank_row, rank_col) through the full N x N fp32 matrix"""
+    N, D = s.shape
+    logits = torch.empty(N, N, device=s.device)
+    hip.call("oneprot_sgemm", s, m, logits, N, N, D, 0, 0, 1.0, 0)
+    rr = torch.empty(N, dtype=torch.int32, device=s.device)
+    rc = torch.empty(N, dtype=torch.int32, device=s.device)
+    hip.call("oneprot_diag_rank", logits, rr, rc, N)
+    return rr, rc
+
+
+def _ranks_streaming(s, m):
+    return retrieval.pair_ranks(s, m)
 
 
 class RetrievalMetric:
-    def __init__(self, k=(1, 10, 100)):
+    def __init__(self, k=(1, 10, 100), *, max_logits_bytes=None):
         self.k = list(k)
+        if max_logits_bytes is None:
+            max_logits_bytes = int(os.environ.get("ONEPROT_RETRIEVAL_LOGITS_BYTES", DEFAULT_MAX_LOGITS_BYTES))
+        self.max_logits_bytes = int(max_logits_bytes)
         self.reset()
 
     def reset(self):
@@ -70,18 +95,14 @@ class RetrievalMetric:
         m = torch.cat([o[:c] for o, c in zip(outs_m, counts)])
         return s.contiguous(), m.contiguous()
 
+    def uses_streaming(self, N):
+        """ONEPROT_RETRIEVAL_STREAM=1 / 0 decides when set; otherwise the size of the N x N fp32 matrix against max_logits_bytes"""
+        v = os.environ.get("ONEPROT_RETRIEVAL_STREAM")
+        if v is not None and v != "":
+            return v != "0"
+        return N * N * 4 > self.max_logits_bytes
+
     def compute(self):
         s, m = self._gathered()
-        N, D = s.shape
-        logits = torch.empty(N, N, device=s.device)
-        hip.call("oneprot_sgemm", s, m, logits, N, N, D, 0, 0, 1.0, 0)
-        rr = torch.empty(N, dtype=torch.int32, device=s.device)
-        rc = torch.empty(N, dtype=torch.int32, device=s.device)
-        hip.call("oneprot_diag_rank", logits, rr, rc, N)
-        out = {}
-        for name, ranks in (("seq_to_mod", rr), ("mod_to_seq", rc)):
-            r = ranks.cpu().numpy()
-            out[f"{name}_median_rank"] = float(np.floor(np.median(r)) + 1)
-            for k in self.k:
-                out[f"{name}_R@{k}"] = float(np.mean(r < k))
-        return out
+        rr, rc = _ranks_streaming(s, m) if self.uses_streaming(s.shape[0]) else _ranks_matrix(s, m)
+        return retrieval.metrics_from_ranks(rr, rc, self.k)
