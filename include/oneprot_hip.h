@@ -179,8 +179,11 @@ int oneprot_attn_bwd(const void* q, const void* k, const void* v, const float* k
    ctx = (keep * softmax / keep_prob) @ V, lse = that of the undropped softmax.  Same arguments as oneprot_attn_fwd otherwise. */
 int oneprot_attn_fwd_dropout(const void* q, const void* k, const void* v, const float* key_bias, void* ctx, float* lse, int B, int H, int L, int hd,
                              float p, uint64_t seed, uint64_t stream_id, void* stream);
-/* Its backward (the two split kernels, any hd / L): dV = (keep * P / keep_prob)^T dO, dS = P * (keep * dP / keep_prob - delta), the mask regenerated
-   from the same (p, seed, stream_id).  Same arguments as oneprot_attn_bwd otherwise. */
+/* Its backward (the two split kernels; hd 16 / 32 / 64, any L): dV = (keep * P / keep_prob)^T dO, dS = P * (keep * dP / keep_prob - delta), the mask
+   regenerated from the same (p, seed, stream_id).  Same arguments as oneprot_attn_bwd otherwise.
+   In all three calls p becomes the 16-bit threshold thr16 = (unsigned)(p * 65536 + 0.5) in fp32: an element is kept iff the upper 16 bits of its hash are
+   >= thr16, and kept values are scaled by 65536 / (65536 - thr16).  p < 2^-17 gives thr16 = 0, no dropout at all; p < 0, NaN, p >= 1 and any
+   p >= 1 - 2^-17 (thr16 = 65536: nothing would be kept) are refused with OP_EINVAL, as is any other hd. */
 int oneprot_attn_bwd_dropout(const void* q, const void* k, const void* v, const float* key_bias, const void* ctx, const void* dctx, const float* lse,
                              const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv, void* workspace, int B, int H, int L, int hd,
                              float p, uint64_t seed, uint64_t stream_id, void* stream);
