@@ -293,6 +293,34 @@ size_t oneprot_attn_varlen_bwd_workspace(int H, int T_pad);
 int oneprot_attn_varlen_bwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
                             const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
                             void* workspace, int N, int T_pad, int H, int hd, void* stream);
+/* The same two calls with attention-probability dropout (hf modeling_bert.py BertSelfAttention: softmax -> dropout -> @ V, per sequence; ref
+   text_encoder.py:54-62 runs the text tower in train mode, here on a packed batch of captions).  Element (query i, key j) of head h of segment s is
+   kept iff the padded kernels keep element (i, j) of stream s * H + h: i, j are positions within the segment, s the segment's index in cu_seqlens (not
+   its place in `work`).  A packed batch therefore drops exactly what oneprot_attn_fwd_dropout drops on the padded batch of the same sequences in the
+   same order, and oneprot_attn_dropout_keep(keep, N, H, max_len, ...)[s, h, :n_s, :n_s] is its mask.  Row sum, LSE and delta are those of the undropped
+   softmax.  p, seed, stream_id, hd and the rope tables (both NULL or both given) as oneprot_attn_fwd_dropout / oneprot_attn_bwd_dropout: OP_EINVAL
+   and no launch otherwise. */
+int oneprot_attn_varlen_fwd_dropout(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse,
+                                    int N, int T_pad, int H, int hd, float p, uint64_t seed, uint64_t stream_id, void* stream);
+int oneprot_attn_varlen_bwd_dropout(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
+                                    const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
+                                    void* workspace, int N, int T_pad, int H, int hd, float p, uint64_t seed, uint64_t stream_id, void* stream);
+/* BERT embeddings on a packed stream (hf modeling_bert.py:53-108; ref text_encoder.py:54-62): row t = LN(word[id_t] + pos[t - start of t's segment] +
+   type0), absolute positions restarting at every segment; tail rows take position 0 (finite).  pos is [n_pos, d]; every segment <= n_pos tokens (the
+   caller checks: the kernel clamps the position).  d % 4 == 0, d <= 2048. */
+int oneprot_bert_embed_packed_fwd(const int64_t* ids, const int* cu_seqlens, const float* word, const float* pos, const float* type0, const float* gamma,
+                                  const float* beta, float* x_f32, void* x_bf16, int N, int T_pad, int d, int vocab, int n_pos, float eps, void* stream);
+/* its position-table gradient (hf modeling_bert.py:53-108, position_embeddings; ref text_encoder.py:33 trains it when the tower is not frozen):
+   dpos[l] = sum over the segments s with n_s > l of de[cu_seqlens[s] + l] for l < n_rows, segments in ascending order, no atomics (deterministic);
+   rows no segment reaches are written as 0; the tail rows of de [T_pad, d] are never read. */
+int oneprot_segment_possum_f32(const float* de, const int* cu_seqlens, float* dpos, int N, int T_pad, int n_rows, int d, void* stream);
+/* pooling per segment without a LayerNorm in front (post-LN BERT; ref base_encoder.py:109-126 from text_encoder.py:54-62): mode 0 the mean over the
+   segment's tokens != pad_id, 1 its first row: the rule of oneprot_pool_fwd.  x fp32 [T_pad, d] -> pooled [N, d]. */
+int oneprot_pool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, float* pooled, int N, int T_pad, int d, int mode,
+                            void* stream);
+/* its backward (ref base_encoder.py:109-126 under autograd): g fp32 [T_pad, d] (+ optional bf16 copy); tail rows exactly 0. */
+int oneprot_pool_packed_bwd(const float* dpooled, const int64_t* ids, const int* cu_seqlens, int pad_id, float* g, void* g_bf16, int N, int T_pad, int d,
+                            int mode, void* stream);
 /* final LayerNorm fused with pooling per sequence (hf modeling_esm.py:552; ref base_encoder.py:109-126): mode 0 mean, 1 CLS; x fp32 [T_pad, d] ->
    pooled [N, d]; mean / rstd / wrow per stream row (wrow = 0 on the tail), hidden_f32 [T_pad, d] optional. */
 int oneprot_lnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* gamma, const float* beta, float* pooled,

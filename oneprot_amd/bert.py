@@ -12,6 +12,7 @@ import torch
 
 from . import hip
 from .esm import ArenaModule, ModelConfig, load_weight_file, resolve_config, _Out
+from .packing import PackedTokens
 
 BERT_DEFAULTS = dict(model_type="bert", vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                      max_position_embeddings=512, type_vocab_size=2, pad_token_id=0, layer_norm_eps=1e-12, initializer_range=0.02,
@@ -31,8 +32,115 @@ def resolve_bert_config(model_name_or_path):
     raise OSError(f"{model_name_or_path} is not a local folder with a config.json and is not a known BERT model identifier")
 
 
+class _PaddedLayout:
+    """The layout-dependent stages of the BERT tower on a padded [B, L] batch: embedding (position l = row % L), attention (key-padding bias, with or
+    without probability dropout) and the position-table gradient (sum over the batch).  Everything else runs row-wise on the B*L rows."""
+    packed = False
+
+    def __init__(self, tr, ids):
+        self.ids = ids.contiguous()
+        self.B, self.L = ids.shape
+        self.T = self.B * self.L
+
+    def embed(self, tr, x, h):
+        cfg, e = tr.config, "embeddings."
+        self.key_bias = torch.empty(self.B, self.L, dtype=torch.float32, device=x.device)
+        hip.call("oneprot_key_padding_bias", self.ids, self.key_bias, self.T, cfg.pad_token_id)
+        hip.call("oneprot_bert_embed_fwd", self.ids, tr.view(e + "word_embeddings.weight"), tr.view(e + "position_embeddings.weight"),
+                 tr.view(e + "token_type_embeddings.weight"), tr.view(e + "LayerNorm.weight"), tr.view(e + "LayerNorm.bias"), x, h, self.B, self.L, tr.d,
+                 cfg.vocab_size, cfg.layer_norm_eps)
+
+    def attn_fwd(self, q, k, v, ctx, lse, H, hd, drop=None):
+        if drop is not None:
+            hip.call("oneprot_attn_fwd_dropout", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd, *drop)
+        else:
+            hip.call("oneprot_attn_fwd", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd)
+
+    def attn_workspace(self, H, dev):
+        return torch.empty(hip.query("oneprot_attn_bwd_workspace", self.B, H, self.L), dtype=torch.uint8, device=dev)
+
+    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd, drop=None):
+        if drop is not None:
+            hip.call("oneprot_attn_bwd_dropout", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], None, None, q_scale, dqkv, ws,
+                     self.B, H, self.L, hd, *drop)
+        else:
+            hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], None, None, q_scale, dqkv, ws, self.B, H, self.L, hd)
+
+    def pos_rows(self, tr):
+        """the position-embedding row of every token: fp32 [T, d]"""
+        return tr.view("embeddings.position_embeddings.weight")[:self.L].repeat(self.B, 1)
+
+    def pos_bwd(self, de, dpos, d):
+        """dpos rows 0 .. n-1 from de [T, d]: the sum over the batch; returns n"""
+        hip.call("oneprot_rowsum_f32", de, dpos[:self.L], self.B, self.L * d)
+        return self.L
+
+
+class _PackedLayout:
+    """The same stages on a packed caption stream (oneprot_amd.packing, pad id = the tower's pad_token_id): the row-wise stages see ONE sequence of T_pad
+    rows (B = 1, L = T_pad; the QKV epilogue's rotary tables are the (1, 0) rows of _norope(T_pad)); absolute positions restart at every segment,
+    attention runs per segment (varlen kernels; no key-bias tensor is built: the segment end is the only mask) and the position-table gradient sums
+    row l over the segments that reach it.  Tail rows hold the pad id: finite activations, exactly zero gradient rows.
+
+    Dropout: the attention-probability masks are those of the padded batch of the same captions in the same order (stream s * H + h, positions within
+    the segment).  The hidden-state Philox masks are indexed by element of the [T_pad, d] stream, so they differ from the padded layout's [B * L, d]
+    masks: the same distribution, another draw."""
+    packed = True
+
+    def __init__(self, tr, packed):
+        self.p = packed
+        self.ids = packed.ids
+        self.cu = packed.cu_seqlens
+        self.N, self.B, self.L = len(packed), 1, packed.T_pad
+        self.T = packed.T_pad
+        self.work = packed.attn_work()
+
+    def embed(self, tr, x, h):
+        cfg, e = tr.config, "embeddings."
+        hip.call("oneprot_bert_embed_packed_fwd", self.ids, self.cu, tr.view(e + "word_embeddings.weight"), tr.view(e + "position_embeddings.weight"),
+                 tr.view(e + "token_type_embeddings.weight"), tr.view(e + "LayerNorm.weight"), tr.view(e + "LayerNorm.bias"), x, h, self.N, self.T, tr.d,
+                 cfg.vocab_size, cfg.max_position_embeddings, cfg.layer_norm_eps)
+
+    def attn_fwd(self, q, k, v, ctx, lse, H, hd, drop=None):
+        if drop is not None:
+            hip.call("oneprot_attn_varlen_fwd_dropout", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd, *drop)
+        else:
+            hip.call("oneprot_attn_varlen_fwd", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd)
+
+    def attn_workspace(self, H, dev):
+        return torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, self.T), dtype=torch.uint8, device=dev)
+
+    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd, drop=None):
+        if drop is not None:
+            hip.call("oneprot_attn_varlen_bwd_dropout", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], None, None,
+                     q_scale, dqkv, ws, self.N, self.T, H, hd, *drop)
+        else:
+            hip.call("oneprot_attn_varlen_bwd", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], None, None, q_scale,
+                     dqkv, ws, self.N, self.T, H, hd)
+
+    def pos_rows(self, tr):
+        # the position of every stream row, built on the host from the lengths (no device read-back); tail rows take position 0
+        key = ("bert_pos", str(self.ids.device))
+        idx = self.p._work.get(key)
+        if idx is None:
+            host = torch.zeros(self.T, dtype=torch.int64)
+            host[:self.p.n_tokens] = torch.cat([torch.arange(n) for n in self.p.lengths])
+            idx = self.p._work[key] = host.to(self.ids.device)
+        return tr.view("embeddings.position_embeddings.weight")[idx]
+
+    def pos_bwd(self, de, dpos, d):
+        n = self.p.max_len
+        hip.call("oneprot_segment_possum_f32", de, self.cu, dpos[:n], self.N, self.T, n, d)
+        return n
+
+
+def _layout(tr, ids):
+    return _PackedLayout(tr, ids) if isinstance(ids, PackedTokens) else _PaddedLayout(tr, ids)
+
+
 class BertTransformer(ArenaModule):
     final_layer_norm = False      # post-LN model: pooling reads the last layer's output directly
+    accepts_packed = True         # run_layers / backward_layers take a PackedTokens stream (oneprot_amd.packing)
 
     def __init__(self, config):
         super().__init__()
@@ -120,27 +228,25 @@ class BertTransformer(ArenaModule):
 
     @torch.no_grad()
     def run_layers(self, ids, save=False):
-        """Embeddings + n post-LN layers.  Returns (last hidden state fp32 [T,d], saved-dict or None)."""
+        """Embeddings + n post-LN layers on padded ids [B, L] or a PackedTokens stream (B = 1, L = T_pad for every row-wise stage).
+        Returns (last hidden state fp32 [T,d], saved-dict or None)."""
+        cfg = self.config
+        if isinstance(ids, PackedTokens) and ids.max_len > cfg.max_position_embeddings:
+            raise ValueError(f"sequence length {ids.max_len} exceeds max_position_embeddings {cfg.max_position_embeddings}")
         if not ids.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
         self._refresh_bf16()
-        cfg = self.config
-        B, L = ids.shape
-        if L > cfg.max_position_embeddings:
+        lay = _layout(self, ids)
+        B, L = lay.B, lay.L
+        if not lay.packed and L > cfg.max_position_embeddings:
             raise ValueError(f"sequence length {L} exceeds max_position_embeddings {cfg.max_position_embeddings}")
         T, d, f, H, hd = B * L, self.d, self.f, self.H, self.hd
         dev = ids.device
-        ids = ids.contiguous()
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
         one, zero = self._norope(L, dev)
-        key_bias = f32(B, L)
-        hip.call("oneprot_key_padding_bias", ids, key_bias, T, cfg.pad_token_id)
         x, h, tmp = f32(T, d), b16(T, d), f32(T, d)
-        e = "embeddings."
-        hip.call("oneprot_bert_embed_fwd", ids, self.view(e + "word_embeddings.weight"), self.view(e + "position_embeddings.weight"),
-                 self.view(e + "token_type_embeddings.weight"), self.view(e + "LayerNorm.weight"), self.view(e + "LayerNorm.bias"), x, h, B, L, d,
-                 cfg.vocab_size, cfg.layer_norm_eps)
+        lay.embed(self, x, h)
         drop = self._train_dropout()
         if drop:      # hf's train-mode dropouts: embeddings, attention probabilities, the two dense outputs of every layer
             drop_call = self._drop_calls
@@ -149,7 +255,7 @@ class BertTransformer(ArenaModule):
             y_drop = f32(T, d)
             hip.call("oneprot_dropout_f32", x, x, T * d, p_h, self._drop_seed, self._drop_stream(drop_call, -1, 0))
             hip.call("oneprot_cast_f32_to_bf16", x, h, T * d)
-        saved = dict(ids=ids, key_bias=key_bias, layers=[], B=B, L=L) if save else None
+        saved = dict(layout=lay, layers=[], B=B, L=L) if save else None
         if drop and save:
             saved["drop_call"] = drop_call
         q, k, v, ctx, u = b16(B, H, L, hd), b16(B, H, L, hd), b16(B, H, L, hd), b16(T, d), b16(T, f)
@@ -186,7 +292,7 @@ class BertTransformer(ArenaModule):
                 hip.call("oneprot_gemm_bf16_nt", h, self._bf16[o:o + n], T, 3 * d, d, d, d, hip.EPI_QKV_ROPE, self.flat.data[ob:ob + nb], q, k, v, None,
                          one, zero, hd ** -0.5 * hip.LOG2E, L, H, hd)
             if drop:
-                hip.call("oneprot_attn_fwd_dropout", q, k, v, key_bias, ctx, lse, B, H, L, hd, p_a, self._drop_seed, self._drop_stream(drop_call, i, 0))
+                lay.attn_fwd(q, k, v, ctx, lse, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
                 # s1 = x + dropout(ctx Wo^T + bo): the residual add leaves the GEMM epilogue so that the mask can sit between the two
                 hip.call("oneprot_gemm_bf16_nt", ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, d, d, hip.EPI_F32,
                          self.view(p + "attention.output.dense.bias"), y_drop, None, None, None, None, None, 1.0, 0, 0, 0)
@@ -194,7 +300,7 @@ class BertTransformer(ArenaModule):
                 hip.call("oneprot_dropout_add_layernorm_fwd", y_drop, x, s1 if save else None, self.view(p + "attention.output.LayerNorm.weight"),
                          self.view(p + "attention.output.LayerNorm.bias"), y16, y1, m1, r1, T, d, eps, p_h, self._drop_seed, self._drop_stream(drop_call, i, 1))
             else:
-                hip.call("oneprot_attn_fwd", q, k, v, key_bias, ctx, lse, B, H, L, hd)
+                lay.attn_fwd(q, k, v, ctx, lse, H, hd)
                 hip.call("oneprot_gemm_bf16_nt", ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, d, d, hip.EPI_BIAS_RESID,
                          self.view(p + "attention.output.dense.bias"), s1, None, None, x, None, None, 1.0, 0, 0, 0)
                 hip.call("oneprot_layernorm_fwd", s1, 0, self.view(p + "attention.output.LayerNorm.weight"), self.view(p + "attention.output.LayerNorm.bias"), y16, y1,
@@ -221,6 +327,7 @@ class BertTransformer(ArenaModule):
         """g: fp32 [T,d] gradient w.r.t. the last layer's output (consumed), g16 unused (post-LN layers start with a LayerNorm backward);
         gflat: fp32 arena gradient (written).  Per layer, backwards (hf modeling_bert.py:354-417):
           y2 = LN2(s2), s2 = y1 + gelu(y1 W1^T + b1) W2^T + b2 ;  y1 = LN1(s1), s1 = x + attn(x) Wo^T + bo."""
+        lay = saved["layout"]
         B, L = saved["B"], saved["L"]
         T, d, f, H, hd = B * L, self.d, self.f, self.H, self.hd
         dev = g.device
@@ -235,7 +342,7 @@ class BertTransformer(ArenaModule):
             lora_raw = self._lora_raw = self._lora_raw_buffers(dev)
             tn_shapes += ((3 * d, self._lora_ops["Rp"]), (self._lora_ops["rp"], d))
         ws_tn = self._tn_workspace(tn_shapes, dev)
-        ws_at = torch.empty(hip.query("oneprot_attn_bwd_workspace", B, H, L), dtype=torch.uint8, device=dev)
+        ws_at = lay.attn_workspace(H, dev)
         ds, ds16, gy = f32(T, d), b16(T, d), f32(T, d)
         dz, dctx, dqkv = b16(T, f), b16(T, d), b16(T, 3 * d)
         drop_call = saved.get("drop_call")                 # the forward ran hf's train-mode dropouts: every mask is regenerated from (seed, call, layer, site)
@@ -270,10 +377,9 @@ class BertTransformer(ArenaModule):
             hip.call("oneprot_gemm_bf16_nt", da16, self._bf16_T[(i, "o")], T, d, d, d, d, hip.EPI_BF16, None, dctx, None, None, None, None, None, 1.0, 0, 0, 0)
             # ---- attention (no rotary: cos/sin = null)
             if drop_call is not None:
-                hip.call("oneprot_attn_bwd_dropout", st["q"], st["k"], st["v"], saved["key_bias"], st["ctx"], dctx, st["lse"], None, None, hd ** -0.5, dqkv, ws_at,
-                         B, H, L, hd, p_a, self._drop_seed, self._drop_stream(drop_call, i, 0))
+                lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
             else:
-                hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], saved["key_bias"], st["ctx"], dctx, st["lse"], None, None, hd ** -0.5, dqkv, ws_at, B, H, L, hd)
+                lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd)
             # ---- QKV projection; g = ds (residual branch) + dqkv Wqkv
             o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
             ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
@@ -285,19 +391,20 @@ class BertTransformer(ArenaModule):
             saved["layers"][i] = None
         if drop_call is not None:                          # x0 = dropout(LN(embeddings))
             hip.call("oneprot_dropout_f32", g, g, T * d, p_h, self._drop_seed, self._drop_stream(drop_call, -1, 0))
-        self._embedding_backward(saved["ids"], g, gflat)
+        self._embedding_backward(lay, g, gflat)
         if on_ready is not None:
             on_ready(0, self._total)
 
-    def _embedding_backward(self, ids, g, gflat):
+    def _embedding_backward(self, lay, g, gflat):
         """x0 = LN(word[id] + pos[l] + type[0]) (hf modeling_bert.py:53-108).  The pre-LN sum is re-gathered (torch indexing: data movement),
-        LayerNorm statistics / backward and the table reductions are HIP kernels; equal token ids are summed in sorted order."""
+        LayerNorm statistics / backward and the table reductions are HIP kernels; equal token ids are summed in sorted order.  On a packed stream l is the
+        position within the segment and the tail rows (pad ids, zero gradient rows) add nothing to any table."""
         cfg = self.config
-        B, L = ids.shape
-        T, d, dev = B * L, self.d, ids.device
+        ids = lay.ids
+        T, d, dev = lay.T, self.d, ids.device
         e = "embeddings."
         gv = lambda name: self.view(name, gflat)
-        esum = (self.view(e + "word_embeddings.weight")[ids.reshape(-1)] + self.view(e + "position_embeddings.weight")[:L].repeat(B, 1)
+        esum = (self.view(e + "word_embeddings.weight")[ids.reshape(-1)] + lay.pos_rows(self)
                 + self.view(e + "token_type_embeddings.weight")[0]).contiguous()
         mean, rstd, y = torch.empty(T, device=dev), torch.empty(T, device=dev), torch.empty(T, d, device=dev)
         hip.call("oneprot_layernorm_fwd", esum, 0, self.view(e + "LayerNorm.weight"), self.view(e + "LayerNorm.bias"), None, y, mean, rstd, T, d, cfg.layer_norm_eps)
@@ -305,10 +412,10 @@ class BertTransformer(ArenaModule):
         ws_ln = torch.empty(hip.query("oneprot_layernorm_bwd_workspace", d), dtype=torch.uint8, device=dev)
         hip.call("oneprot_layernorm_bwd", g, 1, None, 0, esum, 0, self.view(e + "LayerNorm.weight"), mean, rstd, None, de, None,
                  gv(e + "LayerNorm.weight"), gv(e + "LayerNorm.bias"), ws_ln, T, d, 0)
-        # position rows 0..L-1: sum over the batch; token-type row 0: sum over positions of that
+        # position rows 0..n-1: sum over the batch (packed: over the segments that reach the row); token-type row 0: sum over positions of that
         dpos = gv(e + "position_embeddings.weight")
-        hip.call("oneprot_rowsum_f32", de, dpos[:L], B, L * d)
-        hip.call("oneprot_rowsum_f32", dpos[:L], gv(e + "token_type_embeddings.weight")[0], L, d)
+        n = lay.pos_bwd(de, dpos, d)
+        hip.call("oneprot_rowsum_f32", dpos[:n], gv(e + "token_type_embeddings.weight")[0], n, d)
         # word rows: stable sort of the ids, one block per run of equal ids (padding_idx row gets no gradient, as nn.Embedding)
         sorted_ids, perm = torch.sort(ids.reshape(-1), stable=True)
         rows, counts = torch.unique_consecutive(sorted_ids, return_counts=True)
@@ -318,7 +425,10 @@ class BertTransformer(ArenaModule):
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, **_):
+        """BertModel-compatible call returning .last_hidden_state; a packed input gives the stream's [T_pad, d] (tail rows: finite, meaningless)"""
         x, _ = self.run_layers(input_ids, save=False)
+        if isinstance(input_ids, PackedTokens):
+            return _Out(x)
         B, L = input_ids.shape
         return _Out(x.view(B, L, self.d))
 

@@ -2525,10 +2525,12 @@ extern "C" int oneprot_attn_bwd(const void* q, const void* k, const void* v, con
 //   trow  = start                  (ctx / dctx are [T_pad, H*hd], dqkv [T_pad, 3*H*hd]);
 //   bias  = null: the segment end masks the last partial key tile (its zero-filled rows get -inf in the extra k-step), there is no key-bias tensor;
 //   rope0 = start: the rotary tables are gathered per token, row = the token's row in the stream;
-//   DROP  = false, with a default AttnDrop (the packed towers, ESM, have no probability dropout).
+//   bh    = seg * H + head, seg the segment's index in cu_seqlens (not its place in the work list): under DROP a packed batch drops exactly the
+//           elements the padded batch of the same sequences in the same order drops, and oneprot_attn_dropout_keep(N, H, max_len) sliced
+//           [seg, head, :n, :n] is its mask.  DROP = false (ESM: no probability dropout) never reads it; DROP = true is the BERT text tower.
 // Rows past cu_seqlens[N] (the tail) are written as zeros by k_varlen_tail_zero.
 // =========================================================================================================
-struct VarSeg { int start, n, blk; };
+struct VarSeg { int start, n, blk, seg; };
 __device__ __forceinline__ bool varlen_item(const int* __restrict__ cu, const int* __restrict__ work, int N, int T_pad, int H, int& head, VarSeg& sg) {
   const int item = blockIdx.x / H;
   head = blockIdx.x - item * H;
@@ -2537,44 +2539,45 @@ __device__ __forceinline__ bool varlen_item(const int* __restrict__ cu, const in
   sg.start = cu[seg];
   sg.n = cu[seg + 1] - sg.start;
   sg.blk = blk;
+  sg.seg = seg;
   return sg.start >= 0 && sg.n > 0 && sg.start + sg.n <= T_pad && blk >= 0 && blk * 128 < sg.n;
 }
 
-__device__ __forceinline__ AttnSlab packed_slab(const VarSeg& sg, int head, int T_pad) {
-  return AttnSlab{sg.n, sg.blk, head, (size_t)head * T_pad + sg.start, (size_t)sg.start, nullptr, sg.start, 0};
+__device__ __forceinline__ AttnSlab packed_slab(const VarSeg& sg, int head, int T_pad, int H) {
+  return AttnSlab{sg.n, sg.blk, head, (size_t)head * T_pad + sg.start, (size_t)sg.start, nullptr, sg.start, sg.seg * H + head};
 }
 
-template <int HD>
+template <int HD, bool DROP = false>
 __global__ void __launch_bounds__(256, 2) k_attn_varlen_fwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                          const int* __restrict__ cu, const int* __restrict__ work, bf16_t* __restrict__ ctx,
-                                                         float* __restrict__ lse_out, int N, int T_pad, int H) {
+                                                         float* __restrict__ lse_out, int N, int T_pad, int H, AttnDrop dr) {
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  attn_fwd_body<HD, false>(q, k, v, ctx, lse_out, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
+  attn_fwd_body<HD, DROP>(q, k, v, ctx, lse_out, H, packed_slab(sg, head, T_pad, H), dr);
 }
 
-template <int HD>
+template <int HD, bool DROP = false>
 __global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                             const int* __restrict__ cu, const int* __restrict__ work, const bf16_t* __restrict__ ctx,
                                                             const bf16_t* __restrict__ dctx, const float* __restrict__ lse, float* __restrict__ delta,
                                                             const float* __restrict__ cosT, const float* __restrict__ sinT, float q_scale,
-                                                            bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
+                                                            bf16_t* __restrict__ dqkv, int N, int T_pad, int H, AttnDrop dr) {
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  attn_bwd_dq_body<HD, false>(q, k, v, ctx, dctx, lse, delta, cosT, sinT, q_scale, dqkv, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
+  attn_bwd_dq_body<HD, DROP>(q, k, v, ctx, dctx, lse, delta, cosT, sinT, q_scale, dqkv, H, packed_slab(sg, head, T_pad, H), dr);
 }
 
-template <int HD>
+template <int HD, bool DROP = false>
 __global__ void __launch_bounds__(256, 2) k_attn_varlen_bwd_dkv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                              const int* __restrict__ cu, const int* __restrict__ work, const bf16_t* __restrict__ dctx,
                                                              const float* __restrict__ lse, const float* __restrict__ delta, const float* __restrict__ cosT,
-                                                             const float* __restrict__ sinT, bf16_t* __restrict__ dqkv, int N, int T_pad, int H) {
+                                                             const float* __restrict__ sinT, bf16_t* __restrict__ dqkv, int N, int T_pad, int H, AttnDrop dr) {
   int head;
   VarSeg sg;
   if (!varlen_item(cu, work, N, T_pad, H, head, sg)) return;
-  attn_bwd_dkv_body<HD, false>(q, k, v, dctx, lse, delta, cosT, sinT, dqkv, H, packed_slab(sg, head, T_pad), AttnDrop{0u, 0u, 0u, 1.0f});
+  attn_bwd_dkv_body<HD, DROP>(q, k, v, dctx, lse, delta, cosT, sinT, dqkv, H, packed_slab(sg, head, T_pad, H), dr);
 }
 
 // rows [cu[N], T_pad) of a bf16 [T_pad, width] tensor (width % 8 == 0) and, optionally, of the H rows of an fp32 [H, T_pad] tensor are set to zero
@@ -2598,42 +2601,75 @@ static bool varlen_args_ok(const void* cu, const void* work, int n_work, int N, 
   return cu && work && n_work > 0 && N > 0 && H > 0 && T_pad > 0 && (T_pad % 8) == 0 && (long)n_work * H < 0x7fffffffL;
 }
 
-extern "C" int oneprot_attn_varlen_fwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse,
-                                       int N, int T_pad, int H, int hd, void* stream) {
-  if (!q || !k || !v || !ctx || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H)) return OP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
+template <bool DROP>
+static int launch_varlen_fwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse, int N,
+                             int T_pad, int H, int hd, hipStream_t s, const AttnDrop& dr) {
+  if (hd != 16 && hd != 32 && hd != 64) return OP_EINVAL;
   hipLaunchKernelGGL(k_varlen_tail_zero, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, (bf16_t*)ctx, H * hd, lse, H);
   const dim3 grid((unsigned)(n_work * H));
   switch (hd) {
-#define VL_FWD(D) case D: hipLaunchKernelGGL(k_attn_varlen_fwd<D>, grid, dim3(256), fwd_lds<D>(), s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, \
-                                             cu_seqlens, work, (bf16_t*)ctx, lse, N, T_pad, H); break;
+#define VL_FWD(D) case D: hipLaunchKernelGGL((k_attn_varlen_fwd<D, DROP>), grid, dim3(256), fwd_lds<D>(), s, (const bf16_t*)q, (const bf16_t*)k,           \
+                                             (const bf16_t*)v, cu_seqlens, work, (bf16_t*)ctx, lse, N, T_pad, H, dr); break;
     VL_FWD(16) VL_FWD(32) VL_FWD(64)
 #undef VL_FWD
-    default: return OP_EINVAL;
   }
   return launch_status();
 }
 
+extern "C" int oneprot_attn_varlen_fwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx, float* lse,
+                                       int N, int T_pad, int H, int hd, void* stream) {
+  if (!q || !k || !v || !ctx || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H)) return OP_EINVAL;
+  return launch_varlen_fwd<false>(q, k, v, cu_seqlens, work, n_work, ctx, lse, N, T_pad, H, hd, (hipStream_t)stream, AttnDrop{0u, 0u, 0u, 1.0f});
+}
+
+// the same with probability dropout (hf modeling_bert.py BertSelfAttention, the text tower packed); the mask is that of oneprot_attn_fwd_dropout on the
+// padded batch of the same sequences
+extern "C" int oneprot_attn_varlen_fwd_dropout(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, void* ctx,
+                                               float* lse, int N, int T_pad, int H, int hd, float p, uint64_t seed, uint64_t stream_id, void* stream) {
+  AttnDrop dr;
+  if (!q || !k || !v || !ctx || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H) || attn_drop_make(p, seed, stream_id, dr) != OP_OK) return OP_EINVAL;
+  return launch_varlen_fwd<true>(q, k, v, cu_seqlens, work, n_work, ctx, lse, N, T_pad, H, hd, (hipStream_t)stream, dr);
+}
+
 extern "C" size_t oneprot_attn_varlen_bwd_workspace(int H, int T_pad) { return (size_t)H * T_pad * sizeof(float); }
+
+template <bool DROP>
+static int launch_varlen_bwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx, const void* dctx,
+                             const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv, void* workspace, int N, int T_pad,
+                             int H, int hd, hipStream_t s, const AttnDrop& dr) {
+  if (hd != 16 && hd != 32 && hd != 64) return OP_EINVAL;
+  float* delta = (float*)workspace;
+  hipLaunchKernelGGL(k_varlen_tail_zero, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, (bf16_t*)dqkv, 3 * H * hd, (float*)nullptr, H);
+  const dim3 grid((unsigned)(n_work * H));
+  switch (hd) {
+#define VL_BWD(D) case D: { const size_t lds = fwd_lds<D>();                                                                                      \
+      hipLaunchKernelGGL((k_attn_varlen_bwd_dq<D, DROP>), grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens,    \
+                         work, (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, rope_cos, rope_sin, q_scale, (bf16_t*)dqkv, N, T_pad, H, dr);       \
+      hipLaunchKernelGGL((k_attn_varlen_bwd_dkv<D, DROP>), grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens,   \
+                         work, (const bf16_t*)dctx, lse, (const float*)delta, rope_cos, rope_sin, (bf16_t*)dqkv, N, T_pad, H, dr); } break;
+    VL_BWD(16) VL_BWD(32) VL_BWD(64)
+#undef VL_BWD
+  }
+  return launch_status();
+}
 
 extern "C" int oneprot_attn_varlen_bwd(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
                                        const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
                                        void* workspace, int N, int T_pad, int H, int hd, void* stream) {
   if (!q || !k || !v || !ctx || !dctx || !lse || !dqkv || !workspace || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H)) return OP_EINVAL;
   if ((rope_cos == nullptr) != (rope_sin == nullptr)) return OP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  float* delta = (float*)workspace;
-  hipLaunchKernelGGL(k_varlen_tail_zero, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, (bf16_t*)dqkv, 3 * H * hd, (float*)nullptr, H);
-  const dim3 grid((unsigned)(n_work * H));
-  switch (hd) {
-#define VL_BWD(D) case D: { const size_t lds = fwd_lds<D>();                                                                                      \
-      hipLaunchKernelGGL(k_attn_varlen_bwd_dq<D>, grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens, work,      \
-                         (const bf16_t*)ctx, (const bf16_t*)dctx, lse, delta, rope_cos, rope_sin, q_scale, (bf16_t*)dqkv, N, T_pad, H);                 \
-      hipLaunchKernelGGL(k_attn_varlen_bwd_dkv<D>, grid, dim3(256), lds, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, cu_seqlens, work,     \
-                         (const bf16_t*)dctx, lse, (const float*)delta, rope_cos, rope_sin, (bf16_t*)dqkv, N, T_pad, H); } break;
-    VL_BWD(16) VL_BWD(32) VL_BWD(64)
-#undef VL_BWD
-    default: return OP_EINVAL;
-  }
-  return launch_status();
+  return launch_varlen_bwd<false>(q, k, v, cu_seqlens, work, n_work, ctx, dctx, lse, rope_cos, rope_sin, q_scale, dqkv, workspace, N, T_pad, H, hd,
+                                  (hipStream_t)stream, AttnDrop{0u, 0u, 0u, 1.0f});
+}
+
+extern "C" int oneprot_attn_varlen_bwd_dropout(const void* q, const void* k, const void* v, const int* cu_seqlens, const int* work, int n_work, const void* ctx,
+                                               const void* dctx, const float* lse, const float* rope_cos, const float* rope_sin, float q_scale, void* dqkv,
+                                               void* workspace, int N, int T_pad, int H, int hd, float p, uint64_t seed, uint64_t stream_id, void* stream) {
+  AttnDrop dr;
+  if (!q || !k || !v || !ctx || !dctx || !lse || !dqkv || !workspace || !varlen_args_ok(cu_seqlens, work, n_work, N, T_pad, H) ||
+      attn_drop_make(p, seed, stream_id, dr) != OP_OK)
+    return OP_EINVAL;
+  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return OP_EINVAL;
+  return launch_varlen_bwd<true>(q, k, v, cu_seqlens, work, n_work, ctx, dctx, lse, rope_cos, rope_sin, q_scale, dqkv, workspace, N, T_pad, H, hd,
+                                 (hipStream_t)stream, dr);
 }

@@ -637,16 +637,15 @@ extern "C" int oneprot_lnpool_packed_fwd(const float* x, const int64_t* ids, con
 // BERT embeddings: x = LayerNorm(word[id] + pos[l] + type[0])   (hf modeling_bert.py:53-108; eval mode, dropout off)
 // one wave per token, lane owns float4 columns (same scheme as LayerNorm)
 // --------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_bert_embed(const long long* __restrict__ ids, const float* __restrict__ word, const float* __restrict__ pos,
-                                                    const float* __restrict__ type0, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float* __restrict__ x_f32, bf16_t* __restrict__ x_bf16, int T, int L, int d, int vocab, float eps) {
+// one row by one wave: x[row] = LN(word[id] + pos[l] + type0)
+__device__ __forceinline__ void bert_embed_row(long long id, int l, size_t row, const float* __restrict__ word, const float* __restrict__ pos,
+                                               const float* __restrict__ type0, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                               float* __restrict__ x_f32, bf16_t* __restrict__ x_bf16, int d, int vocab, float eps) {
   const int lane = threadIdx.x & 63;
   const int nv4 = d >> 2;
   const float inv_d = 1.0f / (float)d;
-  for (int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6); row < T; row += gridDim.x * ROWS_PER_BLOCK) {
-    long long id = ids[row];
+  {
     if (id < 0 || id >= vocab) id = 0;
-    const int l = row % L;
     float4 v[MAXV];
     float s = 0.f;
 #pragma unroll
@@ -677,17 +676,76 @@ __global__ void __launch_bounds__(256) k_bert_embed(const long long* __restrict_
         float4 o;
         o.x = (v[i].x - mean) * rstd * g.x + be.x; o.y = (v[i].y - mean) * rstd * g.y + be.y;
         o.z = (v[i].z - mean) * rstd * g.z + be.z; o.w = (v[i].w - mean) * rstd * g.w + be.w;
-        if (x_f32) reinterpret_cast<float4*>(x_f32 + (size_t)row * d)[c] = o;
-        if (x_bf16) { u32x2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); reinterpret_cast<u32x2*>(x_bf16 + (size_t)row * d)[c] = pk; }
+        if (x_f32) reinterpret_cast<float4*>(x_f32 + row * d)[c] = o;
+        if (x_bf16) { u32x2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); reinterpret_cast<u32x2*>(x_bf16 + row * d)[c] = pk; }
       }
     }
   }
+}
+__global__ void __launch_bounds__(256) k_bert_embed(const long long* __restrict__ ids, const float* __restrict__ word, const float* __restrict__ pos,
+                                                    const float* __restrict__ type0, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float* __restrict__ x_f32, bf16_t* __restrict__ x_bf16, int T, int L, int d, int vocab, float eps) {
+  for (int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6); row < T; row += gridDim.x * ROWS_PER_BLOCK)
+    bert_embed_row(ids[row], row % L, (size_t)row, word, pos, type0, gamma, beta, x_f32, x_bf16, d, vocab, eps);
 }
 extern "C" int oneprot_bert_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type0, const float* gamma, const float* beta,
                                       float* x_f32, void* x_bf16, int B, int L, int d, int vocab, float eps, void* stream) {
   if (!ids || !word || !pos || !type0 || !gamma || !beta || (!x_f32 && !x_bf16) || B <= 0 || L <= 0 || (d & 3) || d > MAXV * 256) return OP_EINVAL;
   hipLaunchKernelGGL(k_bert_embed, dim3(ln_grid(B * L)), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, word, pos, type0, gamma, beta, x_f32,
                      (bf16_t*)x_bf16, B * L, L, d, vocab, eps);
+  return launch_status();
+}
+
+// Packed stream (ref text_encoder.py:54-62 on a batch without its padding): segment b = rows [cu[b], cu[b+1]), absolute positions restart at every
+// segment; work-group row N = the tail [cu[N], T_pad), whose rows take position 0 (finite rows: LN of word[pad] + pos[0] + type0).  Segments are
+// found as in k_embed_packed_fwd: grid (chunks of 32 tokens, N + 1).
+__global__ void __launch_bounds__(256) k_bert_embed_packed(const long long* __restrict__ ids, const int* __restrict__ cu, const float* __restrict__ word,
+                                                           const float* __restrict__ pos, const float* __restrict__ type0, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, float* __restrict__ x_f32, bf16_t* __restrict__ x_bf16, int N,
+                                                           int T_pad, int d, int vocab, int n_pos, float eps, int tok_per_block) {
+  const int b = blockIdx.y, chunk = blockIdx.x, wave = threadIdx.x >> 6;
+  const bool tail = b == N;
+  const int base = cu[b], L = (tail ? T_pad : cu[b + 1]) - base;
+  if (L <= 0 || base < 0 || base + L > T_pad) return;
+  for (int l0 = chunk * tok_per_block; l0 < L; l0 += gridDim.x * tok_per_block)      // (the tail may be longer than max_len)
+    for (int l = l0 + wave; l < min(L, l0 + tok_per_block); l += ROWS_PER_BLOCK) {
+      const size_t t = (size_t)base + l;
+      bert_embed_row(ids[t], tail ? 0 : min(l, n_pos - 1), t, word, pos, type0, gamma, beta, x_f32, x_bf16, d, vocab, eps);
+    }
+}
+// (a segment longer than n_pos is the caller's error -- the tower raises before it gets here; the kernel clamps the position, it never reads past the table)
+extern "C" int oneprot_bert_embed_packed_fwd(const int64_t* ids, const int* cu_seqlens, const float* word, const float* pos, const float* type0, const float* gamma,
+                                             const float* beta, float* x_f32, void* x_bf16, int N, int T_pad, int d, int vocab, int n_pos, float eps, void* stream) {
+  if (!ids || !cu_seqlens || !word || !pos || !type0 || !gamma || !beta || (!x_f32 && !x_bf16) || N <= 0 || T_pad <= 0 || n_pos <= 0 || vocab <= 0 || d <= 0 ||
+      (d & 3) || d > MAXV * 256)
+    return OP_EINVAL;
+  const int tpb = 32;
+  hipLaunchKernelGGL(k_bert_embed_packed, dim3((min(n_pos, T_pad) + tpb - 1) / tpb, N + 1), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, cu_seqlens,
+                     word, pos, type0, gamma, beta, x_f32, (bf16_t*)x_bf16, N, T_pad, d, vocab, n_pos, eps, tpb);
+  return launch_status();
+}
+
+// Position-table gradient of the packed embedding: dpos[l] = sum over the segments s with n_s > l of de[cu[s] + l], l < n_rows (hf modeling_bert.py:53-108,
+// position_embeddings).  One work-group per position row, a thread per float4 column, the segments in ascending order: fixed order, no atomics.  Rows
+// that no segment reaches are written as zeros; the tail rows of de are never read.
+__global__ void __launch_bounds__(256) k_segment_possum(const float* __restrict__ de, const int* __restrict__ cu, float* __restrict__ dpos, int N, int T_pad,
+                                                        int d) {
+  const int l = blockIdx.x, nv4 = d >> 2;
+  for (int c = threadIdx.x; c < nv4; c += 256) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int s = 0; s < N; ++s) {
+      const int base = cu[s], n = cu[s + 1] - base;
+      if (l < n && base >= 0 && base + n <= T_pad) {
+        const float4 e = reinterpret_cast<const float4*>(de + ((size_t)base + l) * d)[c];
+        acc.x += e.x; acc.y += e.y; acc.z += e.z; acc.w += e.w;
+      }
+    }
+    reinterpret_cast<float4*>(dpos + (size_t)l * d)[c] = acc;
+  }
+}
+extern "C" int oneprot_segment_possum_f32(const float* de, const int* cu_seqlens, float* dpos, int N, int T_pad, int n_rows, int d, void* stream) {
+  if (!de || !cu_seqlens || !dpos || N <= 0 || T_pad <= 0 || n_rows <= 0 || d <= 0 || (d & 3)) return OP_EINVAL;
+  hipLaunchKernelGGL(k_segment_possum, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, de, cu_seqlens, dpos, N, T_pad, d);
   return launch_status();
 }
 
@@ -745,6 +803,77 @@ __global__ void __launch_bounds__(256) k_pool_bwd(const float* __restrict__ dpoo
 extern "C" int oneprot_pool_bwd(const float* dpooled, const int64_t* ids, int pad_id, float* g, void* g_bf16, int B, int L, int d, int mode, void* stream) {
   if (!dpooled || !ids || !g || B <= 0 || L <= 0 || d <= 0 || (d & 3) || mode < 0 || mode > 1) return OP_EINVAL;
   hipLaunchKernelGGL(k_pool_bwd, dim3(B), dim3(256), 0, (hipStream_t)stream, dpooled, (const long long*)ids, pad_id, g, (bf16_t*)g_bf16, L, d, mode);
+  return launch_status();
+}
+
+// The same pooling per segment of a packed stream (x fp32 [T_pad, d], ids int64 [T_pad]; segment b = rows [cu[b], cu[b+1])): the text tower packed
+// (ref text_encoder.py:54-62 -> base_encoder.py:109-126).  Same rule as k_pool_fwd: mean over the tokens != pad_id of the segment, or its first row.
+__global__ void __launch_bounds__(256) k_pool_packed_fwd(const float* __restrict__ x, const long long* __restrict__ ids, const int* __restrict__ cu, int pad_id,
+                                                         float* __restrict__ pooled, int T_pad, int d, int mode) {
+  const int b = blockIdx.x;
+  const int base = cu[b], L = cu[b + 1] - base;
+  if (L <= 0 || base < 0 || base + L > T_pad) return;
+  __shared__ float s_n[4];
+  float cnt = 0.f;
+  for (int l = threadIdx.x; l < L; l += 256) cnt += (ids[(size_t)base + l] != pad_id);
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  const float inv_n = 1.0f / (s_n[0] + s_n[1] + s_n[2] + s_n[3]);
+  for (int j = threadIdx.x; j < d; j += 256) {
+    float s = 0.f;
+    if (mode == 1) s = x[(size_t)base * d + j];
+    else {
+      for (int l = 0; l < L; ++l)
+        if (ids[(size_t)base + l] != pad_id) s += x[((size_t)base + l) * d + j];
+      s *= inv_n;
+    }
+    pooled[(size_t)b * d + j] = s;
+  }
+}
+extern "C" int oneprot_pool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, float* pooled, int N, int T_pad, int d, int mode,
+                                       void* stream) {
+  if (!x || !ids || !cu_seqlens || !pooled || N <= 0 || T_pad <= 0 || d <= 0 || mode < 0 || mode > 1) return OP_EINVAL;
+  hipLaunchKernelGGL(k_pool_packed_fwd, dim3(N), dim3(256), 0, (hipStream_t)stream, x, (const long long*)ids, cu_seqlens, pad_id, pooled, T_pad, d, mode);
+  return launch_status();
+}
+
+// its backward: g[cu[b] + l] = dpooled[b] / n_b on the segment's non-pad tokens (mean) or dpooled[b] at l = 0 (CLS), 0 elsewhere; work-group N writes
+// the tail rows [cu[N], T_pad) as exact zeros.  fp32 + bf16 copy.
+__global__ void __launch_bounds__(256) k_pool_packed_bwd(const float* __restrict__ dpooled, const long long* __restrict__ ids, const int* __restrict__ cu,
+                                                         int pad_id, float* __restrict__ g, bf16_t* __restrict__ g16, int N, int T_pad, int d, int mode) {
+  const int b = blockIdx.x;
+  const bool tail = b == N;
+  const int base = cu[b], L = (tail ? T_pad : cu[b + 1]) - base;
+  if (L <= 0 || base < 0 || base + L > T_pad) return;
+  __shared__ float s_n[4];
+  float cnt = 0.f;
+  for (int l = threadIdx.x; l < L; l += 256) cnt += (ids[(size_t)base + l] != pad_id);
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  const float inv_n = 1.0f / (s_n[0] + s_n[1] + s_n[2] + s_n[3]);
+  const int nv4 = d >> 2;
+  for (int idx = threadIdx.x; idx < L * nv4; idx += 256) {
+    const int l = idx / nv4, c = idx - l * nv4;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!tail) {
+      float w;
+      if (mode == 1) w = (l == 0) ? 1.0f : 0.0f;
+      else w = (ids[(size_t)base + l] != pad_id) ? inv_n : 0.0f;
+      const float4 dp = reinterpret_cast<const float4*>(dpooled + (size_t)b * d)[c];
+      o = make_float4(dp.x * w, dp.y * w, dp.z * w, dp.w * w);
+    }
+    const size_t off = ((size_t)base + l) * d + 4 * c;
+    *reinterpret_cast<float4*>(g + off) = o;
+    if (g16) { u32x2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); *reinterpret_cast<u32x2*>(g16 + off) = pk; }
+  }
+}
+extern "C" int oneprot_pool_packed_bwd(const float* dpooled, const int64_t* ids, const int* cu_seqlens, int pad_id, float* g, void* g_bf16, int N, int T_pad, int d,
+                                       int mode, void* stream) {
+  if (!dpooled || !ids || !cu_seqlens || !g || N <= 0 || T_pad <= 0 || d <= 0 || (d & 3) || mode < 0 || mode > 1) return OP_EINVAL;
+  hipLaunchKernelGGL(k_pool_packed_bwd, dim3(N + 1), dim3(256), 0, (hipStream_t)stream, dpooled, (const long long*)ids, cu_seqlens, pad_id, g, (bf16_t*)g_bf16, N,
+                     T_pad, d, mode);
   return launch_status();
 }
 

@@ -8,7 +8,8 @@ checkpoint wire format (section 8f #3).
 * `SyntheticPairs` -- batches laid out as the reference's collate functions produce them (ref struct_token_dataset.py:87-90, text_dataset.py):
   `(sequence_ids[B,Ls] int64, modality_ids[B,Lm] int64, modality_name, raw)`, ids per BASELINE.md section 3 (cls 0 / eos 2 / pad 1, amino acids 4..23,
   foldseek letters 33..52; text: cls 2 / sep 3 / pad 0, body 5..vocab-1), seeded, optionally ragged with right padding; `packed=True` yields the
-  same sequences as `ragged=True` (same seed) with the ESM sides as oneprot_amd.packing.PackedTokens streams (a text side stays padded).
+  same sequences as `ragged=True` (same seed) with the ESM sides as oneprot_amd.packing.PackedTokens streams; a text side stays padded unless
+  `packed_text=True`, which packs it with BERT's pad id 0.
 * `save_checkpoint` / `load_weights_only` -- Lightning-style {"state_dict": {...}} files with the reference's key names
   (`network.<modality>.transformer....`), loaded exactly as ref src/train.py:73-82 does (optional 'model.' prefix, strict=True, weights only).
 """
@@ -47,10 +48,12 @@ class CombinedLoader:
 class SyntheticPairs:
     """Re-iterable synthetic (sequence, modality) batches for one modality."""
 
-    def __init__(self, modality, batch_size, seq_len, mod_len=None, n_batches=1, seed=1881, device="cpu", ragged=False, text_vocab=30522, packed=False):
+    def __init__(self, modality, batch_size, seq_len, mod_len=None, n_batches=1, seed=1881, device="cpu", ragged=False, text_vocab=30522, packed=False,
+                 packed_text=False):
         self.modality, self.B, self.Ls, self.Lm = modality, batch_size, seq_len, mod_len or seq_len
         self.n, self.seed, self.device, self.text_vocab = n_batches, seed, device, text_vocab
         self.ragged, self.packed = ragged or packed, packed
+        self.packed_text = bool(packed and packed_text)
 
     def __len__(self):
         return self.n
@@ -79,6 +82,8 @@ class SyntheticPairs:
                 seq = PackedTokens.from_padded(seq, pad_id=1)
                 if self.modality != "text":
                     mod = PackedTokens.from_padded(mod, pad_id=1)
+                elif self.packed_text:
+                    mod = PackedTokens.from_padded(mod, pad_id=0)
             yield seq.to(self.device), mod.to(self.device), self.modality, None
 
 

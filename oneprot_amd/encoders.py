@@ -351,23 +351,31 @@ class _EncodeFn(torch.autograd.Function):
 
     @staticmethod
     def _forward_packed(ctx, enc, tr, p, x, saved, need_tr_grad, need_any, n_extra, params):
-        """the pooling end of the forward on a packed stream: final LayerNorm + pooling per segment (pooled [N, d] in segment order)"""
+        """the pooling end of the forward on a packed stream: final LayerNorm + pooling per segment (pooled [N, d] in segment order); a post-LN tower
+        (BERT, final_layer_norm = False) pools the last layer's output directly"""
         N, T, d, dev = len(p), p.T_pad, tr.d, p.device
         cfg = tr.config
         pooled = torch.empty(N, d, device=dev)
         mode = enc.pooling.mode
-        mean, rstd, wrow = (torch.empty(T, device=dev) for _ in range(3)) if need_tr_grad else (None, None, None)
+        final_ln = getattr(tr, "final_layer_norm", True)
+        mean, rstd, wrow = (torch.empty(T, device=dev) for _ in range(3)) if (need_tr_grad and final_ln) else (None, None, None)
         hidden = attn = None
-        lnw, lnb = tr.view("encoder.emb_layer_norm_after.weight"), tr.view("encoder.emb_layer_norm_after.bias")
+        if final_ln:
+            lnw, lnb = tr.view("encoder.emb_layer_norm_after.weight"), tr.view("encoder.emb_layer_norm_after.bias")
         if mode == 2:
             pw = enc.pooling.layer.weight
             if pw.numel() != d:
                 raise RuntimeError(f"Attention1dPooling was built for hidden size {pw.numel()} but the encoder width is {d} "
                                    "(the reference hard-codes 1280: base_encoder.py:180)")
-            hidden = torch.empty(T, d, device=dev)
-            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, hidden, N, T, d, cfg.layer_norm_eps, 0)
+            if final_ln:
+                hidden = torch.empty(T, d, device=dev)
+                hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, hidden, N, T, d, cfg.layer_norm_eps, 0)
+            else:
+                hidden = x
             attn = torch.empty(T, device=dev)
             hip.call("oneprot_attnpool_packed_fwd", hidden, p.ids, p.cu_seqlens, cfg.pad_token_id, pw, enc.pooling.layer.bias, pooled, attn, N, p.max_len, d)
+        elif not final_ln:
+            hip.call("oneprot_pool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, pooled, N, T, d, mode)
         else:
             hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, None, N, T, d, cfg.layer_norm_eps, mode)
         learn = len(enc.norm) > 1 and enc.norm[1].learnable
@@ -435,6 +443,8 @@ class _EncodeFn(torch.autograd.Function):
             if not final_ln:        # BERT: pooling reads the last layer's output directly
                 if mode == 2:
                     g.copy_(dhidden.view(B * L, d))
+                elif packed:
+                    hip.call("oneprot_pool_packed_bwd", dpooled, ctx.ids.ids, ctx.ids.cu_seqlens, tr.config.pad_token_id, g, g16, len(ctx.ids), B * L, d, mode)
                 else:
                     hip.call("oneprot_pool_bwd", dpooled, ctx.ids, tr.config.pad_token_id, g, g16, B, L, d, mode)
             elif packed and mode != 2:      # dy[t] = dpooled[segment of t] * wrow[t]
@@ -601,9 +611,15 @@ class BaseEncoder(nn.Module):
         return ps
 
     def encode(self, input_ids):
-        if isinstance(input_ids, PackedTokens) and not isinstance(self.transformer, EsmTransformer):
-            raise NotImplementedError(f"{type(self).__name__}: packed input is built for the ESM towers only (packed BERT -- absolute positions, token "
-                                      "types, post-LN -- is not); pass padded [B, L] ids")
+        if isinstance(input_ids, PackedTokens):
+            tr = self.transformer
+            if not (isinstance(tr, EsmTransformer) or getattr(tr, "accepts_packed", False)):
+                raise NotImplementedError(f"{type(self).__name__}: packed input is built for the ESM towers and the BERT text tower; pass padded [B, L] ids")
+            # the one refusal of the text tower, before anything looks at the device: a stream packed for another tower (ESM's pad id is 1, BERT's 0)
+            if not isinstance(tr, EsmTransformer) and input_ids.pad_id != tr.config.pad_token_id:
+                raise NotImplementedError(f"{type(self).__name__}: this stream was packed with pad id {input_ids.pad_id}, the tower's pad_token_id is "
+                                          f"{tr.config.pad_token_id} (packed BERT takes streams packed with its own pad id, as the ESM towers do): re-pack with "
+                                          f"PackedTokens.from_padded(ids, pad_id={tr.config.pad_token_id})")
         extra = self._extra_params()
         head_params = [p for p in self.proj.parameters()]
         return _EncodeFn.apply(self, input_ids, self.transformer.flat, len(extra), *extra, *head_params)

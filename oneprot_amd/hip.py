@@ -112,6 +112,12 @@ _SIGS = {
     "oneprot_attn_varlen_fwd": (I, [P, P, P, P, P, I, P, P, I, I, I, I, P]),
     "oneprot_attn_varlen_bwd_workspace": (SZ, [I, I]),
     "oneprot_attn_varlen_bwd": (I, [P, P, P, P, P, I, P, P, P, P, P, F, P, P, I, I, I, I, P]),
+    "oneprot_attn_varlen_fwd_dropout": (I, [P, P, P, P, P, I, P, P, I, I, I, I, F, U64, U64, P]),
+    "oneprot_attn_varlen_bwd_dropout": (I, [P, P, P, P, P, I, P, P, P, P, P, F, P, P, I, I, I, I, F, U64, U64, P]),
+    "oneprot_bert_embed_packed_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "oneprot_segment_possum_f32": (I, [P, P, P, I, I, I, I, P]),
+    "oneprot_pool_packed_fwd": (I, [P, P, P, I, P, I, I, I, I, P]),
+    "oneprot_pool_packed_bwd": (I, [P, P, P, I, P, P, I, I, I, I, P]),
     "oneprot_lnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, P, P, P, I, I, I, F, I, P]),
     "oneprot_lnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
     "oneprot_attnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
@@ -137,6 +143,8 @@ _PTR_DTYPES = {
     "oneprot_esm_embed_packed_fwd": "lifffffff", "oneprot_esm_embed_packed_bwd": "lfffb", "oneprot_attn_varlen_fwd": "hhhiihf",
     "oneprot_attn_varlen_bwd": "hhhiihhfffhb", "oneprot_lnpool_packed_fwd": "flifffffff", "oneprot_lnpool_packed_bwd": "fiffffffhffb",
     "oneprot_attnpool_packed_fwd": "fliffff", "oneprot_attnpool_packed_bwd": "ffifffffb",
+    "oneprot_attn_varlen_fwd_dropout": "hhhiihf", "oneprot_attn_varlen_bwd_dropout": "hhhiihhfffhb", "oneprot_bert_embed_packed_fwd": "liffffffh",
+    "oneprot_segment_possum_f32": "fif", "oneprot_pool_packed_fwd": "flif", "oneprot_pool_packed_bwd": "flifh",
     "oneprot_sim_pair_dot": "fff", "oneprot_sim_rank": "fffii", "oneprot_sim_topk": "ffflb",
 }
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}

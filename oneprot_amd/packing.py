@@ -1,17 +1,21 @@
-"""Packed (variable-length) batches of ESM token ids: the flash-attention "varlen" layout.
+"""Packed (variable-length) batches of token ids (ESM towers and the BERT text tower): the flash-attention "varlen" layout.
 
-A packed batch is a token stream: the N sequences of a batch concatenated, each with its own <cls> ... <eos>, the tail filled with the pad id up
-to T_pad (a multiple of 256, which keeps the 8-phase GEMMs eligible).  `cu_seqlens` int32 [N + 1] marks where each sequence starts.  Every
-row-wise stage of an ESM tower (LayerNorm, the QKV / out-proj / FFN GEMMs and their epilogues, the LoRA branch) runs on the T_pad rows as if they
-were one sequence; embedding, rotary tables, attention and pooling follow the segments.  Against a padded [B, L] batch this
-saves the rows of padding, which in shuffled real data (ref struct_token_dataset.py:87-88, lengths up to 1 024) is a large share of every batch.
+A packed batch is a token stream: the N sequences of a batch concatenated, each with its own <cls> ... <eos> ([CLS] ... [SEP] for a caption), the
+tail filled with the pad id up to T_pad (a multiple of 256, which keeps the 8-phase GEMMs eligible).  `cu_seqlens` int32 [N + 1] marks where each
+sequence starts.  Every row-wise stage of a tower (LayerNorm, the QKV / out-proj / FFN GEMMs and their epilogues, the LoRA branch, BERT's hidden
+dropouts) runs on the T_pad rows as if they were one sequence; embedding, positions (rotary tables for ESM, absolute positions for BERT), attention
+and pooling follow the segments (DESIGN.md sections 3 and 6).  Against a padded [B, L] batch this saves the rows of padding, which in shuffled real
+data (ref struct_token_dataset.py:87-88, lengths up to 1 024; ref text_dataset.py:51, captions padded to the longest of the batch, up to 512) is a
+large share of every batch.
 
-`SequenceEncoder` / `StructTokenEncoder` / `OneProtLitModule` take a PackedTokens wherever they take padded ids and return [N, D] features in
-sequence order.
+`SequenceEncoder` / `StructTokenEncoder` / `TextEncoder` / `OneProtLitModule` take a PackedTokens wherever they take padded ids and return [N, D]
+features in sequence order.  The stream's pad id must be the tower's: 1 for ESM (the default here), 0 for BERT
+(`PackedTokens.from_padded(ids, pad_id=0)`); the text tower refuses a stream packed with another pad id.
 """
 import torch
 
 MAX_SEGMENT = 1026          # ESM-2's max_position_embeddings: the longest sequence (<cls> and <eos> included) the rotary tables are built for
+                            # (the BERT tower enforces its own, smaller max_position_embeddings -- 512 -- when it is handed a stream)
 PAD_MULTIPLE = 256
 
 

@@ -1,4 +1,4 @@
-"""Padded against packed ESM batches, in one process, on identical data (oneprot_amd.packing; DESIGN.md section 6, "Packed batches").
+"""Padded against packed batches (ESM towers, BERT text tower), in one process, on identical data (oneprot_amd.packing; DESIGN.md section 6, "Packed batches").
 
 cfg-2 shapes: ESM-2-150M x2 (sequence tower frozen, struct-token tower trainable), L = 512, 256 pairs per sub-step.  The padded and the packed
 form of the SAME batch (SyntheticPairs(ragged=True) and SyntheticPairs(packed=True), one seed) alternate sub-step by sub-step, so clock and
@@ -7,6 +7,9 @@ power drift fall on both alike; each side is timed between HIP events around its
   ragged   lengths uniform in [L/4, L] (what shuffled real data looks like; the reference pads each batch to its longest row)
   full     every row L tokens long: packing saves nothing, this prices its overhead
   anchor   ESM-2-650M attention1d tower (the cfg-5 anchor), forward only, ragged rows
+  text     cfg-4 shapes: ESM-2-150M (L = 512, frozen) <-> BERT-base text tower (T = 256, frozen, cls pooling + mlp head, HF's train-mode dropout on as in
+           the reference), both sides packed (SyntheticPairs(packed=True, packed_text=True)), ragged and full-length rows; --text-only runs just these
+           two and writes them alone (profiles/packed_ab_text.json)
 
 Per case: pairs/s and real tokens/s of both layouts, the measured speed-up, and the FLOP ratio padded / packed computed from the lengths (GEMM rows;
 attention, whose per-sequence cost goes with the square of the length).  PACKED_AB_PROFILE=1 runs only the ragged cfg-2 case, a few steps, for
@@ -14,6 +17,7 @@ attention, whose per-sequence cost goes with the square of the length).  PACKED_
 profiles/packed_ab_kernels.txt compares (the varlen attention kernels' time per FLOP against the padded ones').
 
 usage: python tools/packed_ab.py [--steps 6] [--out profiles/packed_ab.json]
+       python tools/packed_ab.py --text-only [--out profiles/packed_ab_text.json]
 """
 import argparse
 import functools
@@ -92,6 +96,48 @@ def case_substep(module, B, L, ragged, steps, seed=1881):
                 steps_s=dict(padded=[round(x, 5) for x in ta], packed=[round(x, 5) for x in tb]))
 
 
+def build_text_pair(dev):
+    import torch
+    from src.models.components.sequence_encoder import SequenceEncoder
+    from src.models.components.text_encoder import TextEncoder
+    from src.models.oneprot_module import OneProtLitModule
+    from oneprot_amd.optim import FusedAdam
+    torch.manual_seed(1881)
+    seq = SequenceEncoder("facebook/esm2_t30_150M_UR50D", output_dim=1024, pooling_type="mean", proj_type="mlp", use_lora=False, frozen=True)
+    txt = TextEncoder("microsoft/BiomedNLP-BiomedBERT-base-uncased-abstract-fulltext", output_dim=1024, pooling_type="cls", proj_type="mlp",
+                      use_logit_scale=True, learnable_logit_scale=False, frozen=True, use_lora=False)
+    m = OneProtLitModule(components={"sequence": seq, "text": txt}, optimizer=functools.partial(FusedAdam, lr=1e-3, weight_decay=0.0), loss_fn="CLIP",
+                         use_l1_regularization=True, local_loss=True, gather_with_grad=True).to(dev)
+    m.train()
+    return m
+
+
+def case_text(module, B, L, T, ragged, steps, seed=1881):
+    """one seq <-> text sub-step, padded against both sides packed"""
+    import torch
+    from oneprot_amd.data import SyntheticPairs
+    from oneprot_amd.packing import PackedTokens
+    rag = next(iter(SyntheticPairs("text", B, L, mod_len=T, seed=seed, ragged=ragged)))
+    if ragged:
+        pk = next(iter(SyntheticPairs("text", B, L, mod_len=T, seed=seed, packed=True, packed_text=True)))
+    else:               # full-length rows in packed form
+        pk = (PackedTokens.from_padded(rag[0], pad_id=1), PackedTokens.from_padded(rag[1], pad_id=0), "text", None)
+    dev = torch.device("cuda")
+    b_pad = {"text": (rag[0].to(dev), rag[1].to(dev), "text", None)}
+    b_pk = {"text": (pk[0].to(dev), pk[1].to(dev), "text", None)}
+    t_pad, t_pk, ta, tb = timed_alternating(lambda: module.training_step(b_pad, 0), lambda: module.training_step(b_pk, 0), steps)
+    lens_s, lens_t = [int(n) for n in (rag[0] != 1).sum(1)], [int(n) for n in (rag[1] != 0).sum(1)]
+    trs, trt = module.network["sequence"].transformer, module.network["text"].transformer
+    real = sum(lens_s) + sum(lens_t)
+    spread = lambda v: round(max(v) - min(v), 5)
+    return dict(pairs=B, L=L, T=T, real_tokens=real, padded_tokens=B * (L + T), packed_T_pad=[pk[0].T_pad, pk[1].T_pad],
+                padded=dict(s=round(t_pad, 5), pairs_per_s=round(B / t_pad, 1), real_tokens_per_s=round(real / t_pad), spread_s=spread(ta)),
+                packed=dict(s=round(t_pk, 5), pairs_per_s=round(B / t_pk, 1), real_tokens_per_s=round(real / t_pk), spread_s=spread(tb)),
+                speedup=round(t_pad / t_pk, 3),
+                flop_ratio_padded_over_packed=dict(sequence=flops_ratio(lens_s, L, trs.d, trs.f, trs.n_layers), text=flops_ratio(lens_t, T, trt.d, trt.f, trt.n_layers)),
+                steps_s=dict(padded=[round(x, 5) for x in ta], packed=[round(x, 5) for x in tb]))
+
+
 def case_anchor(B, L, steps):
     import torch
     from oneprot_amd.data import SyntheticPairs
@@ -120,6 +166,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--seq-len", type=int, default=512)
     ap.add_argument("--anchor-batch", type=int, default=64)
+    ap.add_argument("--text-len", type=int, default=256)
+    ap.add_argument("--text-only", action="store_true", help="only the cfg-4 text cases (both sides packed)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     os.environ.setdefault("RANK", "0")
@@ -130,8 +178,24 @@ def main():
     import torch
     dev = torch.device("cuda")
     t0 = time.time()
-    module = build_pair(dev)
     out = dict(tool="tools/packed_ab.py", device=torch.cuda.get_device_name(0), steps=args.steps)
+
+    def text_cases():
+        module = build_text_pair(dev)
+        out["ragged_cfg4_text"] = case_text(module, args.batch, args.seq_len, args.text_len, True, args.steps)
+        out["full_cfg4_text"] = case_text(module, args.batch, args.seq_len, args.text_len, False, args.steps)
+        del module
+        torch.cuda.empty_cache()
+
+    if args.text_only:
+        text_cases()
+        out["wall_s"] = round(time.time() - t0, 1)
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
+    module = build_pair(dev)
     if os.environ.get("PACKED_AB_PROFILE") == "1":
         out["ragged_cfg2"] = case_substep(module, args.batch, args.seq_len, True, min(args.steps, 3))
     else:
@@ -140,6 +204,7 @@ def main():
         del module
         torch.cuda.empty_cache()
         out["anchor_650m_attention1d_fwd"] = case_anchor(args.anchor_batch, args.seq_len, args.steps)
+        text_cases()
     out["wall_s"] = round(time.time() - t0, 1)
     line = json.dumps(out)
     print(line)
