@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .esm import EsmTransformer, resolve_config, ModelConfig
+from .esm import EsmTransformer, resolve_config, ModelConfig, recompute_plan
 from .packing import PackedTokens
 
 
@@ -609,6 +609,18 @@ class BaseEncoder(nn.Module):
         if getattr(self.transformer, "_lora", None):
             ps += [self.transformer.lora_A, self.transformer.lora_B]
         return ps
+
+    def set_activation_recompute(self, k):
+        """Activation recomputation of this encoder's ESM tower by segments of k layers (0: off; None: back to ONEPROT_RECOMPUTE_LAYERS); see
+        EsmTransformer.recompute_layers.  Returns self."""
+        tr = getattr(self, "transformer", None)
+        if not isinstance(tr, EsmTransformer):
+            raise NotImplementedError(f"{type(self).__name__}: activation recomputation is built for the ESM towers (SequenceEncoder, StructTokenEncoder); the BERT "
+                                      "text tower keeps every layer's activations, and the opaque graph encoder of StructEncoder runs under torch autograd as it is")
+        if k is not None:
+            recompute_plan(tr.n_layers, k)      # validates k
+        tr.recompute_layers = k
+        return self
 
     def encode(self, input_ids):
         if isinstance(input_ids, PackedTokens):

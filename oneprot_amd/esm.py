@@ -558,6 +558,23 @@ def _layout(tr, ids):
     return _PackedLayout(tr, ids) if isinstance(ids, PackedTokens) else _PaddedLayout(tr, ids)
 
 
+def _check_recompute_k(k):
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"recompute_layers must be a non-negative int (0 = off), got {k!r}")
+    return k
+
+
+def recompute_plan(n_layers, k):
+    """Layer segments [0,k), [k,2k), ... of a tower of n_layers (the last one may be short; k >= n_layers: one segment) as a list of (lo, hi), or None
+    when k = 0 (recomputation off).  The forward keeps the activations of the top segment only and a boundary record per lower segment."""
+    _check_recompute_k(k)
+    if isinstance(n_layers, bool) or not isinstance(n_layers, int) or n_layers < 1:
+        raise ValueError(f"n_layers must be a positive int, got {n_layers!r}")
+    if k == 0:
+        return None
+    return [(lo, min(lo + k, n_layers)) for lo in range(0, n_layers, k)]
+
+
 class EsmTransformer(ArenaModule):
     """EsmModel replacement.  `add_pooling_layer` only controls whether the (unused) HF pooler parameters exist,
     as in the reference (SequenceEncoder: False, StructTokenEncoder: True)."""
@@ -750,45 +767,98 @@ class EsmTransformer(ArenaModule):
         return self._rope_cache[key]
 
     # ----------------------------------------------------------------------------------------- forward / backward
+    # Activation recomputation by layer segments (DESIGN.md sections 3 and 6): None = read ONEPROT_RECOMPUTE_LAYERS at call time, else 0 (off).  An int k > 0
+    # keeps, of a training forward, only the top segment's activations and one boundary record per lower segment of k layers; the backward re-runs each
+    # lower segment from its record with the forward's own launches before it walks it.  Not part of the state dict.
+    recompute_layers = None
+
+    def _recompute_k(self):
+        k = self.recompute_layers
+        if k is None:
+            raw = os.environ.get("ONEPROT_RECOMPUTE_LAYERS", "").strip()
+            try:
+                k = int(raw) if raw else 0
+            except ValueError:
+                raise ValueError(f"ONEPROT_RECOMPUTE_LAYERS must be a non-negative integer, got {raw!r}") from None
+        return _check_recompute_k(k)
+
     def run_layers(self, ids, save):
         """Embedding + n layers on padded ids [B, L] or a PackedTokens stream (B = 1, L = T_pad for every row-wise stage).
         Returns (x_final fp32 [T,d], saved-dict or None)."""
         if not ids.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
         self._refresh_bf16()
-        cfg = self.config
         lay = _layout(self, ids)
         B, L, T = lay.B, lay.L, lay.T
-        d, f, H, hd, dp = self.d, self.f, self.H, self.hdp, self.dp        # hd: kernel (padded) head dim
-        q_scale = self.hd ** -0.5
-        dev = ids.device
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-        x = f32(T, d)
+        d, f, dp, n = self.d, self.f, self.dp, self.n_layers
+        x = torch.empty(T, d, dtype=torch.float32, device=ids.device)
         lay.embed(self, x)
-        cos, sin = lay.cos, lay.sin
-        saved = dict(layout=lay, layers=[], B=B, L=L) if save else None
-        h = b16(T, d)
-        q, k, v = b16(B, H, L, hd), b16(B, H, L, hd), b16(B, H, L, hd)
-        ctx_ = b16(T, dp)
-        u = b16(T, f)
-        eps = cfg.layer_norm_eps
+        # segments of a recomputing forward: only where activations are kept to begin with (a training forward that needs the tower's gradient) and only
+        # when there is a segment below the top one
+        plan = recompute_plan(n, self._recompute_k()) if (save and self.training) else None
+        if plan is not None and len(plan) < 2:
+            plan = None
         fused_ln = self._fused_ln_ok() and T % 128 == 0
         # FFN-2 + residual AND the next layer's first LayerNorm in one launch of the 8-phase GEMM (row statistics completed across the work-groups of a row
         # panel: oneprot_gemm_bf16_nt_resid_ln8); ONEPROT_FFN2_LN=0 keeps the pair (A/B runs)
         ln8_mode = os.environ.get("ONEPROT_FFN2_LN", "1")    # "0": never; "force": whenever the shape is served (tests: small batches against the oracle); else when it pays
+        if plan is not None and getattr(self, "_grad_overlap", None) is not None:
+            # the recompute pass runs inside the backward, beside the all-reduce channels of GradOverlap: kernels whose work-groups wait for each other are
+            # not co-resident with anything, so BOTH passes of such an application take the wait-free pair (bit identity needs the same forms twice)
+            ln8_mode = "0"
         ln8_min = 0 if ln8_mode == "0" else (1 if ln8_mode == "force" else 2)
         ffn2_ln = ln8_min > 0 and not self._padded and hip.query("oneprot_gemm_resid_ln8_eligible", T, d, f) >= ln8_min
         outproj_ln8 = not fused_ln and ln8_min > 0 and not self._padded and hip.query("oneprot_gemm_resid_ln8_eligible", T, d, dp) >= ln8_min
-        sched_ws = hip.sched_workspace(T) if (ffn2_ln or outproj_ln8 or hip.dynamic_tiles_wanted()) else None      # (pointer, bytes): partial row statistics + work queues
-        pre = None                                          # (h1, stats [2,T] or None) of this layer, already written by the previous layer's FFN-2 launch
-        lora_two = self._lora_two_branch()
-        if lora_two:      # every call draws its own dropout masks; the backward regenerates them from (seed, call, layer)
-            lora_call = self._lora_calls
+        # decided once per application: a recompute pass reads the forms (and the LoRA call id) back from `saved`, never from the environment
+        run = dict(layout=lay, forms=dict(fused_ln=fused_ln, ffn2_ln=ffn2_ln, outproj_ln8=outproj_ln8), lora_call=None, bufs=None)
+        saved = dict(layout=lay, layers=[None] * n, B=B, L=L, forms=run["forms"]) if save else None
+        if self._lora_two_branch():      # every call draws its own dropout masks; the backward regenerates them from (seed, call, layer)
+            run["lora_call"] = self._lora_calls
             self._lora_calls += 1
             if save:
-                saved["lora_call"] = lora_call
-        for i in range(self.n_layers):
+                saved["lora_call"] = run["lora_call"]
+        if plan is None:
+            x, _ = self._run_range(run, x, None, 0, n, save, saved["layers"] if save else None)
+        else:
+            bounds = saved["bounds"] = {}
+            pre = None
+            for lo, hi in plan[:-1]:      # the frozen tower's shared buffers; the layer under a boundary writes the boundary's x_in (and h1 | stats) into buffers of their own
+                bounds[lo] = dict(x_in=x, h1=pre[0] if pre is not None else None, stats=pre[1] if pre is not None else None)
+                x, pre = self._run_range(run, x, pre, lo, hi, False, None, boundary=True)
+            saved["plan"] = plan
+            lo, hi = plan[-1]
+            x, _ = self._run_range(run, x, pre, lo, hi, True, saved["layers"])
+        if save:
+            saved["x_final"] = x
+        return x, saved
+
+    def _run_range(self, run, x, pre, lo, hi, save, layers, boundary=False):
+        """Layers lo..hi-1 on the residual stream x fp32 [T,d]: THE layer body -- the plain forward, the first forward of a recomputing tower and its
+        recompute pass all come through here.  pre: (h1, stats [2,T] or None) of layer lo when the launch below it already wrote them, else None.
+        save: every layer keeps its record in layers[i] and writes x_mid / x_out out of place; otherwise the layers share one set of buffers and update
+        the stream in place.  boundary (not saving): a segment of a recomputing forward -- x and pre belong to a boundary record, so layer lo leaves them
+        alone (its x_mid goes to a work buffer), layer hi-1 writes x_out (and the next layer's h1 | stats) into fresh buffers, which become the next
+        record, and FFN-1 runs in the two-output form the recompute pass will take (see below).
+        Returns (x_out of layer hi-1, pre of layer hi)."""
+        cfg, lay, forms, lora_call = self.config, run["layout"], run["forms"], run["lora_call"]
+        B, L, T = lay.B, lay.L, lay.T
+        d, f, H, hd, dp = self.d, self.f, self.H, self.hdp, self.dp        # hd: kernel (padded) head dim
+        q_scale = self.hd ** -0.5
+        dev = x.device
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
+        cos, sin = lay.cos, lay.sin
+        eps = cfg.layer_norm_eps
+        fused_ln, ffn2_ln, outproj_ln8 = forms["fused_ln"], forms["ffn2_ln"], forms["outproj_ln8"]
+        # (pointer, bytes): partial row statistics + work queues; asked for per pass (another tower may have grown the workspace since the forward)
+        sched_ws = hip.sched_workspace(T) if (ffn2_ln or outproj_ln8 or hip.dynamic_tiles_wanted()) else None
+        lora_two = lora_call is not None
+        if not save:
+            if run["bufs"] is None:
+                run["bufs"] = dict(h=b16(T, d), q=b16(B, H, L, hd), k=b16(B, H, L, hd), v=b16(B, H, L, hd), ctx=b16(T, dp), u=b16(T, f))
+            bufs = run["bufs"]
+            h, q, k, v, ctx_, u = bufs["h"], bufs["q"], bufs["k"], bufs["v"], bufs["ctx"], bufs["u"]
+        for i in range(lo, hi):
             p = f"encoder.layer.{i}."
             if save:
                 stats1 = pre[1] if pre is not None else f32(2, T)      # mean | rstd of the first LayerNorm
@@ -798,8 +868,16 @@ class EsmTransformer(ArenaModule):
                 h1, q, k, v, ctx_, h2, u, z = st["h1"], st["q"], st["k"], st["v"], st["ctx"], st["h2"], st["u"], st["z"]
                 m1, r1, m2, r2, lse = st["mean1"], st["rstd1"], st["mean2"], st["rstd2"], st["lse"]
             else:
-                h1 = h2 = h
+                h1 = pre[0] if pre is not None else h
+                h2 = h
                 z = m1 = r1 = m2 = r2 = lse = None
+                if boundary:
+                    # FFN-1 without a second output is another kernel (forward-only GELU: a polynomial of its own, csrc/gemm_epi.h); the recompute pass will run
+                    # the two-output form, and the residual stream above this segment must be the one IT produces, bit for bit -- so the first forward runs
+                    # that form too, its one-byte codes going to a scratch buffer.  Every other launch only leaves optional stores out.
+                    if "z" not in bufs:
+                        bufs["z"] = torch.empty(T, f, dtype=torch.uint8, device=dev)
+                    z = bufs["z"]
             if pre is None:
                 hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "attention.LayerNorm.weight"), self.view(p + "attention.LayerNorm.bias"), h1, None,
                          m1, r1, T, d, eps)
@@ -814,7 +892,14 @@ class EsmTransformer(ArenaModule):
             else:
                 hip.call("oneprot_gemm_bf16_nt", h1, w_qkv, T, 3 * dp, d, d, d, hip.EPI_QKV_ROPE, b_qkv, q, k, v, None, cos, sin, q_scale * hip.LOG2E, L, H, hd)
             lay.attn_fwd(q, k, v, ctx_, lse, H, hd)
-            x_mid = f32(T, d) if save else x
+            if save:
+                x_mid = f32(T, d)
+            elif boundary and i == lo:      # x is a boundary record's x_in: the stream moves to a work buffer here and is updated in place from then on
+                if "xw" not in bufs:
+                    bufs["xw"] = f32(T, d)
+                x_mid = bufs["xw"]
+            else:
+                x_mid = x
             if fused_ln:
                 # out-projection + bias + residual AND the FFN's pre-LayerNorm in one full-row kernel: x_mid is not read back by a LayerNorm launch
                 # (measured on cfg-2: 0.28-0.29 ms against 0.31-0.32 ms for the pair; the FFN-2 / next-layer pair goes through the 8-phase GEMM with the
@@ -834,13 +919,14 @@ class EsmTransformer(ArenaModule):
                 hip.call("oneprot_layernorm_fwd", x_mid, 0, self.view(p + "LayerNorm.weight"), self.view(p + "LayerNorm.bias"), h2, None, m2, r2, T, d, eps)
             hip.call("oneprot_gemm_bf16_nt", h2, self._w16(p + "intermediate.dense.weight"), T, f, d, d, d, hip.EPI_BIAS_GELU,
                      self.view(p + "intermediate.dense.bias"), u, z, None, None, None, None, 1.0, 0, 0, 0)
-            if z is not None and _GELU_CODE_DROP_BITS:      # experiment hook (tests: what the one-byte gelu' codes cost the gradient): keep only the top 8 - n bits
+            if save and _GELU_CODE_DROP_BITS:      # experiment hook (tests: what the one-byte gelu' codes cost the gradient): keep only the top 8 - n bits
                 nb = _GELU_CODE_DROP_BITS
                 z.add_(1 << (nb - 1)).bitwise_and_(0xFF & ~((1 << nb) - 1))
-            x_out = f32(T, d) if save else x_mid
+            fresh = save or (boundary and i == hi - 1)      # this layer's outputs outlive the shared buffers
+            x_out = f32(T, d) if fresh else x_mid
             if ffn2_ln and i + 1 < self.n_layers:
                 pn = f"encoder.layer.{i + 1}.attention.LayerNorm."
-                pre = (b16(T, d), f32(2, T)) if save else (h, None)
+                pre = (b16(T, d), f32(2, T)) if fresh else (h, None)
                 hip.call("oneprot_gemm_bf16_nt_resid_ln8", u, self._w16(p + "output.dense.weight"), T, d, f, f, f, self.view(p + "output.dense.bias"), x_mid, x_out,
                          self.view(pn + "weight"), self.view(pn + "bias"), eps, pre[0], pre[1], *sched_ws)
             else:
@@ -849,11 +935,16 @@ class EsmTransformer(ArenaModule):
                          self.view(p + "output.dense.bias"), x_out, None, None, x_mid, None, None, 1.0, 0, 0, 0)
             if save:
                 st["x_mid"] = x_mid
-                saved["layers"].append(st)
+                layers[i] = st
             x = x_out
-        if save:
-            saved["x_final"] = x
-        return x, saved
+        return x, pre
+
+    def _recompute_segment(self, saved, lo, hi):
+        """the activations of layers lo..hi-1 again, from the segment's boundary record, by the forward's own launches in the saving form; nothing a
+        forward call advances moves (the LoRA call id and the kernel forms come from `saved`, the bf16 operands are the step's)"""
+        b = saved["bounds"][lo]
+        run = dict(layout=saved["layout"], forms=saved["forms"], lora_call=saved.get("lora_call"), bufs=None)
+        self._run_range(run, b["x_in"], (b["h1"], b["stats"]) if b["h1"] is not None else None, lo, hi, True, saved["layers"])
 
     GRAD_CHUNK_LAYERS = 6      # arena-gradient ranges are handed to `on_ready` every this many layers (overlapped all-reduce)
 
@@ -884,7 +975,11 @@ class EsmTransformer(ArenaModule):
         if self._padded:      # weight gradients come out in the padded-head layout and are gathered back into the arena gradient
             rowmap, colmap = self._head_pad_maps()
             gw_qkv, gb_qkv, gw_o = torch.empty(3 * dp, d, device=dev), torch.empty(3 * dp, device=dev), torch.empty(d, dp, device=dev)
+        bounds = saved.get("bounds")
+        seg_of_top = {hi - 1: (lo, hi) for lo, hi in saved["plan"][:-1]} if bounds is not None else {}
         for i in reversed(range(self.n_layers)):
+            if i in seg_of_top:      # entering a segment the forward did not keep: re-run it from its boundary record first
+                self._recompute_segment(saved, *seg_of_top[i])
             st = saved["layers"][i]
             p = f"encoder.layer.{i}."
             # ---- FFN2: x_out = x_mid + u W2^T + b2        (weight grad + bias grad in one TN launch)
@@ -919,7 +1014,9 @@ class EsmTransformer(ArenaModule):
             # ---- LN1 (input x_in)
             hip.call("oneprot_layernorm_bwd", dh, 0, None, 0, st["x_in"], 0, self.view(p + "attention.LayerNorm.weight"), st["mean1"], st["rstd1"], g, g, g16,
                      gv(p + "attention.LayerNorm.weight"), gv(p + "attention.LayerNorm.bias"), ws_ln, T, d, 0)
-            saved["layers"][i] = None      # release this layer's activations
+            saved["layers"][i] = st = None      # release this layer's activations
+            if bounds is not None:
+                bounds.pop(i, None)      # ... and, under its bottom layer, the segment's boundary record
             if on_ready is not None and i > 0 and i % self.GRAD_CHUNK_LAYERS == 0:
                 lo = self._spec[f"encoder.layer.{i}.attention.self.query.weight"][0]
                 on_ready(lo, ready_hi)
