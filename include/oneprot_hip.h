@@ -353,6 +353,36 @@ size_t oneprot_sim_topk_workspace(int nq, int N, int k);
 int oneprot_sim_topk(const float* Q, const float* Db, int nq, int N, int D, int k, float* scores, int64_t* indices, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---------------- MSA Transformer tower (ref msa_encoder.py:36: `self.transformer(tokens, repr_layers=[12])`, fair-esm's MSATransformer) ----------
+ * Forward only, eval mode (the reference freezes the tower, msa_encoder.py:30-32).  fair-esm is not part of this tree: the call sites below are named by
+ * their published functions, and parity with a fair-esm run is UNPINNED (the tests compare against tests/msa_ref.py, an fp64 restatement).
+ * Tokens int64 [B, R, L], numbered t = (b * R + r) * L + l, T = B * R * L.  qkv: bf16 [T, 3 * H * 64] = q | k | v of one oneprot_gemm_bf16_nt
+ * (ONEPROT_EPI_BF16 + bias) on the stacked projection weights, head h in columns h * 64 .. h * 64 + 63 of each third.  key_bias: fp32 [T] from
+ * oneprot_key_padding_bias (0 = token, anything else = padding).  ctx: bf16 [T, H * 64].  hd must be 64 (-1 otherwise).  A masked key is excluded
+ * (probability 0) instead of biased by -10000: the two differ only where every key of a query is masked -- padded positions -- which hold 0 here. */
+#define ONEPROT_MSA_MAX_LEN 1024      /* longest row L of the tied row attention                       */
+#define ONEPROT_MSA_MAX_ROWS 128      /* deepest MSA R of oneprot_msa_col_attn (R = 1: two GEMMs, host) */
+/* x fp32 [T, d] = LayerNorm(tok_table[id] + pos_table[pos] + row_table[r]) * (id != pad_id), pos = (non-pad tokens of the row up to and including l) +
+   pad_id, pad_id at padding (fair-esm MSATransformer.forward: embed_tokens + LearnedPositionalEmbedding + msa_position_embedding, emb_layer_norm_before,
+   `x * (1 - padding_mask)`).  pos_table [n_pos, d] with n_pos >= L + pad_id + 1; row_table [n_rows, d] with n_rows >= R; d <= 2048. */
+int oneprot_msa_embed_fwd(const int64_t* tokens, const float* tok_table, const float* pos_table, const float* row_table, const float* gamma,
+                          const float* beta, float* x, int B, int R, int L, int d, int vocab, int n_pos, int n_rows, int pad_id, float eps, void* stream);
+/* Tied row attention scores (fair-esm RowSelfAttention.compute_attention_weights): S fp32 [B, H, L, L],
+   S[b,h,i,j] = scale * sum_{r,c} q[b,r,i,h,c] k[b,r,j,h,c] with q taken as 0 at padded (r, i); scale = hd^-1/2 / sqrt(R).  fp32 accumulation over r = 0 .. R-1
+   in that order inside one work-group: no split along K, no atomics, independent of the rest of the batch.  L <= ONEPROT_MSA_MAX_LEN. */
+int oneprot_msa_row_scores(const void* qkv, const float* key_bias, float* S, int B, int R, int L, int H, int hd, float scale, void* stream);
+/* softmax over j of S with the keys where ROW 0 is padded masked, P rounded to bf16, ctx[b,r,i,h,:] = sum_j P[b,h,i,j] v[b,r,j,h,:] with fp32 accumulation
+   (fair-esm RowSelfAttention.compute_attention_update; S is read, not re-derived).  Three launches: the probabilities bf16 [B, H, L, Lp] and V transposed
+   bf16 [B, H, R, 64, Lp] (Lp = L rounded up to 32) are formed in `workspace` (16-byte aligned, at least oneprot_msa_row_context_workspace(B, R, L, H)
+   bytes, -1 otherwise; the query returns 0 for invalid arguments), then ctx^T = V^T P^T on MFMA tiles. */
+size_t oneprot_msa_row_context_workspace(int B, int R, int L, int H);
+int oneprot_msa_row_context(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B, int R, int L,
+                            int H, int hd, void* stream);
+/* Column attention for 2 <= R <= ONEPROT_MSA_MAX_ROWS (fair-esm ColumnSelfAttention.compute_attention_update): for each (b, l, h) softmax_j(scale * q_i . k_j)
+   over the rows j whose token (j, l) is not padding, ctx = P v; scale = hd^-1/2; a query whose keys are all masked gets 0.  A larger R returns -1; R = 1 is
+   out_proj(v_proj(x)) on the host, as published. */
+int oneprot_msa_col_attn(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ RULES = [
     (r"^void k_attn_bwd_fused64<\(int\)32>", 0),   # 8-wave fused backward (two key blocks per wave): 254 of 256 registers, see the kernel's comments before adding a live value
     (r"^void k_layernorm_(fwd|bwd)", 0),
     (r"^void k_sim_", 0),                       # retrieval: similarity tile + rank count / top-k selection / diagonal
+    (r"^(void )?k_msa_", 0),                           # MSA tower: embedding, tied row scores / context, column attention
 ]
 
 

@@ -9,7 +9,8 @@ checkpoint wire format (section 8f #3).
   `(sequence_ids[B,Ls] int64, modality_ids[B,Lm] int64, modality_name, raw)`, ids per BASELINE.md section 3 (cls 0 / eos 2 / pad 1, amino acids 4..23,
   foldseek letters 33..52; text: cls 2 / sep 3 / pad 0, body 5..vocab-1), seeded, optionally ragged with right padding; `packed=True` yields the
   same sequences as `ragged=True` (same seed) with the ESM sides as oneprot_amd.packing.PackedTokens streams; a text side stays padded unless
-  `packed_text=True`, which packs it with BERT's pad id 0.
+  `packed_text=True`, which packs it with BERT's pad id 0.  Modality "msa" (ref msa_dataset.py's batches): tokens [B, msa_depth, Lm] over the 33-symbol
+  alphabet, cls 0 in column 0, pad 1; ragged MSAs are shorter AND shallower (trailing rows fully padded); the MSA side is never packed.
 * `save_checkpoint` / `load_weights_only` -- Lightning-style {"state_dict": {...}} files with the reference's key names
   (`network.<modality>.transformer....`), loaded exactly as ref src/train.py:73-82 does (optional 'model.' prefix, strict=True, weights only).
 """
@@ -49,11 +50,12 @@ class SyntheticPairs:
     """Re-iterable synthetic (sequence, modality) batches for one modality."""
 
     def __init__(self, modality, batch_size, seq_len, mod_len=None, n_batches=1, seed=1881, device="cpu", ragged=False, text_vocab=30522, packed=False,
-                 packed_text=False):
+                 packed_text=False, msa_depth=8):
         self.modality, self.B, self.Ls, self.Lm = modality, batch_size, seq_len, mod_len or seq_len
         self.n, self.seed, self.device, self.text_vocab = n_batches, seed, device, text_vocab
         self.ragged, self.packed = ragged or packed, packed
         self.packed_text = bool(packed and packed_text)
+        self.msa_depth = int(msa_depth)
 
     def __len__(self):
         return self.n
@@ -69,10 +71,29 @@ class SyntheticPairs:
             ids[b, n:] = pad
         return ids
 
+    @staticmethod
+    def _msa_frame(gen, B, R, L, ragged):
+        """[B, R, L]: every row of an MSA has the MSA's length (aligned columns: cls 0, then symbols 4 .. 29, no eos -- the MSA alphabet appends none);
+        a ragged MSA has n <= L columns and m <= R rows, everything else is pad 1"""
+        ids = torch.randint(4, 30, (B, R, L), generator=gen)
+        ids[:, :, 0] = 0
+        lens = torch.randint(max(L // 4, 2), L + 1, (B,), generator=gen) if ragged else torch.full((B,), L)
+        rows = torch.randint(max(R // 4, 1), R + 1, (B,), generator=gen) if ragged else torch.full((B,), R)
+        for b in range(B):
+            ids[b, :, int(lens[b]):] = 1
+            ids[b, int(rows[b]):] = 1
+        return ids
+
     def __iter__(self):
         gen = torch.Generator().manual_seed(self.seed)
         for _ in range(self.n):
             seq = self._frame(gen, self.B, self.Ls, 4, 23, 0, 2, 1, self.ragged)
+            if self.modality == "msa":
+                mod = self._msa_frame(gen, self.B, self.msa_depth, self.Lm, self.ragged)
+                if self.packed:
+                    seq = PackedTokens.from_padded(seq, pad_id=1)
+                yield seq.to(self.device), mod.to(self.device), self.modality, None
+                continue
             if self.modality == "text":
                 mod = self._frame(gen, self.B, self.Lm, 5, self.text_vocab - 1, 2, 3, 0, self.ragged)
             else:       # struct_token (and seqsim, which re-uses the sequence vocabulary in the reference)

@@ -728,3 +728,56 @@ class TextEncoder(BaseEncoder):
 
     def extra_repr(self):
         return f"use_lora={self.use_lora}, frozen={self.frozen}"
+
+
+class MsaEncoder(BaseEncoder):
+    """ref msa_encoder.py:6-55: the frozen MSA Transformer tower (oneprot_amd/msa.py; esm_msa1b_t12_100M_UR50S architecture) behind the reference's
+    signature.  `forward(tokens[B, R, L] int64, padding id 1) -> float32 [B, output_dim]`: representation 12, then the masked mean over every non-pad
+    (r, l) (`use_all_msa=True`) or row 0 through `self.pooling`, then proj -> norm.  The tower is always frozen and in eval mode (the reference's train-mode
+    dropout is not reproduced: DESIGN.md section 7); parity with fair-esm is unpinned (no fair-esm, no checkpoint: tests/msa_ref.py is the oracle).
+    `d_model` follows the loaded architecture (768 for the published model, which the reference hard-codes)."""
+
+    def __init__(self, model_name_or_path: str, output_dim: int, pooling_type: str = "mean", proj_type: str = None, use_logit_scale: bool = False,
+                 learnable_logit_scale: bool = False, use_all_msa: bool = False):
+        from .msa import MsaTransformer
+        transformer = MsaTransformer.from_pretrained(model_name_or_path)
+        super().__init__(d_model=transformer.d, output_dim=output_dim, proj_type=proj_type, use_logit_scale=use_logit_scale,
+                         learnable_logit_scale=learnable_logit_scale, pooling_type=pooling_type)
+        self.transformer = transformer
+        self.config = transformer.config
+        self.transformer.eval()
+        for param in self.transformer.parameters():
+            param.requires_grad = False
+        self.use_all_msa = use_all_msa
+
+    def hidden_and_pooled(self, tokens, want_hidden=True):
+        """(representation n_layers fp32 [B, R, L, d] -- [B, L, d] for row 0, None unless wanted --, pooled [B, d]): final LayerNorm fused with the pooling"""
+        tr = self.transformer
+        tr.check_input(tokens)                          # every refusal before the device is touched
+        mode = 0 if self.use_all_msa else getattr(self.pooling, "mode", 3)
+        if mode not in (0, 1):
+            raise NotImplementedError(f"MsaEncoder(use_all_msa=False): pooling_type {self.pooling_type!r} is not built for row 0 of the MSA; use 'mean' or 'cls' "
+                                      "(use_all_msa=True ignores the pooling, as in the reference)")
+        with torch.no_grad():
+            x, _ = tr.run_layers(tokens)
+            B, R, L = tokens.shape
+            d, dev, pad = tr.d, tokens.device, tr.config.padding_idx
+            if self.use_all_msa:                         # one "sequence" of R * L tokens per MSA
+                ids, n = tokens.contiguous().view(B, R * L), R * L
+            else:
+                x, ids, n = x.view(B, R, L, d)[:, 0].contiguous(), tokens[:, 0].contiguous(), L
+            pooled, hidden = torch.empty(B, d, device=dev), (torch.empty(B, n, d, device=dev) if want_hidden else None)
+            hip.call("oneprot_lnpool_fwd", x, ids, pad, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None, None, None,
+                     None, hidden, B, n, d, tr.config.layer_norm_eps, mode)
+        return (hidden.view(B, R, L, d) if (self.use_all_msa and want_hidden) else hidden), pooled
+
+    def forward(self, tokens):
+        return self.apply_head(self.hidden_and_pooled(tokens, want_hidden=False)[1])
+
+    def train(self, mode=True):
+        super().train(mode)
+        self.transformer.eval()
+        return self
+
+    def extra_repr(self):
+        return f"use_all_msa={self.use_all_msa}"

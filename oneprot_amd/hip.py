@@ -126,7 +126,13 @@ _SIGS = {
     "oneprot_sim_rank": (I, [P, P, P, I, I, I, I, P, P, P]),
     "oneprot_sim_topk_workspace": (SZ, [I, I, I]),
     "oneprot_sim_topk": (I, [P, P, I, I, I, I, P, P, P, SZ, P]),
+    "oneprot_msa_embed_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P]),
+    "oneprot_msa_row_scores": (I, [P, P, P, I, I, I, I, I, F, P]),
+    "oneprot_msa_row_context_workspace": (SZ, [I, I, I, I]),
+    "oneprot_msa_row_context": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
+    "oneprot_msa_col_attn": (I, [P, P, P, I, I, I, I, I, F, P]),
 }
+MSA_MAX_LEN, MSA_MAX_ROWS = 1024, 128      # ONEPROT_MSA_MAX_LEN / ONEPROT_MSA_MAX_ROWS of include/oneprot_hip.h
 
 # Expected element type of every pointer argument, in order (f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a
 # flag argument / epilogue id).  The C side validates shapes and alignment but cannot see a tensor's dtype, device or strides: a strided view or an
@@ -146,6 +152,7 @@ _PTR_DTYPES = {
     "oneprot_attn_varlen_fwd_dropout": "hhhiihf", "oneprot_attn_varlen_bwd_dropout": "hhhiihhfffhb", "oneprot_bert_embed_packed_fwd": "liffffffh",
     "oneprot_segment_possum_f32": "fif", "oneprot_pool_packed_fwd": "flif", "oneprot_pool_packed_bwd": "flifh",
     "oneprot_sim_pair_dot": "fff", "oneprot_sim_rank": "fffii", "oneprot_sim_topk": "ffflb",
+    "oneprot_msa_embed_fwd": "lffffff", "oneprot_msa_row_scores": "hff", "oneprot_msa_row_context": "fhfhb", "oneprot_msa_col_attn": "hfh",
 }
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 

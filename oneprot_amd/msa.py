@@ -1,0 +1,243 @@
+"""MSA Transformer tower on the HIP kernels -- what the reference obtains from `esm.pretrained.load_model_and_alphabet_local` in MsaEncoder
+(ref msa_encoder.py:18,36): fair-esm's MSATransformer (esm_msa1b_t12_100M_UR50S: 12 axial layers, d 768, 12 heads of 64, FFN 3072, learned positions,
+an embedding per MSA row).  Forward only and eval mode: the reference freezes the tower (msa_encoder.py:30-32), so there is no backward.
+
+PARITY UNPINNED: fair-esm and its checkpoint are not available to this tree.  The arithmetic is restated from the published model and tested against the
+fp64 restatement tests/msa_ref.py; neither has been compared with a fair-esm run.  State-dict keys are the published module keys -- those a reference
+OneProt checkpoint holds under `network.msa.transformer.` -- and load strictly.
+
+Known differences: the reference calls `module.train()` on the whole network afterwards, which re-activates the model's 0.1
+dropouts; this tower computes the eval-mode numbers only.  Masked keys are excluded instead of biased by -10000 (equal wherever a query has one valid key).
+
+Per layer: LayerNorm -> one QKV GEMM (bf16 [T, 3d]) -> tied row attention (oneprot_msa_row_scores + oneprot_msa_row_context) -> out-projection + residual;
+the same with oneprot_msa_col_attn (R = 1: out_proj(v_proj(x)), as published); LayerNorm -> FFN-1 + GELU -> FFN-2 + residual.  The row-attention score
+map S [B, H, L, L] fp32 is the one large temporary (its bf16 probabilities and the transposed V of the same MSAs ride along in a workspace): the row
+attention runs in groups of whole MSAs so that S stays under ONEPROT_MSA_SCORE_BYTES (default 1 GiB); the grouping is a pure function of (B, R, L, budget) and cannot change a bit of the result (every MSA is computed by its own work-groups).
+"""
+import os
+import warnings
+
+import torch
+
+from . import hip
+from .esm import ArenaModule, ModelConfig
+from .packing import PackedTokens
+
+MSA_DEFAULTS = dict(model_type="msa_transformer", num_layers=12, embed_dim=768, ffn_embed_dim=3072, attention_heads=12, max_positions=1024,
+                    embed_positions_msa=True, msa_rows=1024, vocab_size=33, padding_idx=1, cls_idx=0, eos_idx=2, mask_idx=32, layer_norm_eps=1e-5)
+_ARCH_KEYS = (("layers", "num_layers"), ("embed_dim", "embed_dim"), ("ffn_embed_dim", "ffn_embed_dim"), ("attention_heads", "attention_heads"),
+              ("max_positions", "max_positions"), ("embed_positions_msa", "embed_positions_msa"))
+_BLOCKS = ("row_self_attention", "column_self_attention")
+
+
+def score_bytes_budget():
+    return int(os.environ.get("ONEPROT_MSA_SCORE_BYTES", str(1 << 30)))
+
+
+def plan_groups(B, R, L, H, budget=None):
+    """[(b0, b1), ...]: consecutive groups of whole MSAs whose fp32 score maps [H, L, L] fit `budget` bytes together (one MSA per group when even a single
+    map does not).  A pure function of its arguments."""
+    budget = score_bytes_budget() if budget is None else int(budget)
+    per = 4 * H * L * L
+    g = max(1, min(B, budget // per))
+    return [(b0, min(b0 + g, B)) for b0 in range(0, B, g)]
+
+
+def upgrade_fair_esm_state_dict(sd):
+    """The published key upgrade for this model: the `encoder.` / `sentence_encoder.` prefixes are stripped and `row` and `column` change places in the key
+    names (fair-esm's loader does both for msa_transformer checkpoints)."""
+    out = {}
+    for k, v in sd.items():
+        for pre in ("encoder.sentence_encoder.", "sentence_encoder.", "encoder."):
+            if k.startswith(pre):
+                k = k[len(pre):]
+                break
+        k = k.replace("row", "\0").replace("column", "row").replace("\0", "column")
+        out[k] = v
+    return out
+
+
+def config_from_args(args):
+    """architecture from the `args` (argparse.Namespace or dict) / `cfg` entry of a fair-esm checkpoint"""
+    if args is not None and not isinstance(args, dict):
+        args = getattr(args, "model", args)
+        args = args if isinstance(args, dict) else vars(args)
+    elif isinstance(args, dict) and isinstance(args.get("model"), (dict,)):
+        args = args["model"]
+    cfg = dict(MSA_DEFAULTS)
+    for src, dst in _ARCH_KEYS:
+        if args and args.get(src) is not None:
+            cfg[dst] = type(MSA_DEFAULTS[dst])(args[src])
+    return ModelConfig(**cfg)
+
+
+class MsaTransformer(ArenaModule):
+    final_layer_norm = True
+    accepts_packed = False
+    max_rows = hip.MSA_MAX_ROWS           # deepest MSA the column-attention kernel takes in one pass
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        d, f, n, H = config.embed_dim, config.ffn_embed_dim, config.num_layers, config.attention_heads
+        self.d, self.f, self.n_layers, self.H = d, f, n, H
+        self.hd = d // H
+        if self.hd != 64 or d != H * 64:
+            raise NotImplementedError(f"head_dim {d / H:g}: the MSA attention kernels are built for head_dim 64 (the published model)")
+        if not getattr(config, "embed_positions_msa", True):
+            raise NotImplementedError("embed_positions_msa=False: the published esm_msa1b model carries the MSA-row embedding")
+        pad = config.padding_idx
+        self._init_arena()
+        self._add("embed_tokens.weight", (config.vocab_size, d))
+        self._add("embed_positions.weight", (config.max_positions + pad + 1, d))
+        self._add("msa_position_embedding", (1, config.msa_rows, 1, d))
+        for nm in ("emb_layer_norm_before", "emb_layer_norm_after"):
+            self._add(nm + ".weight", (d,))
+            self._add(nm + ".bias", (d,))
+        for i in range(n):
+            for blk in _BLOCKS:
+                p = f"layers.{i}.{blk}."
+                for nm in "qkv":                        # q | k | v adjacent: one [3d, d] GEMM operand
+                    self._add(p + f"layer.{nm}_proj.weight", (d, d))
+                for nm in "qkv":
+                    self._add(p + f"layer.{nm}_proj.bias", (d,))
+                self._add(p + "layer.out_proj.weight", (d, d))
+                self._add(p + "layer.out_proj.bias", (d,))
+                self._add(p + "layer_norm.weight", (d,))
+                self._add(p + "layer_norm.bias", (d,))
+            p = f"layers.{i}.feed_forward_layer."
+            for nm, shp in (("layer.fc1.weight", (f, d)), ("layer.fc1.bias", (f,)), ("layer.fc2.weight", (d, f)), ("layer.fc2.bias", (d,)),
+                            ("layer_norm.weight", (d,)), ("layer_norm.bias", (d,))):
+                self._add(p + nm, shp)
+        V = config.vocab_size                           # heads present in checkpoints, unused by the reference (ref msa_encoder.py:36 reads representations only)
+        for k, s in (("lm_head.weight", (V, d)), ("lm_head.bias", (V,)), ("lm_head.dense.weight", (d, d)), ("lm_head.dense.bias", (d,)),
+                     ("lm_head.layer_norm.weight", (d,)), ("lm_head.layer_norm.bias", (d,)), ("contact_head.regression.weight", (1, n * H)),
+                     ("contact_head.regression.bias", (1,))):
+            self._extra[k] = s
+        self._finish_arena()
+        self.reset_parameters()
+        self.capture = None                             # test hook: a list that receives (kind, layer, ctx clone) of every attention output
+        for p in self.parameters():
+            p.requires_grad = False
+        self.eval()
+
+    def train(self, mode=True):
+        """always eval: the tower is frozen and only the eval-mode forward exists"""
+        return super().train(False)
+
+    @torch.no_grad()
+    def reset_parameters(self):
+        for name in self._spec:
+            v = self.view(name)
+            if name.endswith("layer_norm.weight") or name in ("emb_layer_norm_before.weight", "emb_layer_norm_after.weight"):
+                v.fill_(1.0)
+            elif name.endswith(".bias"):
+                v.zero_()
+            else:
+                v.normal_(0.0, 0.02)
+        self.view("embed_tokens.weight")[self.config.padding_idx].zero_()
+
+    def check_input(self, tokens):
+        """every refusal, before anything touches the device"""
+        if isinstance(tokens, PackedTokens):
+            raise NotImplementedError("MsaEncoder: packed token streams are an ESM-tower input; the MSA tower takes padded [B, R, L] tokens")
+        if tokens.dim() != 3:
+            raise ValueError(f"MSA tokens must be [B, R, L], got {tuple(tokens.shape)}")
+        B, R, L = tokens.shape
+        cfg = self.config
+        if L > cfg.max_positions or L > hip.MSA_MAX_LEN:
+            raise ValueError(f"sequence length {L} exceeds max_positions {min(cfg.max_positions, hip.MSA_MAX_LEN)}")
+        if R > self.max_rows or R > cfg.msa_rows:
+            raise NotImplementedError(f"MSA depth {R}: the column-attention kernel takes up to {min(self.max_rows, cfg.msa_rows)} rows in one pass")
+        if not tokens.is_cuda:
+            raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
+
+    def _gemm(self, a, w, M, N, K, epi, bias, out0, aux=None):
+        hip.call("oneprot_gemm_bf16_nt", a, w, M, N, K, K, K, epi, bias, out0, None, None, aux, None, None, 1.0, 0, 0, 0)
+
+    @torch.no_grad()
+    def run_layers(self, tokens, save=False):
+        """tokens int64 [B, R, L] -> (pre-final-LayerNorm hidden state fp32 [B*R*L, d], None)"""
+        self.check_input(tokens)
+        if save:
+            raise NotImplementedError("the MSA tower is frozen: there is no backward")
+        self._refresh_bf16_mirror()
+        cfg = self.config
+        tokens = tokens.contiguous()
+        B, R, L = tokens.shape
+        T, d, f, H, hd, dev = B * R * L, self.d, self.f, self.H, self.hd, tokens.device
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
+        eps, pad = cfg.layer_norm_eps, cfg.padding_idx
+        kb, x = f32(T), f32(T, d)
+        hip.call("oneprot_key_padding_bias", tokens, kb, T, pad)
+        hip.call("oneprot_msa_embed_fwd", tokens, self.view("embed_tokens.weight"), self.view("embed_positions.weight"), self.view("msa_position_embedding"),
+                 self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, R, L, d, cfg.vocab_size,
+                 cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
+        groups = plan_groups(B, R, L, H)
+        gmax = max(b1 - b0 for b0, b1 in groups)
+        S = f32(gmax, H, L, L)
+        ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", gmax, R, L, H), dtype=torch.uint8, device=dev)     # probabilities + V transposed, per group
+        h, qkv, ctx, u = b16(T, d), b16(T, 3 * d), b16(T, d), b16(T, f)
+        row_scale = hd ** -0.5 / R ** 0.5               # R = the padded row count, as published
+        for i in range(self.n_layers):
+            for blk in _BLOCKS:
+                p = f"layers.{i}.{blk}."
+                hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
+                if blk == "column_self_attention" and R == 1:       # one row: softmax over a single key (fair-esm ColumnSelfAttention.forward)
+                    self._gemm(h, self._w16(p + "layer.v_proj.weight"), T, d, d, hip.EPI_BF16, self.view(p + "layer.v_proj.bias"), ctx)
+                else:
+                    o, n = self.span(p + "layer.q_proj.weight", p + "layer.v_proj.weight")
+                    ob, nb = self.span(p + "layer.q_proj.bias", p + "layer.v_proj.bias")
+                    self._gemm(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_BF16, self.flat.data[ob:ob + nb], qkv)
+                    if blk == "row_self_attention":
+                        for b0, b1 in groups:
+                            t0, t1 = b0 * R * L, b1 * R * L
+                            hip.call("oneprot_msa_row_scores", qkv[t0:t1], kb[t0:t1], S, b1 - b0, R, L, H, hd, row_scale)
+                            hip.call("oneprot_msa_row_context", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd)
+                    else:
+                        hip.call("oneprot_msa_col_attn", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5)
+                if self.capture is not None:
+                    self.capture.append((blk[:3], i, ctx.clone()))
+                self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, self.view(p + "layer.out_proj.bias"), x, aux=x)
+            p = f"layers.{i}.feed_forward_layer."
+            hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
+            self._gemm(h, self._w16(p + "layer.fc1.weight"), T, f, d, hip.EPI_BIAS_GELU, self.view(p + "layer.fc1.bias"), u)
+            self._gemm(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, self.view(p + "layer.fc2.bias"), x, aux=x)
+        return x, None
+
+    @torch.no_grad()
+    def forward(self, tokens, repr_layers=(), **_):
+        """MSATransformer-compatible call: {"representations": {n_layers: [B, R, L, d]}} (the last representation, after emb_layer_norm_after)"""
+        x, _ = self.run_layers(tokens)
+        B, R, L = tokens.shape
+        y = torch.empty_like(x)
+        hip.call("oneprot_layernorm_fwd", x, 0, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), None, y, None, None,
+                 B * R * L, self.d, self.config.layer_norm_eps)
+        return {"representations": {self.n_layers: y.view(B, R, L, self.d)}}
+
+    @classmethod
+    def from_pretrained(cls, model_name_or_path, **_):
+        """`model_name_or_path`: a raw fair-esm checkpoint file, {"args" | "cfg": ..., "model": state dict} (what the reference hands to
+        esm.pretrained.load_model_and_alphabet_local, msa_encoder.py:18).  PARITY UNPINNED: the key upgrade and the architecture fields follow the published
+        loader, not a run of it."""
+        path = str(model_name_or_path)
+        if not os.path.isfile(path):
+            if os.environ.get("ONEPROT_ALLOW_RANDOM_INIT", "0") != "1":
+                raise OSError(f"no weights (a fair-esm .pt file) found for {model_name_or_path}; "
+                              "set ONEPROT_ALLOW_RANDOM_INIT=1 to build a randomly initialised model of that architecture")
+            warnings.warn(f"{model_name_or_path}: no weight file, using random initialisation")
+            return cls(ModelConfig(**MSA_DEFAULTS))
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+        cfg = config_from_args(ck.get("cfg") if ck.get("cfg") is not None else ck.get("args"))
+        sd = upgrade_fair_esm_state_dict(ck["model"])
+        for k in ("embed_tokens.weight", "msa_position_embedding"):
+            if k in sd:
+                setattr(cfg, "vocab_size" if k == "embed_tokens.weight" else "msa_rows", sd[k].shape[0 if k == "embed_tokens.weight" else 1])
+        model = cls(cfg)
+        missing, unexpected = model.load_state_dict(sd, strict=False)
+        missing = [m for m in missing if not (m.startswith(("lm_head.", "contact_head.", "extra.")))]
+        unexpected = [u for u in unexpected if not u.endswith("_float_tensor")]
+        if missing or unexpected:
+            raise OSError(f"checkpoint {model_name_or_path}: missing {missing[:5]}, unexpected {unexpected[:5]}")
+        return model

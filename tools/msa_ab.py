@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""The MSA tower forward on the HIP kernels against the only alternative a user of this tree has -- the torch restatement tests/msa_ref.py on the same
+device under bf16 autocast -> profiles/msa_encoder.json.
+
+One process, device-synchronised; each shape is warmed up, then both variants are timed `--reps` (>= 5) times, alternating.  Published architecture
+(12 layers, d 768, 12 heads, FFN 3072), random weights, ragged synthetic MSAs:
+  b16_r50_l512    B = 16, R = 50, L = 512  (the reference's batch: configs/data/modalities/msa.yaml)
+  b4_r50_l1024    B = 4,  R = 50, L = 1024
+GATE, recorded per shape: the HIP median is lower than the torch median by more than the larger of the two spreads (max - min).  A miss is a defect of the
+new kernels and is reported as such.
+Per-kernel shares come from a kernel trace taken in a run of its own:
+  rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/msa_ab.py --only b16_r50_l512 --reps 1 --hip-only --out /dev/null
+  python tools/msa_ab.py --fold-trace DIR            (adds kernel_shares to the JSON written before)
+usage: msa_ab.py [--only NAME[,NAME]] [--reps 5] [--out profiles/msa_encoder.json] [--small] [--hip-only]"""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+import warnings
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SHAPES = {"b16_r50_l512": (16, 50, 512), "b4_r50_l1024": (4, 50, 1024)}
+SMALL = {"b16_r50_l512": (2, 6, 96), "b4_r50_l1024": (1, 6, 160)}
+
+
+def timed(fn, reps_list):
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    reps_list.append(a.elapsed_time(b))
+    return out
+
+
+def stats(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "spread_ms": max(ms) - min(ms), "reps": len(ms)}
+
+
+def run_shape(tr, sd, name, reps, small, hip_only):
+    import torch
+    from oneprot_amd.data import SyntheticPairs
+    from oneprot_amd.msa import plan_groups
+    from tests import msa_ref as MR
+    B, R, L = (SMALL if small else SHAPES)[name]
+    tok = SyntheticPairs._msa_frame(torch.Generator().manual_seed(50), B, R, L, True).cuda()
+    n = tr.n_layers
+
+    def hip_fwd():
+        return tr(tok)["representations"][n]
+
+    def torch_fwd():
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            return MR.forward(tok, sd, tr.H, dtype=torch.float32)
+
+    variants = {"hip": hip_fwd} if hip_only else {"hip": hip_fwd, "torch_bf16_autocast": torch_fwd}
+    res = {k: f().float() for k, f in variants.items()}                # warm-up (and the outputs to compare)
+    torch.cuda.synchronize()
+    out = {"B": B, "R": R, "L": L, "tokens": B * R * L, "score_groups": len(plan_groups(B, R, L, tr.H))}
+    if not hip_only:
+        m = tok.ne(1).unsqueeze(-1)
+        a, b = res["hip"] * m, res["torch_bf16_autocast"] * m
+        out["hidden_cosine_hip_vs_torch"] = float(torch.nn.functional.cosine_similarity(a.flatten(), b.flatten(), dim=0))
+    del res                                                            # (the allocator keeps its blocks: the timed repetitions do not pay hipMalloc)
+    ms = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, f in variants.items():                                  # alternating
+            timed(f, ms[k])
+    for k in variants:
+        out[k] = stats(ms[k])
+    if not hip_only:
+        allowed = max(out["hip"]["spread_ms"], out["torch_bf16_autocast"]["spread_ms"])
+        out["gate"] = {"rule": "hip median < torch median - max(spread of either)", "margin_ms": allowed,
+                       "passed": bool(out["hip"]["median_ms"] < out["torch_bf16_autocast"]["median_ms"] - allowed)}
+    return out
+
+
+def fold_trace(trace_dir, out_path):
+    groups = (("k_msa_row_scores", "msa_row_scores"), ("k_msa_row_softmax", "msa_row_context"), ("k_msa_v_transpose", "msa_row_context"),
+              ("k_msa_row_pv", "msa_row_context"), ("k_msa_col_attn", "msa_col_attn"), ("k_msa_embed", "msa_embed"),
+              ("gemm", "nt_gemm"), ("layernorm", "layernorm"), ("lnpool", "layernorm"))
+    tot = {}
+    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as f:
+            for row in csv.DictReader(f):
+                name = row.get("Kernel_Name") or row.get("Name") or ""
+                key = next((g for pat, g in groups if pat in name), "other")
+                tot[key] = tot.get(key, 0) + int(row["End_Timestamp"]) - int(row["Start_Timestamp"])
+    if not any(k.startswith("msa_") for k in tot):
+        sys.exit(f"no k_msa_* dispatches in a *kernel_trace.csv under {trace_dir}")
+    total = sum(tot.values())
+    doc = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    doc["kernel_shares"] = {"note": "whole traced process (warm-up + 1 repetition, HIP variant only)", "trace_ns": tot,
+                            "share": {k: v / total for k, v in sorted(tot.items(), key=lambda kv: -kv[1])}}
+    json.dump(doc, open(out_path, "w"), indent=1)
+    print(json.dumps(doc["kernel_shares"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default=",".join(SHAPES))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "msa_encoder.json"))
+    ap.add_argument("--small", action="store_true", help="small shapes: a dry run of the tool, not a measurement")
+    ap.add_argument("--hip-only", action="store_true", help="run the HIP variant alone (for the kernel trace)")
+    ap.add_argument("--fold-trace", default=None)
+    a = ap.parse_args()
+    if a.fold_trace:
+        return fold_trace(a.fold_trace, a.out)
+    import torch
+    from oneprot_amd.msa import MsaTransformer
+    os.environ["ONEPROT_ALLOW_RANDOM_INIT"] = "1"
+    warnings.filterwarnings("ignore", message=".*no weight file.*")
+    torch.manual_seed(0)
+    tr = MsaTransformer.from_pretrained("esm_msa1b_t12_100M_UR50S.pt").cuda()
+    sd = {k: v.detach() for k, v in tr.state_dict().items() if not k.startswith(("lm_head.", "contact_head."))}
+    doc = {"device": torch.cuda.get_device_name(0), "small_shapes": a.small, "weights": "random (published architecture)",
+           "torch_variant": "tests/msa_ref.py forward, fp32 weights, torch.autocast(bfloat16)"}
+    for name in a.only.split(","):
+        doc[name] = run_shape(tr, sd, name, max(a.reps, 1), a.small, a.hip_only)
+        print(name, json.dumps(doc[name]), flush=True)
+        torch.cuda.empty_cache()
+    if a.out != "/dev/null":
+        json.dump(doc, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
