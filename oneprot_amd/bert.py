@@ -11,6 +11,7 @@ import warnings
 import torch
 
 from . import hip
+from . import layout
 from .esm import ArenaModule, ModelConfig, load_weight_file, resolve_config, _Out
 from .packing import PackedTokens
 
@@ -32,39 +33,15 @@ def resolve_bert_config(model_name_or_path):
     raise OSError(f"{model_name_or_path} is not a local folder with a config.json and is not a known BERT model identifier")
 
 
-class _PaddedLayout:
-    """The layout-dependent stages of the BERT tower on a padded [B, L] batch: embedding (position l = row % L), attention (key-padding bias, with or
-    without probability dropout) and the position-table gradient (sum over the batch).  Everything else runs row-wise on the B*L rows."""
-    packed = False
-
-    def __init__(self, tr, ids):
-        self.ids = ids.contiguous()
-        self.B, self.L = ids.shape
-        self.T = self.B * self.L
+class _BertPadded(layout.PaddedLayout):
+    """The BERT stages of a padded [B, L] batch: embedding (position l = row % L) and the position-table gradient (sum over the batch)."""
 
     def embed(self, tr, x, h):
         cfg, e = tr.config, "embeddings."
-        self.key_bias = torch.empty(self.B, self.L, dtype=torch.float32, device=x.device)
-        hip.call("oneprot_key_padding_bias", self.ids, self.key_bias, self.T, cfg.pad_token_id)
+        self.make_key_bias(cfg.pad_token_id)
         hip.call("oneprot_bert_embed_fwd", self.ids, tr.view(e + "word_embeddings.weight"), tr.view(e + "position_embeddings.weight"),
                  tr.view(e + "token_type_embeddings.weight"), tr.view(e + "LayerNorm.weight"), tr.view(e + "LayerNorm.bias"), x, h, self.B, self.L, tr.d,
                  cfg.vocab_size, cfg.layer_norm_eps)
-
-    def attn_fwd(self, q, k, v, ctx, lse, H, hd, drop=None):
-        if drop is not None:
-            hip.call("oneprot_attn_fwd_dropout", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd, *drop)
-        else:
-            hip.call("oneprot_attn_fwd", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd)
-
-    def attn_workspace(self, H, dev):
-        return torch.empty(hip.query("oneprot_attn_bwd_workspace", self.B, H, self.L), dtype=torch.uint8, device=dev)
-
-    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd, drop=None):
-        if drop is not None:
-            hip.call("oneprot_attn_bwd_dropout", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], None, None, q_scale, dqkv, ws,
-                     self.B, H, self.L, hd, *drop)
-        else:
-            hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], None, None, q_scale, dqkv, ws, self.B, H, self.L, hd)
 
     def pos_rows(self, tr):
         """the position-embedding row of every token: fp32 [T, d]"""
@@ -76,47 +53,19 @@ class _PaddedLayout:
         return self.L
 
 
-class _PackedLayout:
-    """The same stages on a packed caption stream (oneprot_amd.packing, pad id = the tower's pad_token_id): the row-wise stages see ONE sequence of T_pad
-    rows (B = 1, L = T_pad; the QKV epilogue's rotary tables are the (1, 0) rows of _norope(T_pad)); absolute positions restart at every segment,
-    attention runs per segment (varlen kernels; no key-bias tensor is built: the segment end is the only mask) and the position-table gradient sums
-    row l over the segments that reach it.  Tail rows hold the pad id: finite activations, exactly zero gradient rows.
+class _BertPacked(layout.PackedLayout):
+    """The same on a packed caption stream (pad id = the tower's pad_token_id; the QKV epilogue's rotary tables are the (1, 0) rows of _norope(T_pad)):
+    absolute positions restart at every segment and the position-table gradient sums row l over the segments that reach it.
 
     Dropout: the attention-probability masks are those of the padded batch of the same captions in the same order (stream s * H + h, positions within
     the segment).  The hidden-state Philox masks are indexed by element of the [T_pad, d] stream, so they differ from the padded layout's [B * L, d]
     masks: the same distribution, another draw."""
-    packed = True
-
-    def __init__(self, tr, packed):
-        self.p = packed
-        self.ids = packed.ids
-        self.cu = packed.cu_seqlens
-        self.N, self.B, self.L = len(packed), 1, packed.T_pad
-        self.T = packed.T_pad
-        self.work = packed.attn_work()
 
     def embed(self, tr, x, h):
         cfg, e = tr.config, "embeddings."
         hip.call("oneprot_bert_embed_packed_fwd", self.ids, self.cu, tr.view(e + "word_embeddings.weight"), tr.view(e + "position_embeddings.weight"),
                  tr.view(e + "token_type_embeddings.weight"), tr.view(e + "LayerNorm.weight"), tr.view(e + "LayerNorm.bias"), x, h, self.N, self.T, tr.d,
                  cfg.vocab_size, cfg.max_position_embeddings, cfg.layer_norm_eps)
-
-    def attn_fwd(self, q, k, v, ctx, lse, H, hd, drop=None):
-        if drop is not None:
-            hip.call("oneprot_attn_varlen_fwd_dropout", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd, *drop)
-        else:
-            hip.call("oneprot_attn_varlen_fwd", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd)
-
-    def attn_workspace(self, H, dev):
-        return torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, self.T), dtype=torch.uint8, device=dev)
-
-    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd, drop=None):
-        if drop is not None:
-            hip.call("oneprot_attn_varlen_bwd_dropout", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], None, None,
-                     q_scale, dqkv, ws, self.N, self.T, H, hd, *drop)
-        else:
-            hip.call("oneprot_attn_varlen_bwd", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], None, None, q_scale,
-                     dqkv, ws, self.N, self.T, H, hd)
 
     def pos_rows(self, tr):
         # the position of every stream row, built on the host from the lengths (no device read-back); tail rows take position 0
@@ -134,12 +83,12 @@ class _PackedLayout:
         return n
 
 
-def _layout(tr, ids):
-    return _PackedLayout(tr, ids) if isinstance(ids, PackedTokens) else _PaddedLayout(tr, ids)
+_layout = layout.of      # _layout(tower, ids): the layout of a padded batch or a packed stream, one of tower.layouts
 
 
 class BertTransformer(ArenaModule):
     final_layer_norm = False      # post-LN model: pooling reads the last layer's output directly
+    layouts = (_BertPadded, _BertPacked)      # layout.of(self, ids)
     accepts_packed = True         # run_layers / backward_layers take a PackedTokens stream (oneprot_amd.packing)
 
     def __init__(self, config):
@@ -427,10 +376,7 @@ class BertTransformer(ArenaModule):
     def forward(self, input_ids=None, attention_mask=None, **_):
         """BertModel-compatible call returning .last_hidden_state; a packed input gives the stream's [T_pad, d] (tail rows: finite, meaningless)"""
         x, _ = self.run_layers(input_ids, save=False)
-        if isinstance(input_ids, PackedTokens):
-            return _Out(x)
-        B, L = input_ids.shape
-        return _Out(x.view(B, L, self.d))
+        return _Out(_layout(self, input_ids).final_hidden(self, x))
 
     @classmethod
     def from_pretrained(cls, model_name_or_path, **_):

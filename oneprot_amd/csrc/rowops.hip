@@ -11,18 +11,49 @@
 #define ROWS_PER_BLOCK 4       // 256 threads = 4 waves = 4 rows in flight per block
 
 // --------------------------------------------------------------------------------------------------------
+// Where a work-group finds the rows of its sequence: THE padded / packed fork of the row kernels (attention.hip's is AttnSlab).
+//   padded (VAR = false): sequence b = rows [b * L, (b + 1) * L) of a [B, L] batch.
+//   packed (VAR = true):  sequence b = rows [cu[b], cu[b+1]) of a stream of T_pad rows; work-group N, where the grid has one, takes the tail
+//                         [cu[N], T_pad) of pad rows.  THE guard against a malformed cu_seqlens: ok only if 0 <= base, 0 < L and base + L <= T_pad;
+//                         a group that is not ok touches nothing.  (oneprot_attnpool_packed_fwd has no T_pad and passes N * max_len: that checks cu_seqlens
+//                         against itself, cu[N] <= N * max_len, and does not bound the buffers.)
+// --------------------------------------------------------------------------------------------------------
+struct RowSeg { size_t base; int L; bool tail; bool ok; };
+template <bool VAR>
+__device__ __forceinline__ RowSeg row_seg(int b, int L_or_T_pad, const int* __restrict__ cu, int N) {
+  if constexpr (!VAR) {
+    return {(size_t)b * L_or_T_pad, L_or_T_pad, false, true};
+  } else {
+    const bool tail = b == N;
+    const int base = cu[b], L = (tail ? L_or_T_pad : cu[b + 1]) - base;
+    return {(size_t)base, L, tail, L > 0 && base >= 0 && base + L <= L_or_T_pad};
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------
 // Embedding forward  (hf modeling_esm.py:224-271; ref call site sequence_encoder.py:78)
 // x[b,l,:] = W[id] * 0.88 / (1 - n_mask_b / n_valid_b)  ; 0 where id==mask ; 0 where id==pad
+// Padded: grid (chunks of L, B), the factor also goes to scale_out[b] (row_scale [B]).
+// Packed (VAR; the same arithmetic per sequence): grid (chunks of max_len, N + 1); the tail's pad ids give zero rows and scale 0.  The factor is counted
+// per sequence and kept per token (scale_out = tok_scale [T_pad]: the row_scale of the backward with L = 1).  Also gathers the rotary tables per token:
+// cos_out[t] = rope_cos[position of t within its sequence] ([T_pad, half]; tail rows take position 0), the form the QKV GEMM's rotary epilogue reads
+// with B = 1, L = T_pad.
 // --------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_embed_fwd(const long long* __restrict__ ids, const float* __restrict__ W, float* __restrict__ x,
-                                                   float* __restrict__ row_scale, int L, int d, int vocab, int pad_id, int mask_id,
-                                                   int token_dropout, int tok_per_block) {
+template <bool VAR>
+__global__ void __launch_bounds__(256) k_embed_fwd(const long long* __restrict__ ids, const int* __restrict__ cu, const float* __restrict__ W,
+                                                   const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, float* __restrict__ x,
+                                                   float* __restrict__ scale_out, float* __restrict__ cos_out, float* __restrict__ sin_out, int N,
+                                                   int L_or_T_pad, int d, int vocab, int half, int n_pos, int pad_id, int mask_id, int token_dropout,
+                                                   int tok_per_block) {
   const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
+  const RowSeg sg = row_seg<VAR>(b, L_or_T_pad, cu, N);
+  if (!sg.ok) return;
+  const int L = sg.L;
   __shared__ float s_cnt[2][4];
   __shared__ float s_scale;
   float nvalid = 0.f, nmask = 0.f;
   for (int l = tid; l < L; l += 256) {
-    const long long id = ids[(size_t)b * L + l];
+    const long long id = ids[sg.base + l];
     nvalid += (id != pad_id);
     nmask += (id == mask_id);
   }
@@ -33,77 +64,18 @@ __global__ void __launch_bounds__(256) k_embed_fwd(const long long* __restrict__
     const float nv = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
     const float nm = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
     float sc = 1.0f;
-    if (token_dropout) sc = (1.0f - 0.15f * 0.8f) / (1.0f - nm / nv);
-    s_scale = sc;
-    if (chunk == 0 && row_scale) row_scale[b] = sc;
-  }
-  __syncthreads();
-  const float sc = s_scale;
-  const int nv4 = d >> 2;
-  const int l0 = chunk * tok_per_block;
-  const int l1 = min(L, l0 + tok_per_block);
-  const int wave = tid >> 6, lane = tid & 63;
-  for (int l = l0 + wave; l < l1; l += 4) {
-    const long long id = ids[(size_t)b * L + l];
-    const bool zero = (id == pad_id) || (token_dropout && id == mask_id) || id < 0 || id >= vocab;
-    const float4* src = reinterpret_cast<const float4*>(W + (size_t)(zero ? 0 : id) * d);
-    float4* dst = reinterpret_cast<float4*>(x + ((size_t)b * L + l) * d);
-    for (int v = lane; v < nv4; v += 64) {
-      float4 e = src[v];
-      if (zero) e = make_float4(0.f, 0.f, 0.f, 0.f);
-      else { e.x *= sc; e.y *= sc; e.z *= sc; e.w *= sc; }
-      dst[v] = e;
-    }
-  }
-}
-
-extern "C" int oneprot_esm_embed_fwd(const int64_t* ids, const float* table, float* x, float* row_scale, int B, int L, int d, int vocab,
-                                     int pad_id, int mask_id, int token_dropout, void* stream) {
-  if (!ids || !table || !x || B <= 0 || L <= 0 || d <= 0 || (d & 3)) return OP_EINVAL;
-  const int tpb = 32;
-  dim3 grid((L + tpb - 1) / tpb, B);
-  hipLaunchKernelGGL(k_embed_fwd, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)ids, table, x, row_scale, L, d, vocab, pad_id,
-                     mask_id, token_dropout, tpb);
-  return launch_status();
-}
-
-// Packed embedding (the same arithmetic per sequence; sequence b = rows [cu[b], cu[b+1]) of the stream, work-group row N = the tail, whose pad ids give
-// zero rows and tok_scale 0).  The token-dropout factor is counted per sequence and kept per token (tok_scale [T_pad]: the row_scale of the backward
-// with L = 1).  Also gathers the rotary tables per token: cos_out[t] = rope_cos[position of t within its sequence] ([T_pad, half]; tail rows take
-// position 0), the form the QKV GEMM's rotary epilogue reads with B = 1, L = T_pad.
-__global__ void __launch_bounds__(256) k_embed_packed_fwd(const long long* __restrict__ ids, const int* __restrict__ cu, const float* __restrict__ W,
-                                                          const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, float* __restrict__ x,
-                                                          float* __restrict__ tok_scale, float* __restrict__ cos_out, float* __restrict__ sin_out, int N, int T_pad,
-                                                          int d, int vocab, int half, int n_pos, int pad_id, int mask_id, int token_dropout, int tok_per_block) {
-  const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
-  const bool tail = b == N;
-  const int base = cu[b], L = (tail ? T_pad : cu[b + 1]) - base;
-  if (L <= 0 || base < 0 || base + L > T_pad) return;
-  __shared__ float s_cnt[2][4];
-  __shared__ float s_scale;
-  float nvalid = 0.f, nmask = 0.f;
-  for (int l = tid; l < L; l += 256) {
-    const long long id = ids[(size_t)base + l];
-    nvalid += (id != pad_id);
-    nmask += (id == mask_id);
-  }
-  nvalid = wave_sum(nvalid); nmask = wave_sum(nmask);
-  if ((tid & 63) == 0) { s_cnt[0][tid >> 6] = nvalid; s_cnt[1][tid >> 6] = nmask; }
-  __syncthreads();
-  if (tid == 0) {
-    const float nv = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-    const float nm = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
-    float sc = 1.0f;
-    if (token_dropout && nv > 0.f) sc = (1.0f - 0.15f * 0.8f) / (1.0f - nm / nv);
-    s_scale = tail ? 0.f : sc;
+    if (token_dropout && (!VAR || nv > 0.f)) sc = (1.0f - 0.15f * 0.8f) / (1.0f - nm / nv);      // (only the packed form asks for a valid token first)
+    s_scale = sg.tail ? 0.f : sc;
+    if (!VAR && chunk == 0 && scale_out) scale_out[b] = sc;
   }
   __syncthreads();
   const float sc = s_scale;
   const int nv4 = d >> 2;
   const int wave = tid >> 6, lane = tid & 63;
-  for (int l0 = chunk * tok_per_block; l0 < L; l0 += gridDim.x * tok_per_block)      // (the tail may be longer than max_len)
+  // padded: the grid covers L, one trip; packed: the grid covers max_len and the tail may be longer, so the chunks stride over it
+  for (int l0 = chunk * tok_per_block; l0 < L; l0 += VAR ? gridDim.x * tok_per_block : L)
   for (int l = l0 + wave; l < min(L, l0 + tok_per_block); l += 4) {
-    const size_t t = (size_t)base + l;
+    const size_t t = sg.base + l;
     const long long id = ids[t];
     const bool zero = (id == pad_id) || (token_dropout && id == mask_id) || id < 0 || id >= vocab;
     const float4* src = reinterpret_cast<const float4*>(W + (size_t)(zero ? 0 : id) * d);
@@ -114,13 +86,25 @@ __global__ void __launch_bounds__(256) k_embed_packed_fwd(const long long* __res
       else { e.x *= sc; e.y *= sc; e.z *= sc; e.w *= sc; }
       dst[v] = e;
     }
-    const int pos = tail ? 0 : min(l, n_pos - 1);
-    for (int j = lane; j < half; j += 64) {
-      cos_out[t * half + j] = rope_cos[(size_t)pos * half + j];
-      sin_out[t * half + j] = rope_sin[(size_t)pos * half + j];
+    if constexpr (VAR) {
+      const int pos = sg.tail ? 0 : min(l, n_pos - 1);
+      for (int j = lane; j < half; j += 64) {
+        cos_out[t * half + j] = rope_cos[(size_t)pos * half + j];
+        sin_out[t * half + j] = rope_sin[(size_t)pos * half + j];
+      }
+      if (lane == 0) scale_out[t] = sc;
     }
-    if (lane == 0) tok_scale[t] = sc;
   }
+}
+
+extern "C" int oneprot_esm_embed_fwd(const int64_t* ids, const float* table, float* x, float* row_scale, int B, int L, int d, int vocab,
+                                     int pad_id, int mask_id, int token_dropout, void* stream) {
+  if (!ids || !table || !x || B <= 0 || L <= 0 || d <= 0 || (d & 3)) return OP_EINVAL;
+  const int tpb = 32;
+  dim3 grid((L + tpb - 1) / tpb, B);
+  hipLaunchKernelGGL(k_embed_fwd<false>, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)ids, (const int*)nullptr, table, (const float*)nullptr,
+                     (const float*)nullptr, x, row_scale, (float*)nullptr, (float*)nullptr, B, L, d, vocab, 0, 0, pad_id, mask_id, token_dropout, tpb);
+  return launch_status();
 }
 
 extern "C" int oneprot_esm_embed_packed_fwd(const int64_t* ids, const int* cu_seqlens, const float* table, const float* rope_cos, const float* rope_sin, float* x,
@@ -131,7 +115,7 @@ extern "C" int oneprot_esm_embed_packed_fwd(const int64_t* ids, const int* cu_se
     return OP_EINVAL;
   const int tpb = 32;
   dim3 grid((max_len + tpb - 1) / tpb, N + 1);
-  hipLaunchKernelGGL(k_embed_packed_fwd, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)ids, cu_seqlens, table, rope_cos, rope_sin, x, tok_scale,
+  hipLaunchKernelGGL(k_embed_fwd<true>, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)ids, cu_seqlens, table, rope_cos, rope_sin, x, tok_scale,
                      cos_out, sin_out, N, T_pad, d, vocab, half, n_pos, pad_id, mask_id, token_dropout, tpb);
   return launch_status();
 }
@@ -516,21 +500,18 @@ template <bool VAR>
 __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, int pad_id, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float* __restrict__ pooled, float* __restrict__ mean_out,
                                                     float* __restrict__ rstd_out, float* __restrict__ wrow, bf16_t* __restrict__ hidden_bf16,
-                                                    float* __restrict__ hidden_f32, int L, int d, float eps, int mode, const int* __restrict__ cu = nullptr,
-                                                    int N = 0) {
+                                                    float* __restrict__ hidden_f32, int L_or_T_pad, int d, float eps, int mode,
+                                                    const int* __restrict__ cu = nullptr, int N = 0) {
   extern __shared__ __attribute__((aligned(16))) float s_pool[];    // [8][d]
   __shared__ float s_n[8];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv4 = d >> 2;
   const float inv_d = 1.0f / (float)d;
-  size_t base = (size_t)b * L;                       // stream row of the sequence's first token
-  bool tail = false;
-  if constexpr (VAR) {                               // (L is T_pad here)
-    tail = b == N;
-    base = (size_t)cu[b];
-    L = (tail ? L : cu[b + 1]) - cu[b];
-    if (L <= 0) return;
-  }
+  const RowSeg sg = row_seg<VAR>(b, L_or_T_pad, cu, N);
+  if (!sg.ok) return;
+  const size_t base = sg.base;                       // stream row of the sequence's first token
+  const int L = sg.L;
+  const bool tail = sg.tail;
   float cnt = 0.f;
   for (int l = threadIdx.x; l < L; l += 512) cnt += (ids[base + l] != pad_id);
   cnt = wave_sum(cnt);
@@ -563,7 +544,7 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
     const size_t row = base + l;
     const bool valid = validn;
     float wt = (mode == 0) ? (valid ? inv_n : 0.f) : (l == 0 ? 1.f : 0.f);
-    if (VAR && tail) wt = 0.f;
+    if (tail) wt = 0.f;
     float4 v[MAXV];
     float s = 0.f;
 #pragma unroll
@@ -606,7 +587,7 @@ __global__ void __launch_bounds__(512) k_lnpool_fwd(const float* __restrict__ x,
     if (c < nv4) reinterpret_cast<float4*>(s_pool + (size_t)wave * d)[c] = acc[i];
   }
   __syncthreads();
-  if (VAR && tail) return;
+  if (tail) return;
   for (int j = threadIdx.x; j < d; j += 512) {
     float s = 0.f;
 #pragma unroll
@@ -698,19 +679,18 @@ extern "C" int oneprot_bert_embed_fwd(const int64_t* ids, const float* word, con
 
 // Packed stream (ref text_encoder.py:54-62 on a batch without its padding): segment b = rows [cu[b], cu[b+1]), absolute positions restart at every
 // segment; work-group row N = the tail [cu[N], T_pad), whose rows take position 0 (finite rows: LN of word[pad] + pos[0] + type0).  Segments are
-// found as in k_embed_packed_fwd: grid (chunks of 32 tokens, N + 1).
+// found as in k_embed_fwd<true>: grid (chunks of 32 tokens, N + 1).
 __global__ void __launch_bounds__(256) k_bert_embed_packed(const long long* __restrict__ ids, const int* __restrict__ cu, const float* __restrict__ word,
                                                            const float* __restrict__ pos, const float* __restrict__ type0, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ x_f32, bf16_t* __restrict__ x_bf16, int N,
                                                            int T_pad, int d, int vocab, int n_pos, float eps, int tok_per_block) {
-  const int b = blockIdx.y, chunk = blockIdx.x, wave = threadIdx.x >> 6;
-  const bool tail = b == N;
-  const int base = cu[b], L = (tail ? T_pad : cu[b + 1]) - base;
-  if (L <= 0 || base < 0 || base + L > T_pad) return;
-  for (int l0 = chunk * tok_per_block; l0 < L; l0 += gridDim.x * tok_per_block)      // (the tail may be longer than max_len)
-    for (int l = l0 + wave; l < min(L, l0 + tok_per_block); l += ROWS_PER_BLOCK) {
-      const size_t t = (size_t)base + l;
-      bert_embed_row(ids[t], tail ? 0 : min(l, n_pos - 1), t, word, pos, type0, gamma, beta, x_f32, x_bf16, d, vocab, eps);
+  const int chunk = blockIdx.x, wave = threadIdx.x >> 6;
+  const RowSeg sg = row_seg<true>(blockIdx.y, T_pad, cu, N);
+  if (!sg.ok) return;
+  for (int l0 = chunk * tok_per_block; l0 < sg.L; l0 += gridDim.x * tok_per_block)      // (the tail may be longer than max_len)
+    for (int l = l0 + wave; l < min(sg.L, l0 + tok_per_block); l += ROWS_PER_BLOCK) {
+      const size_t t = sg.base + l;
+      bert_embed_row(ids[t], sg.tail ? 0 : min(l, n_pos - 1), t, word, pos, type0, gamma, beta, x_f32, x_bf16, d, vocab, eps);
     }
 }
 // (a segment longer than n_pos is the caller's error -- the tower raises before it gets here; the kernel clamps the position, it never reads past the table)
@@ -749,22 +729,29 @@ extern "C" int oneprot_segment_possum_f32(const float* de, const int* cu_seqlens
   return launch_status();
 }
 
-// Pooling without a LayerNorm in front (BERT's last layer output is already normalised): mode 0 masked mean, 1 CLS (ref base_encoder.py:109-126)
-__global__ void __launch_bounds__(256) k_pool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, int pad_id, float* __restrict__ pooled, int L, int d, int mode) {
+// Pooling without a LayerNorm in front (BERT's last layer output is already normalised): mode 0 masked mean, 1 CLS (ref base_encoder.py:109-126).
+// VAR: the same per segment of a packed stream (x fp32 [T_pad, d], ids int64 [T_pad]): the text tower packed (ref text_encoder.py:54-62); grid N, no
+// tail group (the tail has no pooled row).
+template <bool VAR>
+__global__ void __launch_bounds__(256) k_pool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, const int* __restrict__ cu, int pad_id,
+                                                  float* __restrict__ pooled, int N, int L_or_T_pad, int d, int mode) {
   const int b = blockIdx.x;
+  const RowSeg sg = row_seg<VAR>(b, L_or_T_pad, cu, N);
+  if (!sg.ok) return;
+  const int L = sg.L;
   __shared__ float s_n[4];
   float cnt = 0.f;
-  for (int l = threadIdx.x; l < L; l += 256) cnt += (ids[(size_t)b * L + l] != pad_id);
+  for (int l = threadIdx.x; l < L; l += 256) cnt += (ids[sg.base + l] != pad_id);
   cnt = wave_sum(cnt);
   if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = cnt;
   __syncthreads();
   const float inv_n = 1.0f / (s_n[0] + s_n[1] + s_n[2] + s_n[3]);
   for (int j = threadIdx.x; j < d; j += 256) {
     float s = 0.f;
-    if (mode == 1) s = x[(size_t)b * L * d + j];
+    if (mode == 1) s = x[sg.base * d + j];
     else {
       for (int l = 0; l < L; ++l)
-        if (ids[(size_t)b * L + l] != pad_id) s += x[((size_t)b * L + l) * d + j];
+        if (ids[sg.base + l] != pad_id) s += x[(sg.base + l) * d + j];
       s *= inv_n;
     }
     pooled[(size_t)b * d + j] = s;
@@ -772,10 +759,19 @@ __global__ void __launch_bounds__(256) k_pool_fwd(const float* __restrict__ x, c
 }
 extern "C" int oneprot_pool_fwd(const float* x, const int64_t* ids, int pad_id, float* pooled, int B, int L, int d, int mode, void* stream) {
   if (!x || !ids || !pooled || B <= 0 || L <= 0 || d <= 0 || mode < 0 || mode > 1) return OP_EINVAL;
-  hipLaunchKernelGGL(k_pool_fwd, dim3(B), dim3(256), 0, (hipStream_t)stream, x, (const long long*)ids, pad_id, pooled, L, d, mode);
+  hipLaunchKernelGGL(k_pool_fwd<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, x, (const long long*)ids, (const int*)nullptr, pad_id, pooled, B, L, d, mode);
+  return launch_status();
+}
+extern "C" int oneprot_pool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, float* pooled, int N, int T_pad, int d, int mode,
+                                       void* stream) {
+  if (!x || !ids || !cu_seqlens || !pooled || N <= 0 || T_pad <= 0 || d <= 0 || mode < 0 || mode > 1) return OP_EINVAL;
+  hipLaunchKernelGGL(k_pool_fwd<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, x, (const long long*)ids, cu_seqlens, pad_id, pooled, N, T_pad, d, mode);
   return launch_status();
 }
 
+// The two backward kernels are NOT one body behind row_seg: merged, the packed instantiation's store loop came out instruction for instruction the same but
+// 12 bytes further into the function, and its CLS mode (a pure store kernel) measured 1 % slower in nine of nine alternating runs
+// (profiles/rowseg_ab.txt, section 2a).  They keep the decoder's guard, spelled out.
 // backward of k_pool_fwd: g[b,l,:] = dpooled[b,:] / n_b on non-pad tokens (mean) or dpooled[b,:] at l = 0 (CLS), 0 elsewhere; fp32 + bf16 copy
 __global__ void __launch_bounds__(256) k_pool_bwd(const float* __restrict__ dpooled, const long long* __restrict__ ids, int pad_id, float* __restrict__ g,
                                                   bf16_t* __restrict__ g16, int L, int d, int mode) {
@@ -806,39 +802,7 @@ extern "C" int oneprot_pool_bwd(const float* dpooled, const int64_t* ids, int pa
   return launch_status();
 }
 
-// The same pooling per segment of a packed stream (x fp32 [T_pad, d], ids int64 [T_pad]; segment b = rows [cu[b], cu[b+1])): the text tower packed
-// (ref text_encoder.py:54-62 -> base_encoder.py:109-126).  Same rule as k_pool_fwd: mean over the tokens != pad_id of the segment, or its first row.
-__global__ void __launch_bounds__(256) k_pool_packed_fwd(const float* __restrict__ x, const long long* __restrict__ ids, const int* __restrict__ cu, int pad_id,
-                                                         float* __restrict__ pooled, int T_pad, int d, int mode) {
-  const int b = blockIdx.x;
-  const int base = cu[b], L = cu[b + 1] - base;
-  if (L <= 0 || base < 0 || base + L > T_pad) return;
-  __shared__ float s_n[4];
-  float cnt = 0.f;
-  for (int l = threadIdx.x; l < L; l += 256) cnt += (ids[(size_t)base + l] != pad_id);
-  cnt = wave_sum(cnt);
-  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  const float inv_n = 1.0f / (s_n[0] + s_n[1] + s_n[2] + s_n[3]);
-  for (int j = threadIdx.x; j < d; j += 256) {
-    float s = 0.f;
-    if (mode == 1) s = x[(size_t)base * d + j];
-    else {
-      for (int l = 0; l < L; ++l)
-        if (ids[(size_t)base + l] != pad_id) s += x[((size_t)base + l) * d + j];
-      s *= inv_n;
-    }
-    pooled[(size_t)b * d + j] = s;
-  }
-}
-extern "C" int oneprot_pool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, float* pooled, int N, int T_pad, int d, int mode,
-                                       void* stream) {
-  if (!x || !ids || !cu_seqlens || !pooled || N <= 0 || T_pad <= 0 || d <= 0 || mode < 0 || mode > 1) return OP_EINVAL;
-  hipLaunchKernelGGL(k_pool_packed_fwd, dim3(N), dim3(256), 0, (hipStream_t)stream, x, (const long long*)ids, cu_seqlens, pad_id, pooled, T_pad, d, mode);
-  return launch_status();
-}
-
-// its backward: g[cu[b] + l] = dpooled[b] / n_b on the segment's non-pad tokens (mean) or dpooled[b] at l = 0 (CLS), 0 elsewhere; work-group N writes
+// the packed backward: g[cu[b] + l] = dpooled[b] / n_b on the segment's non-pad tokens (mean) or dpooled[b] at l = 0 (CLS), 0 elsewhere; work-group N writes
 // the tail rows [cu[N], T_pad) as exact zeros.  fp32 + bf16 copy.
 __global__ void __launch_bounds__(256) k_pool_packed_bwd(const float* __restrict__ dpooled, const long long* __restrict__ ids, const int* __restrict__ cu,
                                                          int pad_id, float* __restrict__ g, bf16_t* __restrict__ g16, int N, int T_pad, int d, int mode) {
@@ -1018,19 +982,19 @@ __device__ __forceinline__ float ap_block_sum(float v, float* s_red, int lane, i
   return t;
 }
 
-// VAR (oneprot_attnpool_packed_fwd / _bwd): sequence b is rows [cu[b], cu[b+1]) of a packed stream; the LDS is sized for the longest (L = max_len)
+// VAR (oneprot_attnpool_packed_fwd / _bwd): sequence b is rows [cu[b], cu[b+1]) of a packed stream; the LDS is sized for the longest (L = max_len), so the
+// decoded length is clamped to it.  The forward's entry point has no T_pad: its bound on the stream is N * max_len.
 template <bool VAR>
 __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_fwd(const float* __restrict__ x, const long long* __restrict__ ids, int pad_id, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, float* __restrict__ pooled, float* __restrict__ attn, int L, int d,
-                                                                const int* __restrict__ cu = nullptr) {
+                                                                const int* __restrict__ cu = nullptr, int T_bound = 0) {
   extern __shared__ __attribute__((aligned(16))) float s_a[];      // [L rounded to 4] weights, then [groups][d] partial sums
   __shared__ float s_red[AP_WAVES];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  size_t base = (size_t)b * L;
-  if constexpr (VAR) {
-    base = (size_t)cu[b];
-    L = min(cu[b + 1] - cu[b], L);
-  }
+  const RowSeg sg = row_seg<VAR>(b, VAR ? T_bound : L, cu, gridDim.x);      // (grid N: no tail group)
+  if (!sg.ok) return;
+  const size_t base = sg.base;
+  L = min(sg.L, L);
   const float* xb = x + base * d;
   const long long* idb = ids + base;
   const float bs = bias[0];
@@ -1061,15 +1025,14 @@ extern "C" int oneprot_attnpool_fwd(const float* x, const int64_t* ids, int pad_
 template <bool VAR>
 __global__ void __launch_bounds__(AP_WAVES * 64) k_attnpool_bwd(const float* __restrict__ x, const float* __restrict__ attn, const float* __restrict__ w,
                                                                 const float* __restrict__ dpooled, float* __restrict__ dw_part, float* __restrict__ db_part,
-                                                                float* __restrict__ dx, int L, int d, const int* __restrict__ cu = nullptr) {
+                                                                float* __restrict__ dx, int L, int d, const int* __restrict__ cu = nullptr, int T_pad = 0) {
   extern __shared__ __attribute__((aligned(16))) float s_ds[];     // [L rounded to 4], then [groups][d] partial sums
   __shared__ float s_red[AP_WAVES];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  size_t base = (size_t)b * L;
-  if constexpr (VAR) {
-    base = (size_t)cu[b];
-    L = min(cu[b + 1] - cu[b], L);
-  }
+  const RowSeg sg = row_seg<VAR>(b, VAR ? T_pad : L, cu, gridDim.x);
+  if (!sg.ok) return;
+  const size_t base = sg.base;
+  L = min(sg.L, L);
   const float* xb = x + base * d;
   const float* dp = dpooled + (size_t)b * d;
   const float* ab = attn + base;
@@ -1108,8 +1071,9 @@ __global__ void __launch_bounds__(256) k_zero_tail_rows_f32(const int* __restric
 extern "C" int oneprot_attnpool_packed_fwd(const float* x, const int64_t* ids, const int* cu_seqlens, int pad_id, const float* w, const float* bias, float* pooled,
                                            float* attn, int N, int max_len, int d, void* stream) {
   if (!x || !ids || !cu_seqlens || !w || !bias || !pooled || N <= 0 || max_len <= 0 || (d & 3) || ap_lds_bytes(max_len, d) > 60 * 1024) return OP_EINVAL;
+  const long long bound = (long long)N * max_len;       // no T_pad here: N sequences of at most max_len rows end at or before this row
   hipLaunchKernelGGL(k_attnpool_fwd<true>, dim3(N), dim3(AP_WAVES * 64), ap_lds_bytes(max_len, d), (hipStream_t)stream, x, (const long long*)ids, pad_id, w, bias,
-                     pooled, attn, max_len, d, cu_seqlens);
+                     pooled, attn, max_len, d, cu_seqlens, bound < INT32_MAX ? (int)bound : INT32_MAX);
   return launch_status();
 }
 extern "C" int oneprot_attnpool_packed_bwd(const float* x, const float* attn, const int* cu_seqlens, const float* w, const float* dpooled, float* dw, float* db,
@@ -1121,7 +1085,7 @@ extern "C" int oneprot_attnpool_packed_bwd(const float* x, const float* attn, co
   float* part = (float*)workspace;
   if (dx) hipLaunchKernelGGL(k_zero_tail_rows_f32, dim3(64), dim3(256), 0, s, cu_seqlens, N, T_pad, dx, d);
   hipLaunchKernelGGL(k_attnpool_bwd<true>, dim3(N), dim3(AP_WAVES * 64), ap_lds_bytes(max_len, d), s, x, attn, w, dpooled, part, part + (size_t)N * d, dx, max_len, d,
-                     cu_seqlens);
+                     cu_seqlens, T_pad);
   hipLaunchKernelGGL(k_reduce_partials, dim3((d + 255) / 256), dim3(256), 0, s, (const float*)part, dw, N, (size_t)d, 0);
   hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, s, (const float*)(part + (size_t)N * d), db, N, (size_t)1, 0);
   return launch_status();

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from . import layout
 from .esm import EsmTransformer, resolve_config, ModelConfig, recompute_plan
 from .packing import PackedTokens
 
@@ -306,89 +307,19 @@ class _EncodeFn(torch.autograd.Function):
         if need_tr_grad:
             tr._live_apps = getattr(tr, "_live_apps", 0) + 1       # applications awaiting their backward (see backward: overlap guard)
         x, saved = tr.run_layers(ids, save=need_tr_grad)
-        if isinstance(ids, PackedTokens):
-            return _EncodeFn._forward_packed(ctx, enc, tr, ids, x, saved, need_tr_grad, need_any, n_extra, params)
-        B, L = ids.shape
-        d = tr.d
-        dev = ids.device
-        ids = ids.contiguous()
-        pooled = torch.empty(B, d, device=dev)
-        mode = enc.pooling.mode
-        final_ln = getattr(tr, "final_layer_norm", True)
-        mean = rstd = wrow = hidden = attn = None
-        if need_tr_grad:
-            mean, rstd, wrow = (torch.empty(B * L, device=dev) for _ in range(3))
-        if mode == 2:                                   # attention1d: needs the normalised hidden state itself
-            pw = enc.pooling.layer.weight
-            if pw.numel() != d:
-                raise RuntimeError(f"Attention1dPooling was built for hidden size {pw.numel()} but the encoder width is {d} "
-                                   "(the reference hard-codes 1280: base_encoder.py:180)")
-            if final_ln:
-                hidden = torch.empty(B, L, d, device=dev)
-                hip.call("oneprot_lnpool_fwd", x, ids, tr.config.pad_token_id, tr.view("encoder.emb_layer_norm_after.weight"),
-                         tr.view("encoder.emb_layer_norm_after.bias"), pooled, mean, rstd, wrow, None, hidden, B, L, d, tr.config.layer_norm_eps, 0)
-            else:
-                hidden = x.view(B, L, d)
-            attn = torch.empty(B, L, device=dev)
-            hip.call("oneprot_attnpool_fwd", hidden, ids, tr.config.pad_token_id, pw, enc.pooling.layer.bias, pooled, attn, B, L, d)
-        elif final_ln:
-            hip.call("oneprot_lnpool_fwd", x, ids, tr.config.pad_token_id, tr.view("encoder.emb_layer_norm_after.weight"),
-                     tr.view("encoder.emb_layer_norm_after.bias"), pooled, mean, rstd, wrow, None, None, B, L, d, tr.config.layer_norm_eps, mode)
-        else:       # BERT: the last layer's output is already post-LN
-            hip.call("oneprot_pool_fwd", x, ids, tr.config.pad_token_id, pooled, B, L, d, mode)
+        lay = saved["layout"] if saved is not None else layout.of(tr, ids)      # (a frozen tower keeps nothing: the pooling end builds its own, no launch)
+        pooled, fin, pool = lay.pool_fwd(tr, x, enc.pooling, need_tr_grad)
         learn = len(enc.norm) > 1 and enc.norm[1].learnable
         scale_t, dscale_t = enc.norm[1].scale_device() if learn else (None, None)
         scale = 1.0 if learn else enc.logit_scale_value()
         feat, hst = _Head.forward(pooled, enc.proj, scale, need_any, scale_t)
         ctx.enc, ctx.saved, ctx.hst, ctx.scale = enc, saved, hst, scale
         ctx.scale_t, ctx.dscale_t = scale_t, dscale_t
-        ctx.fin = (mean, rstd, wrow)
-        ctx.pool = (hidden, attn) if (mode == 2 and need_any) else None
+        ctx.fin = fin
+        ctx.pool = pool if (enc.pooling.mode == 2 and need_any) else None
         ctx.need_tr_grad = need_tr_grad
         ctx.n_extra, ctx.n_params = n_extra, len(params)
-        ctx.ids = ids
-        return feat
-
-    @staticmethod
-    def _forward_packed(ctx, enc, tr, p, x, saved, need_tr_grad, need_any, n_extra, params):
-        """the pooling end of the forward on a packed stream: final LayerNorm + pooling per segment (pooled [N, d] in segment order); a post-LN tower
-        (BERT, final_layer_norm = False) pools the last layer's output directly"""
-        N, T, d, dev = len(p), p.T_pad, tr.d, p.device
-        cfg = tr.config
-        pooled = torch.empty(N, d, device=dev)
-        mode = enc.pooling.mode
-        final_ln = getattr(tr, "final_layer_norm", True)
-        mean, rstd, wrow = (torch.empty(T, device=dev) for _ in range(3)) if (need_tr_grad and final_ln) else (None, None, None)
-        hidden = attn = None
-        if final_ln:
-            lnw, lnb = tr.view("encoder.emb_layer_norm_after.weight"), tr.view("encoder.emb_layer_norm_after.bias")
-        if mode == 2:
-            pw = enc.pooling.layer.weight
-            if pw.numel() != d:
-                raise RuntimeError(f"Attention1dPooling was built for hidden size {pw.numel()} but the encoder width is {d} "
-                                   "(the reference hard-codes 1280: base_encoder.py:180)")
-            if final_ln:
-                hidden = torch.empty(T, d, device=dev)
-                hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, hidden, N, T, d, cfg.layer_norm_eps, 0)
-            else:
-                hidden = x
-            attn = torch.empty(T, device=dev)
-            hip.call("oneprot_attnpool_packed_fwd", hidden, p.ids, p.cu_seqlens, cfg.pad_token_id, pw, enc.pooling.layer.bias, pooled, attn, N, p.max_len, d)
-        elif not final_ln:
-            hip.call("oneprot_pool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, pooled, N, T, d, mode)
-        else:
-            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, cfg.pad_token_id, lnw, lnb, pooled, mean, rstd, wrow, None, N, T, d, cfg.layer_norm_eps, mode)
-        learn = len(enc.norm) > 1 and enc.norm[1].learnable
-        scale_t, dscale_t = enc.norm[1].scale_device() if learn else (None, None)
-        scale = 1.0 if learn else enc.logit_scale_value()
-        feat, hst = _Head.forward(pooled, enc.proj, scale, need_any, scale_t)
-        ctx.enc, ctx.saved, ctx.hst, ctx.scale = enc, saved, hst, scale
-        ctx.scale_t, ctx.dscale_t = scale_t, dscale_t
-        ctx.fin = (mean, rstd, wrow)
-        ctx.pool = (hidden, attn) if (mode == 2 and need_any) else None
-        ctx.need_tr_grad = need_tr_grad
-        ctx.n_extra, ctx.n_params = n_extra, len(params)
-        ctx.ids = p
+        ctx.lay = lay
         return feat
 
     @staticmethod
@@ -399,26 +330,10 @@ class _EncodeFn(torch.autograd.Function):
         dpooled, hgrads = _Head.backward(dfeat, enc.proj, ctx.scale, ctx.hst, ctx.scale_t)
         extra_grads = []
         dhidden = None
-        mode = enc.pooling.mode
-        packed = isinstance(ctx.ids, PackedTokens)
-        if mode == 2 and packed:
-            hidden, attn = ctx.pool
-            p, (T, d) = ctx.ids, hidden.shape
-            dw, db = torch.empty(d, device=dev), torch.empty(1, device=dev)
-            if ctx.need_tr_grad:
-                dhidden = torch.empty(T, d, device=dev)
-            hip.call("oneprot_attnpool_packed_bwd", hidden, attn, p.cu_seqlens, enc.pooling.layer.weight, dpooled, dw, db, dhidden,
-                     _ws(hip.query("oneprot_attnpool_bwd_workspace", len(p), d), dev), len(p), T, p.max_len, d)
-            extra_grads += [dw.view_as(enc.pooling.layer.weight), db]
-        elif mode == 2:
-            hidden, attn = ctx.pool
-            B, L, d = hidden.shape
-            dw, db = torch.empty(d, device=dev), torch.empty(1, device=dev)
-            if ctx.need_tr_grad:
-                dhidden = torch.empty(B * L, d, device=dev)
-            hip.call("oneprot_attnpool_bwd", hidden, attn, enc.pooling.layer.weight, dpooled, dw, db, dhidden,
-                     _ws(hip.query("oneprot_attnpool_bwd_workspace", B, d), dev), B, L, d)
-            extra_grads += [dw.view_as(enc.pooling.layer.weight), db]
+        mode, lay = enc.pooling.mode, ctx.lay
+        if mode == 2:
+            dw, db, dhidden = lay.attnpool_bwd(ctx.pool, enc.pooling.layer.weight, dpooled, ctx.need_tr_grad)
+            extra_grads += [dw, db]
         if len(enc.norm) > 1 and enc.norm[1].learnable:
             # d/d(log s) [clip(e^l) * xhat] = (dfeat . xhat) * d clip(e^l)/dl, the last factor e^l or 0 (clip active): all on the device
             g = torch.zeros(1, device=dev)
@@ -428,34 +343,11 @@ class _EncodeFn(torch.autograd.Function):
         gflat = None
         if ctx.need_tr_grad:
             saved = ctx.saved
-            B, L, d = saved["B"], saved["L"], tr.d
             # the persistent buffer only for the encoder's single application of a step: with several (seqsim) the first gradient waits inside the
             # autograd engine, invisible as .grad, until the last one has been produced -- each application then gets a tensor of its own
             lone = getattr(tr, "_live_apps", 1) == 1 and not getattr(tr, "_multi_app_step", False)
             gflat = _arena_grad_buffer(tr, dev) if lone else torch.zeros(tr._total, device=dev)
-            mean, rstd, wrow = ctx.fin
-            g = torch.empty(B * L, d, device=dev)
-            g16 = torch.empty(B * L, d, dtype=torch.bfloat16, device=dev)
-            final_ln = getattr(tr, "final_layer_norm", True)
-            if final_ln:
-                lnw, lnb = tr.view("encoder.emb_layer_norm_after.weight", gflat), tr.view("encoder.emb_layer_norm_after.bias", gflat)
-                ws = _ws(hip.query("oneprot_layernorm_bwd_workspace", d), dev)
-            if not final_ln:        # BERT: pooling reads the last layer's output directly
-                if mode == 2:
-                    g.copy_(dhidden.view(B * L, d))
-                elif packed:
-                    hip.call("oneprot_pool_packed_bwd", dpooled, ctx.ids.ids, ctx.ids.cu_seqlens, tr.config.pad_token_id, g, g16, len(ctx.ids), B * L, d, mode)
-                else:
-                    hip.call("oneprot_pool_bwd", dpooled, ctx.ids, tr.config.pad_token_id, g, g16, B, L, d, mode)
-            elif packed and mode != 2:      # dy[t] = dpooled[segment of t] * wrow[t]
-                hip.call("oneprot_lnpool_packed_bwd", dpooled, ctx.ids.cu_seqlens, wrow, saved["x_final"], tr.view("encoder.emb_layer_norm_after.weight"), mean, rstd,
-                         g, g16, lnw, lnb, ws, len(ctx.ids), B * L, d)
-            elif mode == 2:
-                hip.call("oneprot_layernorm_bwd", dhidden, 1, None, 0, saved["x_final"], 0, tr.view("encoder.emb_layer_norm_after.weight"), mean, rstd, None, g, g16,
-                         lnw, lnb, ws, B * L, d, 0)
-            else:
-                hip.call("oneprot_layernorm_bwd", dpooled, 2, wrow, L, saved["x_final"], 0, tr.view("encoder.emb_layer_norm_after.weight"), mean, rstd, None, g, g16,
-                         lnw, lnb, ws, B * L, d, 0)
+            g, g16 = lay.pool_bwd(tr, mode, dpooled, dhidden, ctx.fin, saved["x_final"], gflat)
             saved["x_final"] = None
             # Overlapped data-parallel reduction (oneprot_amd.distributed.GradOverlap): only when this is the encoder's single application in
             # the step and nothing has been accumulated yet -- then the arena gradient is installed as .grad here (autograd gets None for it)

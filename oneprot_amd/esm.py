@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .packing import PackedTokens
+from . import layout
 
 KNOWN_ESM = {   # public facts of the ESM-2 checkpoints (SURVEY.md section 8 header)
     "esm2_t6_8M_UR50D": dict(num_hidden_layers=6, hidden_size=320, intermediate_size=1280),
@@ -478,33 +478,17 @@ class ArenaModule(nn.Module):
         save_file(sd, os.path.join(path, "model.safetensors"))
 
 
-class _PaddedLayout:
-    """The three layout-dependent stages of an ESM tower on a padded [B, L] batch: embedding (token-dropout factor per row), rotary tables (positions
-    0..L-1, the GEMM epilogue reads row % L) and attention (key-padding bias).  Everything else runs row-wise on the B*L rows."""
-    packed = False
-
-    def __init__(self, tr, ids):
-        self.ids = ids.contiguous()
-        self.B, self.L = ids.shape
-        self.T = self.B * self.L
-        self.cos, self.sin = tr._rope(self.L)
+class _EsmPadded(layout.PaddedLayout):
+    """The ESM stages of a padded [B, L] batch: embedding (token-dropout factor per row) and rotary tables (positions 0..L-1, the GEMM epilogue reads
+    row % L).  Everything but these, attention and the pooling end (layout.py) runs row-wise on the B*L rows."""
 
     def embed(self, tr, x):
-        cfg, dev = tr.config, x.device
-        self.key_bias = torch.empty(self.B, self.L, device=dev)
-        hip.call("oneprot_key_padding_bias", self.ids, self.key_bias, self.T, cfg.pad_token_id)
-        self.row_scale = torch.empty(self.B, device=dev)
+        cfg = tr.config
+        self.cos, self.sin = tr._rope(self.L)
+        self.make_key_bias(cfg.pad_token_id)
+        self.row_scale = torch.empty(self.B, device=x.device)
         hip.call("oneprot_esm_embed_fwd", self.ids, tr.view("embeddings.word_embeddings.weight"), x, self.row_scale, self.B, self.L, tr.d, cfg.vocab_size,
                  cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0)
-
-    def attn_fwd(self, q, k, v, ctx, lse, H, hd):
-        hip.call("oneprot_attn_fwd", q, k, v, self.key_bias, ctx, lse, self.B, H, self.L, hd)
-
-    def attn_workspace(self, H, dev):
-        return torch.empty(hip.query("oneprot_attn_bwd_workspace", self.B, H, self.L), dtype=torch.uint8, device=dev)
-
-    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd):
-        hip.call("oneprot_attn_bwd", st["q"], st["k"], st["v"], self.key_bias, st["ctx"], dctx, st["lse"], self.cos, self.sin, q_scale, dqkv, ws, self.B, H, self.L, hd)
 
     def embed_bwd(self, tr, g, dtable):
         cfg, V = tr.config, tr.config.vocab_size
@@ -513,20 +497,9 @@ class _PaddedLayout:
                  1 if cfg.token_dropout else 0, 0)
 
 
-class _PackedLayout:
-    """The same three stages on a packed token stream (oneprot_amd.packing): the row-wise stages see ONE sequence of T_pad rows (B = 1, L = T_pad:
-    q / k / v come out of the QKV GEMM as [H, T_pad, hd], its rotary epilogue reads row t of per-token tables); the embedding counts the
-    token-dropout factor per segment and gathers those tables, attention runs per segment (varlen kernels).  Tail rows are pad tokens: finite
-    activations, exactly zero gradient rows."""
-    packed = True
-
-    def __init__(self, tr, packed):
-        self.p = packed
-        self.ids = packed.ids
-        self.cu = packed.cu_seqlens
-        self.N, self.B, self.L = len(packed), 1, packed.T_pad
-        self.T = packed.T_pad
-        self.work = packed.attn_work()
+class _EsmPacked(layout.PackedLayout):
+    """The same on a packed token stream: q / k / v come out of the QKV GEMM as [H, T_pad, hd], its rotary epilogue reads row t of per-token tables; the
+    embedding counts the token-dropout factor per segment and gathers those tables."""
 
     def embed(self, tr, x):
         cfg, dev = tr.config, x.device
@@ -537,25 +510,11 @@ class _PackedLayout:
         hip.call("oneprot_esm_embed_packed_fwd", self.ids, self.cu, tr.view("embeddings.word_embeddings.weight"), cos_t, sin_t, x, self.tok_scale, self.cos, self.sin,
                  self.N, self.T, self.p.max_len, tr.d, cfg.vocab_size, half, cos_t.shape[0], cfg.pad_token_id, cfg.mask_token_id, 1 if cfg.token_dropout else 0)
 
-    def attn_fwd(self, q, k, v, ctx, lse, H, hd):
-        hip.call("oneprot_attn_varlen_fwd", q, k, v, self.cu, self.work, self.work.shape[0], ctx, lse, self.N, self.T, H, hd)
-
-    def attn_workspace(self, H, dev):
-        return torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, self.T), dtype=torch.uint8, device=dev)
-
-    def attn_bwd(self, st, dctx, q_scale, dqkv, ws, H, hd):
-        hip.call("oneprot_attn_varlen_bwd", st["q"], st["k"], st["v"], self.cu, self.work, self.work.shape[0], st["ctx"], dctx, st["lse"], self.cos, self.sin,
-                 q_scale, dqkv, ws, self.N, self.T, H, hd)
-
     def embed_bwd(self, tr, g, dtable):
         cfg, V = tr.config, tr.config.vocab_size
         ws = torch.empty(hip.query("oneprot_esm_embed_bwd_workspace", self.T, tr.d, V), dtype=torch.uint8, device=g.device)
         hip.call("oneprot_esm_embed_packed_bwd", self.ids, g, self.tok_scale, dtable, ws, self.T, tr.d, V, cfg.pad_token_id, cfg.mask_token_id,
                  1 if cfg.token_dropout else 0, 0)
-
-
-def _layout(tr, ids):
-    return _PackedLayout(tr, ids) if isinstance(ids, PackedTokens) else _PaddedLayout(tr, ids)
 
 
 def _check_recompute_k(k):
@@ -578,6 +537,7 @@ def recompute_plan(n_layers, k):
 class EsmTransformer(ArenaModule):
     """EsmModel replacement.  `add_pooling_layer` only controls whether the (unused) HF pooler parameters exist,
     as in the reference (SequenceEncoder: False, StructTokenEncoder: True)."""
+    layouts = (_EsmPadded, _EsmPacked)      # layout.of(self, ids)
 
     def __init__(self, config, add_pooling_layer=True):
         super().__init__()
@@ -788,7 +748,7 @@ class EsmTransformer(ArenaModule):
         if not ids.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
         self._refresh_bf16()
-        lay = _layout(self, ids)
+        lay = layout.of(self, ids)
         B, L, T = lay.B, lay.L, lay.T
         d, f, dp, n = self.d, self.f, self.dp, self.n_layers
         x = torch.empty(T, d, dtype=torch.float32, device=ids.device)
@@ -1030,19 +990,7 @@ class EsmTransformer(ArenaModule):
         """EsmModel-compatible call returning .last_hidden_state (no autograd; the trainable path is
         oneprot_amd.encoders' fused encode).  Packed input: last_hidden_state is the stream's [T_pad, d] (tail rows: the pad embedding's)."""
         x, _ = self.run_layers(input_ids, save=False)
-        if isinstance(input_ids, PackedTokens):
-            p, d = input_ids, self.d
-            hidden = torch.empty(p.T_pad, d, device=x.device)
-            pooled = torch.empty(len(p), d, device=x.device)
-            hip.call("oneprot_lnpool_packed_fwd", x, p.ids, p.cu_seqlens, self.config.pad_token_id, self.view("encoder.emb_layer_norm_after.weight"),
-                     self.view("encoder.emb_layer_norm_after.bias"), pooled, None, None, None, hidden, len(p), p.T_pad, d, self.config.layer_norm_eps, 0)
-            return _Out(hidden)
-        B, L = input_ids.shape
-        hidden = torch.empty(B, L, self.d, device=x.device)
-        pooled = torch.empty(B, self.d, device=x.device)
-        hip.call("oneprot_lnpool_fwd", x, input_ids.contiguous(), self.config.pad_token_id, self.view("encoder.emb_layer_norm_after.weight"),
-                 self.view("encoder.emb_layer_norm_after.bias"), pooled, None, None, None, None, hidden, B, L, self.d, self.config.layer_norm_eps, 0)
-        return _Out(hidden)
+        return _Out(layout.of(self, input_ids).final_hidden(self, x))
 
     @classmethod
     def from_pretrained(cls, model_name_or_path, config=None, add_pooling_layer=True, **_):

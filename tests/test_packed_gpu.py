@@ -216,6 +216,91 @@ def test_split_kernels_padded_equals_packed(hd, lengths):
     assert torch.equal(dqkv_pk[:n_real], dqkv_pad)
 
 
+@pytest.mark.parametrize("d", [64, 128])
+def test_row_kernels_padded_equals_packed(d):
+    """the row kernels that fork on the layout (embedding, pooling with and without the final LayerNorm) find their rows through the `row_seg` decoder of
+    rowops.hip, one body for both forms (the pooling backward: two kernels with the same arithmetic): the same sequences give the same bits through
+    the padded and the packed entry points (C ABI only).  The value-changing operations are
+    the same in the same order; a padded sequence's pad rows add exact zeros.  Lengths: one row, a partial chunk, 33 = one token into the embedding's
+    second chunk of 32, 130, and 257 = the padded L (no pad row; a 512-thread count loop's second trip has none, a 256-thread one's has one token).
+    d = 64 / 128: 16 / 32 float4 columns for 64 lanes.  <mask> ids in two segments (their own token-dropout factors), one pad id inside a segment."""
+    torch.manual_seed(7 + d)
+    lengths = [1, 7, 33, 130, 257]
+    N, L, T, V, hd, PAD, MASK, eps = len(lengths), 257, 512, 33, 32, 1, 32, 1e-5
+    cu = _cu(lengths)
+    n_real = cu[-1]
+    gen = torch.Generator().manual_seed(11)
+    ids_pad = torch.full((N, L), PAD, dtype=torch.int64)
+    for b, n in enumerate(lengths):
+        ids_pad[b, :n] = torch.randint(4, 24, (n,), generator=gen)
+    ids_pad[2, [3, 20]] = MASK
+    ids_pad[4, torch.randperm(257, generator=gen)[:40]] = MASK
+    ids_pad[3, 50] = PAD                                             # a pad id inside a segment: no pooling weight, not counted
+    ids_pk = torch.full((T,), PAD, dtype=torch.int64)
+    for b, (a, n) in enumerate(zip(cu[:-1], lengths)):
+        ids_pk[a:a + n] = ids_pad[b, :n]
+    ids_pad, ids_pk = ids_pad.to(DEV), ids_pk.to(DEV)
+    cu_d = torch.tensor(cu, dtype=torch.int32, device=DEV)
+    segs = list(zip(range(N), cu[:-1], lengths))
+
+    def same(pk, pad, what):                                         # pk [T, ...] per stream row, pad [N, L, ...]
+        for b, a, n in segs:
+            assert torch.equal(pk[a:a + n], pad[b, :n]), (what, b)
+
+    # ---- embedding: x, the token-dropout factor per token = per row, the gathered rotary rows
+    W = torch.randn(V, d).to(DEV)
+    cos_t, sin_t = (t.to(DEV) for t in _rope_half(1026, hd))
+    x_pad, row_scale = torch.full((N, L, d), 5.0, device=DEV), torch.empty(N, device=DEV)
+    hip.call("oneprot_esm_embed_fwd", ids_pad, W, x_pad, row_scale, N, L, d, V, PAD, MASK, 1)
+    x_pk, tok_scale = torch.full((T, d), 5.0, device=DEV), torch.full((T,), 5.0, device=DEV)
+    cos_o, sin_o = torch.empty(T, hd // 2, device=DEV), torch.empty(T, hd // 2, device=DEV)
+    hip.call("oneprot_esm_embed_packed_fwd", ids_pk, cu_d, W, cos_t, sin_t, x_pk, tok_scale, cos_o, sin_o, N, T, L, d, V, hd // 2, 1026, PAD, MASK, 1)
+    torch.cuda.synchronize()
+    same(x_pk, x_pad, "embed x")
+    assert x_pk[:n_real].abs().max() > 0 and len(set(row_scale.tolist())) == 3       # no <mask>, 2 of 33, 40 of 257
+    for b, a, n in segs:
+        assert (tok_scale[a:a + n] == row_scale[b]).all(), b
+        assert torch.equal(cos_o[a:a + n], cos_t[:n]) and torch.equal(sin_o[a:a + n], sin_t[:n]), b
+        assert (x_pad[b, n:] == 0).all()
+    assert (x_pk[n_real:] == 0).all() and (tok_scale[n_real:] == 0).all()
+
+    # ---- pooling inputs: finite everywhere, as the towers' pad rows are
+    h_pk = torch.randn(T, d, device=DEV)
+    h_pad = torch.randn(N, L, d, device=DEV)
+    for b, a, n in segs:
+        h_pad[b, :n] = h_pk[a:a + n]
+    dpooled = torch.randn(N, d, device=DEV)
+    gamma, beta = (1 + 0.1 * torch.randn(d)).to(DEV), (0.1 * torch.randn(d)).to(DEV)
+    for mode in (0, 1):
+        # pooling without a LayerNorm, forward and backward (fp32 and the bf16 copy)
+        p_pad, p_pk = torch.empty(N, d, device=DEV), torch.empty(N, d, device=DEV)
+        hip.call("oneprot_pool_fwd", h_pad, ids_pad, PAD, p_pad, N, L, d, mode)
+        hip.call("oneprot_pool_packed_fwd", h_pk, ids_pk, cu_d, PAD, p_pk, N, T, d, mode)
+        g_pad, g_pk = torch.full((N, L, d), 9.0, device=DEV), torch.full((T, d), 9.0, device=DEV)
+        g16_pad, g16_pk = torch.empty(N, L, d, dtype=torch.bfloat16, device=DEV), torch.empty(T, d, dtype=torch.bfloat16, device=DEV)
+        hip.call("oneprot_pool_bwd", dpooled, ids_pad, PAD, g_pad, g16_pad, N, L, d, mode)
+        hip.call("oneprot_pool_packed_bwd", dpooled, ids_pk, cu_d, PAD, g_pk, g16_pk, N, T, d, mode)
+        # final LayerNorm + pooling
+        q_pad, q_pk = torch.empty(N, d, device=DEV), torch.empty(N, d, device=DEV)
+        st_pad = [torch.empty(N, L, device=DEV) for _ in range(3)]
+        st_pk = [torch.full((T,), 9.0, device=DEV) for _ in range(3)]
+        hid_pad, hid_pk = torch.empty(N, L, d, device=DEV), torch.empty(T, d, device=DEV)
+        hip.call("oneprot_lnpool_fwd", h_pad, ids_pad, PAD, gamma, beta, q_pad, *st_pad, None, hid_pad, N, L, d, eps, mode)
+        hip.call("oneprot_lnpool_packed_fwd", h_pk, ids_pk, cu_d, PAD, gamma, beta, q_pk, *st_pk, hid_pk, N, T, d, eps, mode)
+        torch.cuda.synchronize()
+        assert torch.isfinite(p_pad).all() and torch.equal(p_pk, p_pad), ("pool_fwd", mode)
+        same(g_pk, g_pad, ("pool_bwd", mode))
+        same(g16_pk, g16_pad, ("pool_bwd bf16", mode))
+        assert g_pad[3, 50].abs().max() == 0 and (g_pad[3, 49].abs().max() > 0) == (mode == 0)
+        assert (g_pk[n_real:] == 0).all() and (g16_pk[n_real:] == 0).all()
+        assert all((g_pad[b, n:] == 0).all() for b, a, n in segs)
+        assert torch.isfinite(q_pad).all() and torch.equal(q_pk, q_pad), ("lnpool pooled", mode)
+        for nm, s_pk, s_pad in zip(("mean", "rstd", "wrow"), st_pk, st_pad):
+            same(s_pk, s_pad, ("lnpool " + nm, mode))
+        same(hid_pk, hid_pad, ("lnpool hidden", mode))
+        assert (st_pk[2][n_real:] == 0).all() and st_pk[2][cu[3] + 50] == 0      # wrow: the tail and the pad id weigh nothing
+
+
 # ------------------------------------------------------------------------------------------------------------------ 3. packed embedding
 def test_packed_embedding_forward_backward():
     torch.manual_seed(4)

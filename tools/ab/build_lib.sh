@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")"
 CS=../../oneprot_amd/csrc
 name="$1"; units="$2"; shift 2
-ALL="rowops gemm_nt gemm_nt8 gemm_nt_ln gemm_tn sgemm attention featops retrieval"
+ALL="rowops gemm_nt gemm_nt8 gemm_nt_ln gemm_tn sgemm attention featops retrieval msa"
 objs=""; pids=""
 for u in $ALL; do
   src=""
