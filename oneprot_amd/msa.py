@@ -117,6 +117,8 @@ class MsaTransformer(ArenaModule):
         self._finish_arena()
         self.reset_parameters()
         self.capture = None                             # test hook: a list that receives (kind, layer, ctx clone) of every attention output
+        self.stages = None                              # second test hook: a list that receives (name, layer, clone): the residual stream on entry to every block ("row" /
+                                                        # "col" / "ffn") and after the last layer ("out"), and what each attention read ("row.qkv" / "col.qkv"; R = 1: "col.v")
         for p in self.parameters():
             p.requires_grad = False
         self.eval()
@@ -183,6 +185,8 @@ class MsaTransformer(ArenaModule):
         for i in range(self.n_layers):
             for blk in _BLOCKS:
                 p = f"layers.{i}.{blk}."
+                if self.stages is not None:
+                    self.stages.append((blk[:3], i, x.clone()))
                 hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
                 if blk == "column_self_attention" and R == 1:       # one row: softmax over a single key (fair-esm ColumnSelfAttention.forward)
                     self._gemm(h, self._w16(p + "layer.v_proj.weight"), T, d, d, hip.EPI_BF16, self.view(p + "layer.v_proj.bias"), ctx)
@@ -199,11 +203,18 @@ class MsaTransformer(ArenaModule):
                         hip.call("oneprot_msa_col_attn", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5)
                 if self.capture is not None:
                     self.capture.append((blk[:3], i, ctx.clone()))
+                if self.stages is not None:             # the attention kernels leave qkv as they found it
+                    one_row = blk == "column_self_attention" and R == 1
+                    self.stages.append((blk[:3] + (".v" if one_row else ".qkv"), i, (ctx if one_row else qkv).clone()))
                 self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, self.view(p + "layer.out_proj.bias"), x, aux=x)
             p = f"layers.{i}.feed_forward_layer."
+            if self.stages is not None:
+                self.stages.append(("ffn", i, x.clone()))
             hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
             self._gemm(h, self._w16(p + "layer.fc1.weight"), T, f, d, hip.EPI_BIAS_GELU, self.view(p + "layer.fc1.bias"), u)
             self._gemm(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, self.view(p + "layer.fc2.bias"), x, aux=x)
+        if self.stages is not None:
+            self.stages.append(("out", self.n_layers, x.clone()))
         return x, None
 
     @torch.no_grad()

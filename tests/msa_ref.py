@@ -72,16 +72,21 @@ def row_context(S, v, pad_mask, H, p_round=None):
     return torch.einsum("bhij,brjhc->brihc", P, v.reshape(B, R, L, H, D // H)).reshape(B, R, L, D)
 
 
+def col_scores(q, k, H):
+    """S [B, H, L, R, R] of the column attention (before the key mask): S[b, h, l, i, j] = hd^-1/2 q[b, i, l, h] . k[b, j, l, h]"""
+    B, R, L, D = q.shape
+    hd = D // H
+    return torch.einsum("bilhc,bjlhc->bhlij", q.reshape(B, R, L, H, hd) * hd ** -0.5, k.reshape(B, R, L, H, hd))
+
+
 def col_context(q, k, v, pad_mask, H, general=False):
     """ctx [B, R, L, H * hd] of the column attention; R = 1 takes the published shortcut (ctx = v) unless `general`"""
     B, R, L, D = q.shape
     hd = D // H
     if R == 1 and not general:
         return v
-    q5, k5, v5 = (t.reshape(B, R, L, H, hd) for t in (q, k, v))
-    S = torch.einsum("bilhc,bjlhc->bhlij", q5 * hd ** -0.5, k5)
-    S = S.masked_fill(pad_mask.permute(0, 2, 1)[:, None, :, None, :], -10000.0)
-    return torch.einsum("bhlij,bjlhc->bilhc", torch.softmax(S, dim=-1), v5).reshape(B, R, L, D)
+    S = col_scores(q, k, H).masked_fill(pad_mask.permute(0, 2, 1)[:, None, :, None, :], -10000.0)
+    return torch.einsum("bhlij,bjlhc->bilhc", torch.softmax(S, dim=-1), v.reshape(B, R, L, H, hd)).reshape(B, R, L, D)
 
 
 def layer(x, sd, i, pad_mask, H, taps=None):
@@ -103,6 +108,54 @@ def layer(x, sd, i, pad_mask, H, taps=None):
     a = p + "feed_forward_layer."
     h = _ln(x, sd, a + "layer_norm")
     return x + _lin(F.gelu(_lin(h, sd, a + "layer.fc1")), sd, a + "layer.fc2")
+
+
+# The blocks of `layer` one stage at a time, each from that stage's own input (the per-stage tower test hands them what the tower captured).  `rnd`: optional
+# rounding applied where the tower holds a bf16 tensor (LayerNorm output, GELU output); chained without it they are `layer` (tests/test_msa_cpu.py).
+def qkv_proj(x, sd, i, blk, rnd=None):
+    """x [.., d] -> the q | k | v projections of LN(x) side by side [.., 3 d]: one product with the stacked weights; blk: row_self_attention / column_self_attention"""
+    a = f"layers.{i}.{blk}."
+    h = _ln(x, sd, a + "layer_norm")
+    h = h if rnd is None else rnd(h)
+    w = torch.cat([sd[a + f"layer.{n}_proj.weight"] for n in "qkv"])
+    return h @ w.T + torch.cat([sd[a + f"layer.{n}_proj.bias"] for n in "qkv"])
+
+
+def attn_out(x, ctx, sd, i, blk):
+    return x + _lin(ctx, sd, f"layers.{i}.{blk}.layer.out_proj")
+
+
+def ffn(x, sd, i, rnd=None):
+    a = f"layers.{i}.feed_forward_layer."
+    h = _ln(x, sd, a + "layer_norm")
+    u = F.gelu(_lin(h if rnd is None else rnd(h), sd, a + "layer.fc1"))
+    return x + _lin(u if rnd is None else rnd(u), sd, a + "layer.fc2")
+
+
+GEMM_WEIGHTS = ("_proj.weight", "fc1.weight", "fc2.weight")
+
+
+def tower_operands(sd, rnd, dtype=torch.float64):
+    """the state dict as the tower reads it: the GEMM weights through `rnd` (its bf16 mirror), LayerNorms, biases and tables as they are"""
+    return {k: (rnd(v.detach().cpu()) if k.endswith(GEMM_WEIGHTS) else v.detach().cpu().to(dtype)) for k, v in sd.items() if v.is_floating_point()}
+
+
+def ffn_rounding_self_difference(tokens, sd, heads, rnd, pad=PAD):
+    """The reference against itself: per layer, max |ffn with `rnd` on the LayerNorm and GELU outputs - ffn exact| from the same FFN input, along the forward with
+    `rnd` wherever the tower holds a bf16 tensor.  What a bf16 tie flip between an fp32 and an fp64 LayerNorm can at most do to the FFN stage is a fraction of it."""
+    sd = tower_operands(sd, rnd)
+    n_layers = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("layers."))
+    pad_mask = tokens.eq(pad)
+    x, out = embed(tokens, sd, pad), []
+    for i in range(n_layers):
+        q, k, v = rnd(qkv_proj(x, sd, i, "row_self_attention", rnd)).chunk(3, dim=-1)
+        x = attn_out(x, rnd(row_context(row_scores(q, k, pad_mask, heads), v, pad_mask, heads)), sd, i, "row_self_attention")
+        q, k, v = rnd(qkv_proj(x, sd, i, "column_self_attention", rnd)).chunk(3, dim=-1)
+        x = attn_out(x, rnd(col_context(q, k, v, pad_mask, heads)), sd, i, "column_self_attention")
+        y = ffn(x, sd, i, rnd)
+        out.append(float((y - ffn(x, sd, i)).abs().max()))
+        x = y
+    return out
 
 
 def forward(tokens, sd, heads, dtype=torch.float64, pad=PAD, taps=None):

@@ -62,6 +62,43 @@ def test_row_scale_uses_the_padded_row_count():
     assert torch.allclose(MR.row_scores(q, k, pad3, 2) * math.sqrt(3), MR.row_scores(q[:, :2], k[:, :2], pad2, 2) * math.sqrt(2), rtol=1e-12, atol=1e-12)
 
 
+@pytest.mark.parametrize("R", [3, 1])
+def test_stage_helpers_chained_reproduce_forward(R):
+    """qkv_proj -> row / column context -> attn_out, ffn: the helpers of the per-stage tower test, chained in fp64, are MR.forward (R = 1: the column shortcut)"""
+    tr = _tower()
+    with torch.no_grad():
+        tr.flat.normal_(0.0, 0.08)
+    sd = {k: v.detach().to(F64) for k, v in tr.state_dict().items()}
+    g = torch.Generator().manual_seed(8)
+    tok = torch.randint(4, 30, (2, R, 11), generator=g)
+    tok[:, :, 0] = 0
+    tok[1, :, 8:] = 1
+    tok[0, R - 1, 4] = 1
+    pad = tok.eq(1)
+    x = MR.embed(tok, sd)
+    for i in range(2):
+        q, k, v = MR.qkv_proj(x, sd, i, "row_self_attention").chunk(3, dim=-1)
+        x = MR.attn_out(x, MR.row_context(MR.row_scores(q, k, pad, 2), v, pad, 2), sd, i, "row_self_attention")
+        q, k, v = MR.qkv_proj(x, sd, i, "column_self_attention").chunk(3, dim=-1)
+        x = MR.attn_out(x, MR.col_context(q, k, v, pad, 2), sd, i, "column_self_attention")
+        x = MR.ffn(x, sd, i)
+    x = MR._ln(x, sd, "emb_layer_norm_after")
+    ref = MR.forward(tok, sd, 2)
+    assert torch.allclose(x, ref, rtol=1e-12, atol=1e-12) and float(ref.abs().max()) > 0.1
+
+
+def test_ffn_gate_of_the_grouped_stage_test_is_the_measured_one(tmp_path):
+    """tests/test_msa_edges_gpu.py runs the FFN stage of its grouped tower test at four times the reference's own difference (bf16-rounded LayerNorm and GELU
+    outputs against exact ones): that figure, recomputed here from the same file of weights and the same tokens"""
+    from oneprot_amd.msa import MsaTransformer
+    from tests import test_msa_edges_gpu as ME
+    from tests import test_msa_gpu as MG
+    tr = MsaTransformer.from_pretrained(MG._checkpoint(tmp_path))
+    shape, lens, rows, seed = ME.GROUPED
+    diff = MR.ffn_rounding_self_difference(MG._tokens(*shape, lens, rows, seed), tr.state_dict(), tr.H, ME.bf)
+    assert len(diff) == 2 and diff[0] > diff[1] and 0.995 * ME.FFN_SELF_DIFFERENCE_GROUPED < diff[0] <= ME.FFN_SELF_DIFFERENCE_GROUPED
+
+
 # ---------------------------------------------------------------------------------------------------------------- surface
 def test_msa_encoder_signature_is_the_reference_one():
     from src.models.components.msa_encoder import MsaEncoder

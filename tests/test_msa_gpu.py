@@ -107,7 +107,7 @@ def test_row_scores_and_context_vs_fp64(shape, lens, rows, holes):
 
 
 @pytest.mark.parametrize("L", [1, 33])
-@pytest.mark.parametrize("R", [2, 3, 16, 17, 50, 64, 65, 128])
+@pytest.mark.parametrize("R", [2, 3, 16, 17, 31, 32, 33, 50, 64, 65, 96, 97, 127, 128])       # every edge of R rounded up to 16 (query tiles) and to 32 (LDS fill, P.V trips)
 def test_col_attn_vs_fp64(R, L):
     B, H = 2, 2
     ids = _ids(B, R, L, [L, L], [R - R // 3, max(R // 2, 1)])             # trailing rows fully padded
@@ -170,20 +170,21 @@ def test_embed_vs_fp64():
 ARCH = dict(layers=2, embed_dim=128, ffn_embed_dim=256, attention_heads=2, max_positions=160, embed_positions_msa=True)
 
 
-def _checkpoint(tmp_path, seed=0):
-    """a random 2-layer model written as a fair-esm file (encoder.-prefixed keys, row / column swapped), so that the encoder is built through the loader"""
+def _checkpoint(tmp_path, seed=0, arch=ARCH, name="msa_tiny.pt", std=0.08):
+    """a random model (by default the 2-layer ARCH) written as a fair-esm file (encoder.-prefixed keys, row / column swapped), so that the encoder is built
+    through the loader"""
     from oneprot_amd.msa import MsaTransformer, config_from_args
-    path = os.path.join(str(tmp_path), "msa_tiny.pt")
+    path = os.path.join(str(tmp_path), name)
     if not os.path.exists(path):
         torch.manual_seed(seed)
-        tr = MsaTransformer(config_from_args(ARCH))
+        tr = MsaTransformer(config_from_args(arch))
         with torch.no_grad():
-            tr.flat.normal_(0.0, 0.08)
+            tr.flat.normal_(0.0, std)
             for k in tr._spec:
                 if k.endswith("layer_norm.weight") or k.startswith("emb_layer_norm") and k.endswith("weight"):
                     tr.view(k).add_(1.0)
         sw = lambda k: k.replace("row", "\0").replace("column", "row").replace("\0", "column")
-        torch.save({"args": argparse.Namespace(arch="msa_transformer", **ARCH), "model": {"encoder." + sw(k): v.clone() for k, v in tr.state_dict().items()}}, path)
+        torch.save({"args": argparse.Namespace(arch="msa_transformer", **arch), "model": {"encoder." + sw(k): v.clone() for k, v in tr.state_dict().items()}}, path)
     return path
 
 
