@@ -354,7 +354,8 @@ int oneprot_sim_topk(const float* Q, const float* Db, int nq, int N, int D, int 
                      void* stream);
 
 /* ---------------- MSA Transformer tower (ref msa_encoder.py:36: `self.transformer(tokens, repr_layers=[12])`, fair-esm's MSATransformer) ----------
- * Forward only, eval mode (the reference freezes the tower, msa_encoder.py:30-32).  fair-esm is not part of this tree: the call sites below are named by
+ * Forward only (the reference freezes the tower, msa_encoder.py:30-32); eval mode, and the two *_dropout calls at the end for the train-mode
+ * forward.  fair-esm is not part of this tree: the call sites below are named by
  * their published functions, and parity with a fair-esm run is UNPINNED (the tests compare against tests/msa_ref.py, an fp64 restatement).
  * Tokens int64 [B, R, L], numbered t = (b * R + r) * L + l, T = B * R * L.  qkv: bf16 [T, 3 * H * 64] = q | k | v of one oneprot_gemm_bf16_nt
  * (ONEPROT_EPI_BF16 + bias) on the stacked projection weights, head h in columns h * 64 .. h * 64 + 63 of each third.  key_bias: fp32 [T] from
@@ -382,6 +383,22 @@ int oneprot_msa_row_context(const float* S, const void* qkv, const float* key_bi
    over the rows j whose token (j, l) is not padding, ctx = P v; scale = hd^-1/2; a query whose keys are all masked gets 0.  A larger R returns -1; R = 1 is
    out_proj(v_proj(x)) on the host, as published. */
 int oneprot_msa_col_attn(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, void* stream);
+/* Train-mode twins of the two calls above: fair-esm applies nn.Dropout(attention_dropout) to the probabilities between the softmax and the product
+   with V, and the reference runs its frozen tower in train mode during training (Lightning's module.train() undoes msa_encoder.py:30).  The mask is the
+   per-element hash of oneprot_attn_dropout_keep (same rule, same thr16 / scale, same refusals of p: p < 0, NaN and p >= 1 return -1; p < 2^-17 is no dropout at
+   all and equals the undropped call bit for bit); a dropped probability is 0, a kept one bf16(p_ij * 65536 / (65536 - thr16)), scaled in fp32 before its one
+   rounding; row maximum and sum are those of the undropped softmax.  Our generator, not torch's: the same distribution as nn.Dropout, another draw.
+   oneprot_msa_row_context_dropout (fair-esm RowSelfAttention.compute_attention_update: `attn_probs = self.dropout_module(attn_probs)`): the attention is
+   tied, so there is ONE mask element per (b, h, i, j) for all R rows, keep(q = i, k = j, bh = (b_first + b) * H + h) -- in the layout of
+   oneprot_attn_dropout_keep(keep, B_total, H, L, ...): keep[b_first + b, h, i, j].  b_first is the place of the call's first MSA in the whole batch, so
+   that a batch run in groups of whole MSAs drops what the one call would; b_first < 0 or (b_first + B) * H > 65535 returns -1.
+   oneprot_msa_col_attn_dropout (fair-esm ColumnSelfAttention.compute_attention_update, R > 1: `attn_probs = self.dropout_module(attn_probs)`): one mask
+   element per (b, h, l, i, j), keep(q = i, k = j, bh = (b * H + h) * L + l) -- oneprot_attn_dropout_keep(keep, B * H * L, 1, R, ...) viewed as
+   [B, H, L, R, R]; L <= ONEPROT_MSA_MAX_LEN.  R = 1 returns -1 as in the undropped call: the published shortcut has no attention dropout. */
+int oneprot_msa_row_context_dropout(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B, int R,
+                                    int L, int H, int hd, int b_first, float p, uint64_t seed, uint64_t stream_id, void* stream);
+int oneprot_msa_col_attn_dropout(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, float p, uint64_t seed,
+                                 uint64_t stream_id, void* stream);
 
 #ifdef __cplusplus
 }

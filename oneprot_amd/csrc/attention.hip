@@ -16,6 +16,7 @@
 //   backward dK/dV kernel puts the key on the lane: S = Q K^T, dP = dO V^T, dV^T += dO^T P, dK^T += Q^T dS.
 // Tiles in LDS are row-major with a 16-byte-chunk XOR swizzle that keeps the ds_read_b128 row reads conflict-free.
 #include "common.h"
+#include "attn_drop.h"
 #include "sched_ws.h"
 #include "../../include/oneprot_hip.h"
 #include <float.h>
@@ -154,12 +155,7 @@ __device__ __forceinline__ void decode_block(int nblk_per_bh, int nbh, int& bh, 
 // >= thr16 = round(p * 65536), kept probabilities scaled by 65536 / (65536 - thr16).  The row sum, the log-sum-exp and delta = rowsum(dO * O) are
 // untouched by the mask.  oneprot_attn_dropout_keep writes the mask out for tests.  (The hidden-state dropouts use Philox, featops.hip; here a
 // Philox call per element would cost ten times the tile's own vector work.)
-struct AttnDrop { unsigned thr16, s0, s1; float scale; };
-__device__ __forceinline__ bool attn_keep(unsigned qi, unsigned ki, unsigned bh, const AttnDrop& dr) {
-  unsigned x = (qi * 0x9E3779B1u) ^ (ki * 0x85EBCA77u + dr.s0) ^ (bh * 0xC2B2AE3Du + dr.s1);
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return (x >> 16) >= dr.thr16;
-}
+// AttnDrop, attn_keep and attn_drop_make: attn_drop.h (msa.hip applies the same rule to the axial attentions).
 // the 16 elements of a 32 x 32 accumulator tile a lane holds: index 8 * (e >> 2) + 4 * h + (e & 3) along the tile's row axis
 __device__ __forceinline__ unsigned attn_keep_bits_q(int qidx, int key0, int h, int bh, const AttnDrop& dr) {      // lane = query, rows = keys
   unsigned bits = 0;
@@ -172,15 +168,6 @@ __device__ __forceinline__ unsigned attn_keep_bits_k(int kidx, int q0, int h, in
 #pragma unroll
   for (int e = 0; e < 16; ++e) bits |= (attn_keep((unsigned)(q0 + 8 * (e >> 2) + 4 * h + (e & 3)), (unsigned)kidx, (unsigned)bh, dr) ? 1u : 0u) << e;
   return bits;
-}
-static int attn_drop_make(float p, uint64_t seed, uint64_t stream_id, AttnDrop& dr) {
-  if (!(p >= 0.f) || !(p < 1.f)) return OP_EINVAL;
-  dr.thr16 = (unsigned)(p * 65536.f + 0.5f);
-  if (dr.thr16 >= 65536u) return OP_EINVAL;
-  dr.scale = 65536.f / (float)(65536u - dr.thr16);
-  const uint64_t m = (seed ^ (stream_id * 0x9E3779B97F4A7C15ull)) * 0xD6E8FEB86659FD93ull;
-  dr.s0 = (unsigned)m; dr.s1 = (unsigned)(m >> 32) ^ (unsigned)(stream_id * 0x2545F491u);
-  return OP_OK;
 }
 
 // One work-group's share of a split kernel: one (sequence, head) and one 128-row block of it.  The padded kernels fill it from decode_block, the

@@ -10,7 +10,7 @@ PIDS=""
 ASM=""       # units whose .s is already being written: the loop after this one must not start a second writer of the same .s.tmp
 for s in $SRCS; do
   o="${s%.hip}.o"
-  if [ ! -f "$o" ] || [ ! -f "$o.remarks" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ gemm_epi.h -nt "$o" ] || [ gemm_epi8.h -nt "$o" ] || [ sched_ws.h -nt "$o" ] || [ ../../include/oneprot_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ ! -f "$o.remarks" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ attn_drop.h -nt "$o" ] || [ gemm_epi.h -nt "$o" ] || [ gemm_epi8.h -nt "$o" ] || [ sched_ws.h -nt "$o" ] || [ ../../include/oneprot_hip.h -nt "$o" ]; then
     ( if hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-value -Rpass-analysis=kernel-resource-usage -c "$s" -o "$o.tmp" 2> "$o.remarks.tmp"; then
         mv "$o.tmp" "$o"; mv "$o.remarks.tmp" "$o.remarks"
       else

@@ -17,7 +17,17 @@
 // Every reduction runs in a fixed order inside one work-group (no split along K chosen by the grid, no atomics): an MSA's result does not depend on
 // what else is in the batch.  Masked keys are excluded (probability 0) instead of biased by -10000: the two differ only where every key of a query is
 // masked, i.e. at padded positions, which then hold 0 -- finite, as the next layer's tied scores need.
+//
+// TRAIN-MODE DROPOUT (oneprot_msa_row_context_dropout, oneprot_msa_col_attn_dropout): fair-esm applies nn.Dropout(attention_dropout) to the probabilities
+// of both attentions between the softmax and the product with V; the reference runs the frozen tower that way in every training step (Lightning's
+// module.train() undoes msa_encoder.py:30).  The DROP = true instantiations of k_msa_row_softmax and k_msa_col_attn apply the per-element hash mask of
+// attn_drop.h to the normalised probability in fp32, before its one rounding to bf16; maximum and sum are those of the undropped softmax.
+//   row    one mask element per (b, h, i, j), shared by the R rows (the attention is tied):  attn_keep(q = i, k = j, bh = (b_first + b) * H + h),
+//          b_first = the MSA's place in the batch when the host hands over a group of whole MSAs: the grouping cannot change a bit
+//   column one per (b, h, l, i, j):  attn_keep(q = i, k = j, bh = (b * H + h) * L + l)   (< 2^26: B * H <= 65535, L <= 1024)
+// The DROP = false instantiations are the kernels as they were.
 #include "common.h"
+#include "attn_drop.h"
 #include "../../include/oneprot_hip.h"
 #include <float.h>
 
@@ -151,7 +161,9 @@ __global__ void __launch_bounds__(256) k_msa_row_scores(const bf16_t* __restrict
 //   Vt bf16 [B, H, R, 64, Lp]   V transposed (channel x key, zeros past L): the product sums over V's row index, so its fragments must run along the keys
 // and then ctx^T = Vt . P^T as a plain tile product with both fragments loaded straight from global memory (16 bytes per lane).
 #define RC_MAXL ONEPROT_MSA_MAX_LEN
-__global__ void __launch_bounds__(256) k_msa_row_softmax(const float* __restrict__ S, const float* __restrict__ kb, bf16_t* __restrict__ P, int R, int L, int Lp, int H) {
+template <bool DROP>
+__global__ void __launch_bounds__(256) k_msa_row_softmax(const float* __restrict__ S, const float* __restrict__ kb, bf16_t* __restrict__ P, int R, int L, int Lp, int H,
+                                                         int b_first, const AttnDrop dr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave, bh = blockIdx.y, b = bh / H;
   if (i >= L) return;                                    // whole wave; the kernel has no barrier
@@ -179,7 +191,12 @@ __global__ void __launch_bounds__(256) k_msa_row_softmax(const float* __restrict
 #pragma unroll
   for (int t = 0; t < RC_MAXL / 64; ++t) {
     const int j = lane + 64 * t;
-    if (j < Lp) Pi[j] = f2bf(v[t] * inv);
+    if (DROP) {                                            // fair-esm RowSelfAttention: dropout_module(attn_probs); one mask for all R rows
+      const bool keep = attn_keep((unsigned)i, (unsigned)j, (unsigned)(b_first * H + bh), dr);
+      if (j < Lp) Pi[j] = keep ? f2bf(v[t] * inv * dr.scale) : (bf16_t)0;
+    } else {
+      if (j < Lp) Pi[j] = f2bf(v[t] * inv);
+    }
   }
 }
 
@@ -248,8 +265,9 @@ __global__ void __launch_bounds__(256) k_msa_row_pv(const bf16_t* __restrict__ P
 // of 32 rows) sits transposed in LDS for all four waves; a wave's probabilities go through its own LDS rows to become the B operand of ctx^T = V^T . P^T.
 #define CA_MAXR 128
 #define CA_S (CA_MAXR + 8)          // bf16 per LDS row: 272 bytes, 16-byte aligned
+template <bool DROP>
 __global__ void __launch_bounds__(256) k_msa_col_attn(const bf16_t* __restrict__ qkv, const float* __restrict__ kb, bf16_t* __restrict__ ctx, int R, int L, int H,
-                                                      float scale) {
+                                                      float scale, const AttnDrop dr) {
   __shared__ __attribute__((aligned(16))) bf16_t sV[64 * CA_S];
   __shared__ __attribute__((aligned(16))) bf16_t sP[4][16 * CA_S];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, g = lane >> 4, kq = g * 8;
@@ -306,7 +324,14 @@ __global__ void __launch_bounds__(256) k_msa_col_attn(const bf16_t* __restrict__
         const float inv = sum > 0.f ? 1.f / sum : 0.f;     // every key masked: probabilities 0, context 0 (finite)
 #pragma unroll
         for (int nt = 0; nt < CA_MAXR / 16; ++nt)
-          if (nt * 16 < Rp) sPw[(g * 4 + reg) * CA_S + nt * 16 + fr] = f2bf(s[nt][reg] * inv);
+          if (nt * 16 < Rp) {
+            if (DROP) {                                    // fair-esm ColumnSelfAttention: dropout_module(attn_probs), one mask element per (b, h, l, i, j)
+              const bool keep = attn_keep((unsigned)(t * 16 + g * 4 + reg), (unsigned)(nt * 16 + fr), (unsigned)((b * H + h) * L + l), dr);
+              sPw[(g * 4 + reg) * CA_S + nt * 16 + fr] = keep ? f2bf(s[nt][reg] * inv * dr.scale) : (bf16_t)0;
+            } else {
+              sPw[(g * 4 + reg) * CA_S + nt * 16 + fr] = f2bf(s[nt][reg] * inv);
+            }
+          }
       }
     }
     __syncthreads();
@@ -361,8 +386,11 @@ extern "C" size_t oneprot_msa_row_context_workspace(int B, int R, int L, int H) 
   return msa_p_bytes(B, L, H) + (size_t)B * H * R * 64 * ((L + 31) & ~31) * sizeof(bf16_t);
 }
 
-extern "C" int oneprot_msa_row_context(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B, int R,
-                                       int L, int H, int hd, void* stream) {
+static const AttnDrop kNoDrop = AttnDrop{0u, 0u, 0u, 1.0f};
+
+// the three launches of the tied row context; dr = null: the undropped softmax
+static int msa_row_context_launch(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B, int R, int L, int H,
+                                  int hd, int b_first, const AttnDrop* dr, void* stream) {
   if (!S || !qkv || !key_bias || !ctx || !workspace || !msa_shape_ok(B, R, L, H, hd) || L > ONEPROT_MSA_MAX_LEN || R > 65535 ||
       (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)workspace) & 15))
     return OP_EINVAL;
@@ -371,18 +399,44 @@ extern "C" int oneprot_msa_row_context(const float* S, const void* qkv, const fl
   bf16_t* P = (bf16_t*)workspace;
   bf16_t* Vt = (bf16_t*)((char*)workspace + msa_p_bytes(B, L, H));
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_msa_row_softmax, dim3((unsigned)((L + 3) / 4), (unsigned)(B * H)), dim3(256), 0, s, S, key_bias, P, R, L, Lp, H);
+  const dim3 gs((unsigned)((L + 3) / 4), (unsigned)(B * H));
+  if (dr) hipLaunchKernelGGL(k_msa_row_softmax<true>, gs, dim3(256), 0, s, S, key_bias, P, R, L, Lp, H, b_first, *dr);
+  else hipLaunchKernelGGL(k_msa_row_softmax<false>, gs, dim3(256), 0, s, S, key_bias, P, R, L, Lp, H, 0, kNoDrop);
   hipLaunchKernelGGL(k_msa_v_transpose, dim3((unsigned)(Lp / 32), (unsigned)R, (unsigned)(B * H)), dim3(256), 0, s, (const bf16_t*)qkv, Vt, R, L, Lp, H);
   hipLaunchKernelGGL(k_msa_row_pv, dim3((unsigned)((L + 63) / 64), (unsigned)((R + 3) / 4), (unsigned)(B * H)), dim3(256), 0, s, (const bf16_t*)P, (const bf16_t*)Vt,
                      (bf16_t*)ctx, R, L, Lp, H);
   return launch_status();
 }
 
-extern "C" int oneprot_msa_col_attn(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, void* stream) {
+extern "C" int oneprot_msa_row_context(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B, int R,
+                                       int L, int H, int hd, void* stream) {
+  return msa_row_context_launch(S, qkv, key_bias, ctx, workspace, workspace_bytes, B, R, L, H, hd, 0, nullptr, stream);
+}
+
+extern "C" int oneprot_msa_row_context_dropout(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, int B,
+                                               int R, int L, int H, int hd, int b_first, float p, uint64_t seed, uint64_t stream_id, void* stream) {
+  AttnDrop dr;
+  if (attn_drop_make(p, seed, stream_id, dr) != OP_OK || b_first < 0 || B <= 0 || H <= 0 || ((int64_t)b_first + B) * H > 65535) return OP_EINVAL;
+  return msa_row_context_launch(S, qkv, key_bias, ctx, workspace, workspace_bytes, B, R, L, H, hd, b_first, dr.thr16 ? &dr : nullptr, stream);
+}
+
+static int msa_col_attn_launch(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, const AttnDrop* dr, void* stream) {
   if (!qkv || !key_bias || !ctx || !msa_shape_ok(B, R, L, H, hd) || R < 2 || R > ONEPROT_MSA_MAX_ROWS || L > 65535 || B > 65535 ||
       (((uintptr_t)qkv | (uintptr_t)ctx) & 15))
     return OP_EINVAL;
-  hipLaunchKernelGGL(k_msa_col_attn, dim3((unsigned)H, (unsigned)L, (unsigned)B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, key_bias, (bf16_t*)ctx, R, L,
-                     H, scale);
+  const dim3 grid((unsigned)H, (unsigned)L, (unsigned)B);
+  if (dr) hipLaunchKernelGGL(k_msa_col_attn<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, key_bias, (bf16_t*)ctx, R, L, H, scale, *dr);
+  else hipLaunchKernelGGL(k_msa_col_attn<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, key_bias, (bf16_t*)ctx, R, L, H, scale, kNoDrop);
   return launch_status();
+}
+
+extern "C" int oneprot_msa_col_attn(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, void* stream) {
+  return msa_col_attn_launch(qkv, key_bias, ctx, B, R, L, H, hd, scale, nullptr, stream);
+}
+
+extern "C" int oneprot_msa_col_attn_dropout(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, float p, uint64_t seed,
+                                            uint64_t stream_id, void* stream) {
+  AttnDrop dr;
+  if (attn_drop_make(p, seed, stream_id, dr) != OP_OK || L > ONEPROT_MSA_MAX_LEN) return OP_EINVAL;      // (b * H + h) * L + l stays below 2^26
+  return msa_col_attn_launch(qkv, key_bias, ctx, B, R, L, H, hd, scale, dr.thr16 ? &dr : nullptr, stream);
 }

@@ -625,9 +625,13 @@ class TextEncoder(BaseEncoder):
 class MsaEncoder(BaseEncoder):
     """ref msa_encoder.py:6-55: the frozen MSA Transformer tower (oneprot_amd/msa.py; esm_msa1b_t12_100M_UR50S architecture) behind the reference's
     signature.  `forward(tokens[B, R, L] int64, padding id 1) -> float32 [B, output_dim]`: representation 12, then the masked mean over every non-pad
-    (r, l) (`use_all_msa=True`) or row 0 through `self.pooling`, then proj -> norm.  The tower is always frozen and in eval mode (the reference's train-mode
-    dropout is not reproduced: DESIGN.md section 7); parity with fair-esm is unpinned (no fair-esm, no checkpoint: tests/msa_ref.py is the oracle).
-    `d_model` follows the loaded architecture (768 for the published model, which the reference hard-codes)."""
+    (r, l) (`use_all_msa=True`) or row 0 through `self.pooling`, then proj -> norm.  The tower is always frozen and its own `.training` stays False; parity with
+    fair-esm is unpinned (no fair-esm, no checkpoint: tests/msa_ref.py is the oracle).  `d_model` follows the loaded architecture (768 for the published
+    model, which the reference hard-codes).
+    `train_dropout` (a property that reads and writes `transformer.train_dropout`; None = follow ONEPROT_MSA_DROPOUT, default 0): when it is on AND this
+    encoder is in train mode, the tower runs with fair-esm's train-mode dropouts, as the reference's does in every training step (oneprot_amd/msa.py,
+    DESIGN.md section 7).  Off by default; `.eval()`, validation and test are deterministic either way.  It is not a constructor argument: the constructor
+    keeps the reference's signature exactly."""
 
     def __init__(self, model_name_or_path: str, output_dim: int, pooling_type: str = "mean", proj_type: str = None, use_logit_scale: bool = False,
                  learnable_logit_scale: bool = False, use_all_msa: bool = False):
@@ -642,6 +646,14 @@ class MsaEncoder(BaseEncoder):
             param.requires_grad = False
         self.use_all_msa = use_all_msa
 
+    @property
+    def train_dropout(self):
+        return self.transformer.train_dropout
+
+    @train_dropout.setter
+    def train_dropout(self, on):
+        self.transformer.train_dropout = None if on is None else bool(on)
+
     def hidden_and_pooled(self, tokens, want_hidden=True):
         """(representation n_layers fp32 [B, R, L, d] -- [B, L, d] for row 0, None unless wanted --, pooled [B, d]): final LayerNorm fused with the pooling"""
         tr = self.transformer
@@ -651,7 +663,7 @@ class MsaEncoder(BaseEncoder):
             raise NotImplementedError(f"MsaEncoder(use_all_msa=False): pooling_type {self.pooling_type!r} is not built for row 0 of the MSA; use 'mean' or 'cls' "
                                       "(use_all_msa=True ignores the pooling, as in the reference)")
         with torch.no_grad():
-            x, _ = tr.run_layers(tokens)
+            x, _ = tr.run_layers(tokens, drop=bool(self.training and tr.dropout_enabled()))
             B, R, L = tokens.shape
             d, dev, pad = tr.d, tokens.device, tr.config.padding_idx
             if self.use_all_msa:                         # one "sequence" of R * L tokens per MSA

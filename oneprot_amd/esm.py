@@ -104,9 +104,9 @@ class ArenaModule(nn.Module):
     state-dict hooks that expose / accept the HF key names."""
 
     # Counter-based dropout streams (Philox key = seed, counter high words = stream id): every consumer gets a domain of its own so that no two
-    # of them can draw the same mask -- bits 60..63 the purpose (1: BERT hidden / attention dropout, 2: LoRA dropout), bits 44..59 the tower
+    # of them can draw the same mask -- bits 60..63 the purpose (1: BERT hidden / attention dropout, 2: LoRA dropout, 3: the MSA tower's train-mode dropouts), bits 44..59 the tower
     # (construction order within the process until OneProtLitModule re-numbers it by modality name; saved / restored with the stream state), bits 0..43 the consumer's own (call, layer, site) numbering.
-    RNG_DOMAIN_BERT, RNG_DOMAIN_LORA = 1, 2
+    RNG_DOMAIN_BERT, RNG_DOMAIN_LORA, RNG_DOMAIN_MSA = 1, 2, 3
     _next_rng_uid = 0
 
     def _init_arena(self):

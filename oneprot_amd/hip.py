@@ -131,6 +131,8 @@ _SIGS = {
     "oneprot_msa_row_context_workspace": (SZ, [I, I, I, I]),
     "oneprot_msa_row_context": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
     "oneprot_msa_col_attn": (I, [P, P, P, I, I, I, I, I, F, P]),
+    "oneprot_msa_row_context_dropout": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, F, U64, U64, P]),
+    "oneprot_msa_col_attn_dropout": (I, [P, P, P, I, I, I, I, I, F, F, U64, U64, P]),
 }
 MSA_MAX_LEN, MSA_MAX_ROWS = 1024, 128      # ONEPROT_MSA_MAX_LEN / ONEPROT_MSA_MAX_ROWS of include/oneprot_hip.h
 
@@ -153,6 +155,7 @@ _PTR_DTYPES = {
     "oneprot_segment_possum_f32": "fif", "oneprot_pool_packed_fwd": "flif", "oneprot_pool_packed_bwd": "flifh",
     "oneprot_sim_pair_dot": "fff", "oneprot_sim_rank": "fffii", "oneprot_sim_topk": "ffflb",
     "oneprot_msa_embed_fwd": "lffffff", "oneprot_msa_row_scores": "hff", "oneprot_msa_row_context": "fhfhb", "oneprot_msa_col_attn": "hfh",
+    "oneprot_msa_row_context_dropout": "fhfhb", "oneprot_msa_col_attn_dropout": "hfh",
 }
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 

@@ -1,13 +1,22 @@
 """MSA Transformer tower on the HIP kernels -- what the reference obtains from `esm.pretrained.load_model_and_alphabet_local` in MsaEncoder
 (ref msa_encoder.py:18,36): fair-esm's MSATransformer (esm_msa1b_t12_100M_UR50S: 12 axial layers, d 768, 12 heads of 64, FFN 3072, learned positions,
-an embedding per MSA row).  Forward only and eval mode: the reference freezes the tower (msa_encoder.py:30-32), so there is no backward.
+an embedding per MSA row).  Forward only: the reference freezes the tower (msa_encoder.py:30-32), so there is no backward.
 
 PARITY UNPINNED: fair-esm and its checkpoint are not available to this tree.  The arithmetic is restated from the published model and tested against the
 fp64 restatement tests/msa_ref.py; neither has been compared with a fair-esm run.  State-dict keys are the published module keys -- those a reference
 OneProt checkpoint holds under `network.msa.transformer.` -- and load strictly.
 
-Known differences: the reference calls `module.train()` on the whole network afterwards, which re-activates the model's 0.1
-dropouts; this tower computes the eval-mode numbers only.  Masked keys are excluded instead of biased by -10000 (equal wherever a query has one valid key).
+Known differences: masked keys are excluded instead of biased by -10000 (equal wherever a query has one valid key).
+
+TRAIN-MODE DROPOUT, on request.  The reference puts the tower in eval (msa_encoder.py:30) and Lightning's `module.train()` then switches the whole network
+back, so every training step of the reference runs the frozen tower with fair-esm's three dropouts active (0.1 each in the published model): `dropout`
+after emb_layer_norm_before and on the output of each of a layer's three residual blocks (NormalizedResidualBlock), `attention_dropout` on the
+probabilities of the row and the column attention, `activation_dropout` between the FFN's GELU and fc2.  `run_layers(tokens, drop=True)` /
+`forward(tokens, drop=True)` reproduce that with masks from our own generators (the distribution of nn.Dropout, not torch's stream): the attention masks
+are the per-element hash of the BERT tower's attention dropout (oneprot_msa_row_context_dropout / oneprot_msa_col_attn_dropout; the tied row attention
+has one mask element per (b, h, i, j) for all rows), the hidden masks Philox of (seed, call, layer, site, element of the flat [T, d] / [T, f] tensor).
+OFF by default: the tower's own `.training` stays False whatever `.train()` is called with, and MsaEncoder asks for `drop` only when it is in train mode
+and the switch -- `transformer.train_dropout` (None: follow ONEPROT_MSA_DROPOUT, default 0) -- is on.  The default forward is unchanged bit for bit.
 
 Per layer: LayerNorm -> one QKV GEMM (bf16 [T, 3d]) -> tied row attention (oneprot_msa_row_scores + oneprot_msa_row_context) -> out-projection + residual;
 the same with oneprot_msa_col_attn (R = 1: out_proj(v_proj(x)), as published); LayerNorm -> FFN-1 + GELU -> FFN-2 + residual.  The row-attention score
@@ -25,8 +34,11 @@ from .packing import PackedTokens
 
 MSA_DEFAULTS = dict(model_type="msa_transformer", num_layers=12, embed_dim=768, ffn_embed_dim=3072, attention_heads=12, max_positions=1024,
                     embed_positions_msa=True, msa_rows=1024, vocab_size=33, padding_idx=1, cls_idx=0, eos_idx=2, mask_idx=32, layer_norm_eps=1e-5)
+# fair-esm's three dropout probabilities (MSATransformer.add_args; 0.1 each in esm_msa1b_t12_100M_UR50S): used by the train-mode forward only
+MSA_DEFAULTS.update(dropout=0.1, attention_dropout=0.1, activation_dropout=0.1)
 _ARCH_KEYS = (("layers", "num_layers"), ("embed_dim", "embed_dim"), ("ffn_embed_dim", "ffn_embed_dim"), ("attention_heads", "attention_heads"),
-              ("max_positions", "max_positions"), ("embed_positions_msa", "embed_positions_msa"))
+              ("max_positions", "max_positions"), ("embed_positions_msa", "embed_positions_msa"), ("dropout", "dropout"),
+              ("attention_dropout", "attention_dropout"), ("activation_dropout", "activation_dropout"))
 _BLOCKS = ("row_self_attention", "column_self_attention")
 
 
@@ -124,8 +136,34 @@ class MsaTransformer(ArenaModule):
         self.eval()
 
     def train(self, mode=True):
-        """always eval: the tower is frozen and only the eval-mode forward exists"""
+        """always eval: the tower is frozen, and its train-mode dropout is an argument of the forward (`drop`), not a module mode"""
         return super().train(False)
+
+    # ---- fair-esm's train-mode dropouts, on request (module docstring).  The switch: None follows ONEPROT_MSA_DROPOUT (default 0 = off).
+    train_dropout = None
+
+    def dropout_enabled(self):
+        """whether MsaEncoder asks for the train-mode dropouts when it is in train mode"""
+        if self.train_dropout is not None:
+            return bool(self.train_dropout)
+        return os.environ.get("ONEPROT_MSA_DROPOUT", "0") != "0"
+
+    def _drop_probs(self):
+        cfg = self.config
+        return tuple(float(getattr(cfg, k, MSA_DEFAULTS[k])) for k in ("dropout", "attention_dropout", "activation_dropout"))
+
+    def _next_drop_call(self):
+        if getattr(self, "_drop_seed", None) is None:
+            self._drop_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF      # masks follow torch.manual_seed, as in bert.py
+            self._drop_calls = 0
+        call = self._drop_calls
+        self._drop_calls += 1
+        return call
+
+    def _drop_stream(self, call, layer, site):
+        """stream id of a dropout site.  layer -1, site 0: the embedding dropout; within a layer 0 = row probabilities, 1 = row-block output,
+        2 = column probabilities, 3 = column-block output, 4 = FFN activation, 5 = FFN output.  Hidden masks index the flat [T, d] / [T, f] element."""
+        return self._rng_stream(self.RNG_DOMAIN_MSA, (call * (self.n_layers + 1) + layer + 1) * 8 + site)
 
     @torch.no_grad()
     def reset_parameters(self):
@@ -158,8 +196,9 @@ class MsaTransformer(ArenaModule):
         hip.call("oneprot_gemm_bf16_nt", a, w, M, N, K, K, K, epi, bias, out0, None, None, aux, None, None, 1.0, 0, 0, 0)
 
     @torch.no_grad()
-    def run_layers(self, tokens, save=False):
-        """tokens int64 [B, R, L] -> (pre-final-LayerNorm hidden state fp32 [B*R*L, d], None)"""
+    def run_layers(self, tokens, save=False, drop=False):
+        """tokens int64 [B, R, L] -> (pre-final-LayerNorm hidden state fp32 [B*R*L, d], None).  drop=True: fair-esm's train-mode forward -- one call id is
+        drawn and every dropout site applies its mask (module docstring)."""
         self.check_input(tokens)
         if save:
             raise NotImplementedError("the MSA tower is frozen: there is no backward")
@@ -176,6 +215,13 @@ class MsaTransformer(ArenaModule):
         hip.call("oneprot_msa_embed_fwd", tokens, self.view("embed_tokens.weight"), self.view("embed_positions.weight"), self.view("msa_position_embedding"),
                  self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, R, L, d, cfg.vocab_size,
                  cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
+        if drop:
+            call, seed = self._next_drop_call(), self._drop_seed
+            p_h, p_a, p_f = self._drop_probs()
+            y, u_drop = f32(T, d), b16(T, f)            # a block's output before its dropout; dropout(u) in a buffer of its own (oneprot_dropout_bf16 declares
+                                                        # its operands __restrict__ and the header does not allow y = x for it, unlike the fp32 kernels)
+            # MSATransformer.forward: emb_layer_norm_before -> dropout_module -> x * (1 - padding_mask); the kernel above has zeroed the padding already
+            hip.call("oneprot_dropout_f32", x, x, T * d, p_h, seed, self._drop_stream(call, -1, 0))
         groups = plan_groups(B, R, L, H)
         gmax = max(b1 - b0 for b0, b1 in groups)
         S = f32(gmax, H, L, L)
@@ -198,7 +244,13 @@ class MsaTransformer(ArenaModule):
                         for b0, b1 in groups:
                             t0, t1 = b0 * R * L, b1 * R * L
                             hip.call("oneprot_msa_row_scores", qkv[t0:t1], kb[t0:t1], S, b1 - b0, R, L, H, hd, row_scale)
-                            hip.call("oneprot_msa_row_context", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd)
+                            if drop:                    # b0: the mask is that of the MSA's place in the batch, whatever the grouping
+                                hip.call("oneprot_msa_row_context_dropout", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd, b0, p_a,
+                                         seed, self._drop_stream(call, i, 0))
+                            else:
+                                hip.call("oneprot_msa_row_context", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd)
+                    elif drop:
+                        hip.call("oneprot_msa_col_attn_dropout", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5, p_a, seed, self._drop_stream(call, i, 2))
                     else:
                         hip.call("oneprot_msa_col_attn", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5)
                 if self.capture is not None:
@@ -206,21 +258,31 @@ class MsaTransformer(ArenaModule):
                 if self.stages is not None:             # the attention kernels leave qkv as they found it
                     one_row = blk == "column_self_attention" and R == 1
                     self.stages.append((blk[:3] + (".v" if one_row else ".qkv"), i, (ctx if one_row else qkv).clone()))
-                self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, self.view(p + "layer.out_proj.bias"), x, aux=x)
+                if drop:        # NormalizedResidualBlock: x = residual + dropout(layer(layer_norm(x))) -- the add leaves the GEMM epilogue so that the mask sits between
+                    self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_F32, self.view(p + "layer.out_proj.bias"), y)
+                    hip.call("oneprot_dropout_add_f32", y, x, x, T * d, p_h, seed, self._drop_stream(call, i, 1 if blk == "row_self_attention" else 3))
+                else:
+                    self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, self.view(p + "layer.out_proj.bias"), x, aux=x)
             p = f"layers.{i}.feed_forward_layer."
             if self.stages is not None:
                 self.stages.append(("ffn", i, x.clone()))
             hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
             self._gemm(h, self._w16(p + "layer.fc1.weight"), T, f, d, hip.EPI_BIAS_GELU, self.view(p + "layer.fc1.bias"), u)
-            self._gemm(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, self.view(p + "layer.fc2.bias"), x, aux=x)
+            if drop:            # FeedForwardNetwork: fc2(activation_dropout(gelu(fc1(x)))), then the block's own dropout
+                hip.call("oneprot_dropout_bf16", u, u_drop, T * f, p_f, seed, self._drop_stream(call, i, 4))
+                self._gemm(u_drop, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_F32, self.view(p + "layer.fc2.bias"), y)
+                hip.call("oneprot_dropout_add_f32", y, x, x, T * d, p_h, seed, self._drop_stream(call, i, 5))
+            else:
+                self._gemm(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, self.view(p + "layer.fc2.bias"), x, aux=x)
         if self.stages is not None:
             self.stages.append(("out", self.n_layers, x.clone()))
         return x, None
 
     @torch.no_grad()
-    def forward(self, tokens, repr_layers=(), **_):
-        """MSATransformer-compatible call: {"representations": {n_layers: [B, R, L, d]}} (the last representation, after emb_layer_norm_after)"""
-        x, _ = self.run_layers(tokens)
+    def forward(self, tokens, repr_layers=(), drop=False, **_):
+        """MSATransformer-compatible call: {"representations": {n_layers: [B, R, L, d]}} (the last representation, after emb_layer_norm_after);
+        drop=True: with fair-esm's train-mode dropouts (run_layers)"""
+        x, _ = self.run_layers(tokens, drop=drop)
         B, R, L = tokens.shape
         y = torch.empty_like(x)
         hip.call("oneprot_layernorm_fwd", x, 0, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), None, y, None, None,

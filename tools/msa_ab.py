@@ -11,7 +11,10 @@ new kernels and is reported as such.
 Per-kernel shares come from a kernel trace taken in a run of its own:
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/msa_ab.py --only b16_r50_l512 --reps 1 --hip-only --out /dev/null
   python tools/msa_ab.py --fold-trace DIR            (adds kernel_shares to the JSON written before)
-usage: msa_ab.py [--only NAME[,NAME]] [--reps 5] [--out profiles/msa_encoder.json] [--small] [--hip-only]"""
+--dropout: a second comparison at the same two shapes, HIP against HIP -- the default forward and the forward with fair-esm's train-mode dropouts
+(`drop=True`: masked row / column probabilities, six Philox passes per layer), alternating in one process; the medians and their ratio are ADDED to the JSON
+written before under "dropout_ab" (the other keys stay).  A record of the cost, not a gate.
+usage: msa_ab.py [--only NAME[,NAME]] [--reps 5] [--out profiles/msa_encoder.json] [--small] [--hip-only] [--dropout]"""
 import argparse
 import csv
 import glob
@@ -80,6 +83,28 @@ def run_shape(tr, sd, name, reps, small, hip_only):
     return out
 
 
+def run_dropout_ab(tr, name, reps, small):
+    """the default forward against the forward with the train-mode dropouts: same tokens, alternating"""
+    import torch
+    from oneprot_amd.data import SyntheticPairs
+    B, R, L = (SMALL if small else SHAPES)[name]
+    tok = SyntheticPairs._msa_frame(torch.Generator().manual_seed(50), B, R, L, True).cuda()
+    n = tr.n_layers
+    variants = {"hip": lambda: tr(tok)["representations"][n], "hip_dropout": lambda: tr(tok, drop=True)["representations"][n]}
+    for f in variants.values():                                        # warm-up
+        f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, f in variants.items():
+            timed(f, ms[k])
+    out = {"B": B, "R": R, "L": L, "tokens": B * R * L, "probabilities": list(tr._drop_probs())}
+    for k in variants:
+        out[k] = stats(ms[k])
+    out["dropout_over_default"] = out["hip_dropout"]["median_ms"] / out["hip"]["median_ms"]
+    return out
+
+
 def fold_trace(trace_dir, out_path):
     groups = (("k_msa_row_scores", "msa_row_scores"), ("k_msa_row_softmax", "msa_row_context"), ("k_msa_v_transpose", "msa_row_context"),
               ("k_msa_row_pv", "msa_row_context"), ("k_msa_col_attn", "msa_col_attn"), ("k_msa_embed", "msa_embed"),
@@ -109,6 +134,7 @@ def main():
     ap.add_argument("--small", action="store_true", help="small shapes: a dry run of the tool, not a measurement")
     ap.add_argument("--hip-only", action="store_true", help="run the HIP variant alone (for the kernel trace)")
     ap.add_argument("--fold-trace", default=None)
+    ap.add_argument("--dropout", action="store_true", help="default forward against the forward with the train-mode dropouts; adds dropout_ab to --out")
     a = ap.parse_args()
     if a.fold_trace:
         return fold_trace(a.fold_trace, a.out)
@@ -118,6 +144,17 @@ def main():
     warnings.filterwarnings("ignore", message=".*no weight file.*")
     torch.manual_seed(0)
     tr = MsaTransformer.from_pretrained("esm_msa1b_t12_100M_UR50S.pt").cuda()
+    if a.dropout:
+        doc = json.load(open(a.out)) if a.out != "/dev/null" and os.path.exists(a.out) else {}
+        ab = doc["dropout_ab"] = {"device": torch.cuda.get_device_name(0), "small_shapes": a.small,
+                                  "variants": "MsaTransformer.forward(tokens) against forward(tokens, drop=True), alternating in one process"}
+        for name in a.only.split(","):
+            ab[name] = run_dropout_ab(tr, name, max(a.reps, 1), a.small)
+            print(name, json.dumps(ab[name]), flush=True)
+            torch.cuda.empty_cache()
+        if a.out != "/dev/null":
+            json.dump(doc, open(a.out, "w"), indent=1)
+        return
     sd = {k: v.detach() for k, v in tr.state_dict().items() if not k.startswith(("lm_head.", "contact_head."))}
     doc = {"device": torch.cuda.get_device_name(0), "small_shapes": a.small, "weights": "random (published architecture)",
            "torch_variant": "tests/msa_ref.py forward, fp32 weights, torch.autocast(bfloat16)"}
