@@ -233,38 +233,35 @@ class BertTransformer(ArenaModule):
             if lora_two:      # peft's two branches in one launch: [h | dropout(h) A^T] x [W | s B]^T  (esm.py, enable_lora)
                 xc, lora_u = self._lora_branch_operand(i, h, T, lora_call)
                 kc = self._lora_ops["Kc"]
-                hip.call("oneprot_gemm_bf16_nt", xc, self._lora_ops["Wc"][i], T, 3 * d, kc, kc, kc, hip.EPI_QKV_ROPE, self.flat.data[ob:ob + nb], q, k, v, None,
-                         one, zero, hd ** -0.5 * hip.LOG2E, L, H, hd)
+                hip.gemm_nt(xc, self._lora_ops["Wc"][i], T, 3 * d, kc, hip.EPI_QKV_ROPE, q, bias=self.flat.data[ob:ob + nb], out1=k, out2=v,
+                            rope=(one, zero, L, H, hd), q_scale=hd ** -0.5 * hip.LOG2E)
                 if save:
                     st["lora_u"] = lora_u
             else:
-                hip.call("oneprot_gemm_bf16_nt", h, self._bf16[o:o + n], T, 3 * d, d, d, d, hip.EPI_QKV_ROPE, self.flat.data[ob:ob + nb], q, k, v, None,
-                         one, zero, hd ** -0.5 * hip.LOG2E, L, H, hd)
+                hip.gemm_nt(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_QKV_ROPE, q, bias=self.flat.data[ob:ob + nb], out1=k, out2=v,
+                            rope=(one, zero, L, H, hd), q_scale=hd ** -0.5 * hip.LOG2E)
             if drop:
                 lay.attn_fwd(q, k, v, ctx, lse, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
                 # s1 = x + dropout(ctx Wo^T + bo): the residual add leaves the GEMM epilogue so that the mask can sit between the two
-                hip.call("oneprot_gemm_bf16_nt", ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, d, d, hip.EPI_F32,
-                         self.view(p + "attention.output.dense.bias"), y_drop, None, None, None, None, None, 1.0, 0, 0, 0)
+                hip.gemm_nt(ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, hip.EPI_F32, y_drop, bias=self.view(p + "attention.output.dense.bias"))
                 # ... and the LayerNorm that follows reads the sum where it is formed (one kernel; a frozen tower never writes the sum)
                 hip.call("oneprot_dropout_add_layernorm_fwd", y_drop, x, s1 if save else None, self.view(p + "attention.output.LayerNorm.weight"),
                          self.view(p + "attention.output.LayerNorm.bias"), y16, y1, m1, r1, T, d, eps, p_h, self._drop_seed, self._drop_stream(drop_call, i, 1))
             else:
                 lay.attn_fwd(q, k, v, ctx, lse, H, hd)
-                hip.call("oneprot_gemm_bf16_nt", ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, d, d, hip.EPI_BIAS_RESID,
-                         self.view(p + "attention.output.dense.bias"), s1, None, None, x, None, None, 1.0, 0, 0, 0)
-                hip.call("oneprot_layernorm_fwd", s1, 0, self.view(p + "attention.output.LayerNorm.weight"), self.view(p + "attention.output.LayerNorm.bias"), y16, y1,
-                         m1, r1, T, d, eps)
-            hip.call("oneprot_gemm_bf16_nt", y16, self._w16(p + "intermediate.dense.weight"), T, f, d, d, d, hip.EPI_BIAS_GELU,
-                     self.view(p + "intermediate.dense.bias"), u, z, None, None, None, None, 1.0, 0, 0, 0)
+                hip.gemm_nt(ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, hip.EPI_BIAS_RESID, s1, bias=self.view(p + "attention.output.dense.bias"),
+                            aux=x)
+                hip.layernorm_fwd(s1, self.view(p + "attention.output.LayerNorm.weight"), self.view(p + "attention.output.LayerNorm.bias"), T, d, eps,
+                                  y16=y16, y32=y1, mean=m1, rstd=r1)
+            hip.gemm_nt(y16, self._w16(p + "intermediate.dense.weight"), T, f, d, hip.EPI_BIAS_GELU, u, bias=self.view(p + "intermediate.dense.bias"), out1=z)
             if drop:
-                hip.call("oneprot_gemm_bf16_nt", u, self._w16(p + "output.dense.weight"), T, d, f, f, f, hip.EPI_F32, self.view(p + "output.dense.bias"),
-                         y_drop, None, None, None, None, None, 1.0, 0, 0, 0)
+                hip.gemm_nt(u, self._w16(p + "output.dense.weight"), T, d, f, hip.EPI_F32, y_drop, bias=self.view(p + "output.dense.bias"))
                 hip.call("oneprot_dropout_add_layernorm_fwd", y_drop, y1, s2 if save else None, self.view(p + "output.LayerNorm.weight"),
                          self.view(p + "output.LayerNorm.bias"), h_out, x_out, m2, r2, T, d, eps, p_h, self._drop_seed, self._drop_stream(drop_call, i, 2))
             else:
-                hip.call("oneprot_gemm_bf16_nt", u, self._w16(p + "output.dense.weight"), T, d, f, f, f, hip.EPI_BIAS_RESID, self.view(p + "output.dense.bias"),
-                         s2, None, None, y1, None, None, 1.0, 0, 0, 0)
-                hip.call("oneprot_layernorm_fwd", s2, 0, self.view(p + "output.LayerNorm.weight"), self.view(p + "output.LayerNorm.bias"), h_out, x_out, m2, r2, T, d, eps)
+                hip.gemm_nt(u, self._w16(p + "output.dense.weight"), T, d, f, hip.EPI_BIAS_RESID, s2, bias=self.view(p + "output.dense.bias"), aux=y1)
+                hip.layernorm_fwd(s2, self.view(p + "output.LayerNorm.weight"), self.view(p + "output.LayerNorm.bias"), T, d, eps,
+                                  y16=h_out, y32=x_out, mean=m2, rstd=r2)
             if save:
                 saved["layers"].append(st)
             x, h = x_out, h_out
@@ -302,28 +299,28 @@ class BertTransformer(ArenaModule):
             st = saved["layers"][i]
             p = f"encoder.layer.{i}."
             # ---- LN2: ds = LN2'(g)  (fp32 + bf16 copy)
-            hip.call("oneprot_layernorm_bwd", g, 1, None, 0, st["s2"], 0, self.view(p + "output.LayerNorm.weight"), st["mean2"], st["rstd2"], None, ds, ds16,
-                     gv(p + "output.LayerNorm.weight"), gv(p + "output.LayerNorm.bias"), ws_ln, T, d, 0)
+            hip.layernorm_bwd(g, 1, st["s2"], self.view(p + "output.LayerNorm.weight"), st["mean2"], st["rstd2"], ds, gv(p + "output.LayerNorm.weight"),
+                              gv(p + "output.LayerNorm.bias"), ws_ln, T, d, dx16=ds16)
             # ---- FFN2 (weight + bias grads in one TN launch), then du * gelu'(z) in the dgrad epilogue
             do16 = ds16
             if drop_call is not None:
                 hip.call("oneprot_dropout_bf16", ds16, dm16, T * d, p_h, self._drop_seed, self._drop_stream(drop_call, i, 2))
                 do16 = dm16
-            self._wgrad(do16, st["u"], T, d, f, d, f, gv(p + "output.dense.weight"), gv(p + "output.dense.bias"), ws_tn)
-            hip.call("oneprot_gemm_bf16_nt", do16, self._bf16_T[(i, "w2")], T, f, d, d, d, hip.EPI_GELU_BWD, None, dz, None, None, st["z"], None, None, 1.0, 0, 0, 0)
+            self._wgrad(do16, st["u"], T, d, f, gv(p + "output.dense.weight"), gv(p + "output.dense.bias"), ws_tn)
+            hip.gemm_nt(do16, self._bf16_T[(i, "w2")], T, f, d, hip.EPI_GELU_BWD, dz, aux=st["z"])
             # ---- FFN1; gy = ds (residual branch) + dz W1
-            self._wgrad(dz, st["y16"], T, f, d, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
-            hip.call("oneprot_gemm_bf16_nt", dz, self._bf16_T[(i, "w1")], T, d, f, f, f, hip.EPI_BIAS_RESID, None, gy, None, None, ds, None, None, 1.0, 0, 0, 0)
+            self._wgrad(dz, st["y16"], T, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
+            hip.gemm_nt(dz, self._bf16_T[(i, "w1")], T, d, f, hip.EPI_BIAS_RESID, gy, aux=ds)
             # ---- LN1: ds = LN1'(gy)
-            hip.call("oneprot_layernorm_bwd", gy, 1, None, 0, st["s1"], 0, self.view(p + "attention.output.LayerNorm.weight"), st["mean1"], st["rstd1"], None, ds, ds16,
-                     gv(p + "attention.output.LayerNorm.weight"), gv(p + "attention.output.LayerNorm.bias"), ws_ln, T, d, 0)
+            hip.layernorm_bwd(gy, 1, st["s1"], self.view(p + "attention.output.LayerNorm.weight"), st["mean1"], st["rstd1"], ds,
+                              gv(p + "attention.output.LayerNorm.weight"), gv(p + "attention.output.LayerNorm.bias"), ws_ln, T, d, dx16=ds16)
             # ---- out-proj
             da16 = ds16
             if drop_call is not None:
                 hip.call("oneprot_dropout_bf16", ds16, dm16, T * d, p_h, self._drop_seed, self._drop_stream(drop_call, i, 1))
                 da16 = dm16
-            self._wgrad(da16, st["ctx"], T, d, d, d, d, gv(p + "attention.output.dense.weight"), gv(p + "attention.output.dense.bias"), ws_tn)
-            hip.call("oneprot_gemm_bf16_nt", da16, self._bf16_T[(i, "o")], T, d, d, d, d, hip.EPI_BF16, None, dctx, None, None, None, None, None, 1.0, 0, 0, 0)
+            self._wgrad(da16, st["ctx"], T, d, d, gv(p + "attention.output.dense.weight"), gv(p + "attention.output.dense.bias"), ws_tn)
+            hip.gemm_nt(da16, self._bf16_T[(i, "o")], T, d, d, hip.EPI_BF16, dctx)
             # ---- attention (no rotary: cos/sin = null)
             if drop_call is not None:
                 lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
@@ -332,9 +329,8 @@ class BertTransformer(ArenaModule):
             # ---- QKV projection; g = ds (residual branch) + dqkv Wqkv
             o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
             ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
-            hip.call("oneprot_gemm_bf16_tn", dqkv, st["x16"], T, 3 * d, d, 3 * d, d, gflat[o:o + n], gflat[ob:ob + nb], ws_tn, ws_tn.numel(), 0)
-            hip.call("oneprot_gemm_bf16_nt", dqkv, self._bf16_T[(i, "qkv")], T, d, 3 * d, 3 * d, 3 * d, hip.EPI_BIAS_RESID, None, g, None, None, ds, None, None,
-                     1.0, 0, 0, 0)
+            hip.gemm_tn(dqkv, st["x16"], T, 3 * d, d, gflat[o:o + n], gflat[ob:ob + nb], ws_tn)
+            hip.gemm_nt(dqkv, self._bf16_T[(i, "qkv")], T, d, 3 * d, hip.EPI_BIAS_RESID, g, aux=ds)
             if lora_raw is not None:      # two-branch LoRA: adapter gradients, and g += mask * (du A) / keep
                 self._lora_branch_backward(i, st["x16"], st["lora_u"], dqkv, T, saved["lora_call"], ws_tn, lora_raw, dh32=g)
             saved["layers"][i] = None
@@ -356,11 +352,10 @@ class BertTransformer(ArenaModule):
         esum = (self.view(e + "word_embeddings.weight")[ids.reshape(-1)] + lay.pos_rows(self)
                 + self.view(e + "token_type_embeddings.weight")[0]).contiguous()
         mean, rstd, y = torch.empty(T, device=dev), torch.empty(T, device=dev), torch.empty(T, d, device=dev)
-        hip.call("oneprot_layernorm_fwd", esum, 0, self.view(e + "LayerNorm.weight"), self.view(e + "LayerNorm.bias"), None, y, mean, rstd, T, d, cfg.layer_norm_eps)
+        hip.layernorm_fwd(esum, self.view(e + "LayerNorm.weight"), self.view(e + "LayerNorm.bias"), T, d, cfg.layer_norm_eps, y32=y, mean=mean, rstd=rstd)
         de = torch.empty(T, d, device=dev)
         ws_ln = torch.empty(hip.query("oneprot_layernorm_bwd_workspace", d), dtype=torch.uint8, device=dev)
-        hip.call("oneprot_layernorm_bwd", g, 1, None, 0, esum, 0, self.view(e + "LayerNorm.weight"), mean, rstd, None, de, None,
-                 gv(e + "LayerNorm.weight"), gv(e + "LayerNorm.bias"), ws_ln, T, d, 0)
+        hip.layernorm_bwd(g, 1, esum, self.view(e + "LayerNorm.weight"), mean, rstd, de, gv(e + "LayerNorm.weight"), gv(e + "LayerNorm.bias"), ws_ln, T, d)
         # position rows 0..n-1: sum over the batch (packed: over the segments that reach the row); token-type row 0: sum over positions of that
         dpos = gv(e + "position_embeddings.weight")
         n = lay.pos_bwd(de, dpos, d)

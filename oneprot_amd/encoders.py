@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import hip
 from . import layout
+from .layout import _ws
 from .esm import EsmTransformer, resolve_config, ModelConfig, recompute_plan
 from .packing import PackedTokens
 
@@ -175,10 +176,6 @@ class _IdentityPooling(nn.Identity):
         return x
 
 
-def _ws(nbytes, dev):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
-
 # ------------------------------------------------------------------------------------------------- projection head
 class _Head:
     """fp32 projection head on [B, d] rows: LN -> Linear [-> GELU -> LN -> Linear] -> L2 normalise -> * scale
@@ -199,7 +196,7 @@ class _Head:
         else:
             ln0, lin1 = mods[0], mods[1]
             a0, m0, r0 = f32(B, d), f32(B), f32(B)
-            hip.call("oneprot_layernorm_fwd", x, 0, ln0.weight, ln0.bias, None, a0, m0, r0, B, d, ln0.eps)
+            hip.layernorm_fwd(x, ln0.weight, ln0.bias, B, d, ln0.eps, y32=a0, mean=m0, rstd=r0)
             n1 = lin1.out_features
             y1 = f32(B, n1)
             hip.call("oneprot_sgemm", a0, lin1.weight, y1, B, n1, d, 0, 0, 1.0, 0)
@@ -211,7 +208,7 @@ class _Head:
                 g1 = f32(B, n1)
                 hip.call("oneprot_gelu_f32", y1, g1, B * n1)
                 a3, m3, r3 = f32(B, n1), f32(B), f32(B)
-                hip.call("oneprot_layernorm_fwd", g1, 0, ln3.weight, ln3.bias, None, a3, m3, r3, B, n1, ln3.eps)
+                hip.layernorm_fwd(g1, ln3.weight, ln3.bias, B, n1, ln3.eps, y32=a3, mean=m3, rstd=r3)
                 n4 = lin4.out_features
                 y = f32(B, n4)
                 hip.call("oneprot_sgemm", a3, lin4.weight, y, B, n4, n1, 0, 0, 1.0, 0)
@@ -253,8 +250,7 @@ class _Head:
             da3 = f32(B, n1)
             hip.call("oneprot_sgemm", dy, lin4.weight, da3, B, n1, D, 0, 1, 1.0, 0)       # da = dy W
             dg1, dgam3, dbet3 = f32(B, n1), f32(n1), f32(n1)
-            hip.call("oneprot_layernorm_bwd", da3, 1, None, 0, st["g1"], 0, ln3.weight, st["m3"], st["r3"], None, dg1, None, dgam3, dbet3,
-                     _ws(hip.query("oneprot_layernorm_bwd_workspace", n1), dev), B, n1, 0)
+            hip.layernorm_bwd(da3, 1, st["g1"], ln3.weight, st["m3"], st["r3"], dg1, dgam3, dbet3, _ws(hip.query("oneprot_layernorm_bwd_workspace", n1), dev), B, n1)
             dy1 = f32(B, n1)
             hip.call("oneprot_gelu_bwd_f32", st["y1"], dg1, dy1, B * n1)
             tail = [dgam3, dbet3, dW4]
@@ -266,8 +262,7 @@ class _Head:
         da0 = f32(B, d)
         hip.call("oneprot_sgemm", dy1, lin1.weight, da0, B, d, n1, 0, 1, 1.0, 0)
         dpooled, dgam0, dbet0 = f32(B, d), f32(d), f32(d)
-        hip.call("oneprot_layernorm_bwd", da0, 1, None, 0, pooled, 0, ln0.weight, st["m0"], st["r0"], None, dpooled, None, dgam0, dbet0,
-                 _ws(hip.query("oneprot_layernorm_bwd_workspace", d), dev), B, d, 0)
+        hip.layernorm_bwd(da0, 1, pooled, ln0.weight, st["m0"], st["r0"], dpooled, dgam0, dbet0, _ws(hip.query("oneprot_layernorm_bwd_workspace", d), dev), B, d)
         grads = [dgam0, dbet0, dW1] + tail
         return dpooled, grads
 

@@ -332,12 +332,12 @@ class ArenaModule(nn.Module):
             hip.call("oneprot_sgemm", self.lora_B.data[i, ti], self.lora_A.data[i, ti], tmp[blk * d * d:(blk + 1) * d * d], d, d, r, 0, 1, self._lora["scaling"], 1)
         return tmp
 
-    def _wgrad(self, dY, X, T, N, K, ldy, ldx, dW, db, ws):
+    def _wgrad(self, dY, X, T, N, K, dW, db, ws):
         """weight + bias gradient of one Linear; under LoRA the base weight is frozen, so only the bias gradient (column sums of dY) is formed"""
         if self._lora:
             hip.call("oneprot_colsum_bf16", dY, db, ws, T, N, 0)
         else:
-            hip.call("oneprot_gemm_bf16_tn", dY, X, T, N, K, ldy, ldx, dW, db, ws, ws.numel(), 0)
+            hip.gemm_tn(dY, X, T, N, K, dW, db, ws)
 
     @staticmethod
     def _tn_workspace(shapes, dev):
@@ -433,8 +433,7 @@ class ArenaModule(nn.Module):
         u = torch.empty(T, Rp, dtype=torch.bfloat16, device=h.device)
         for ti in range(len(self._lora["targets"])):
             hip.call("oneprot_dropout_bf16", h, sc["hd"], T * d, float(self._lora["dropout"]), self._lora_seed, self._lora_stream(call_id, i, ti))
-            hip.call("oneprot_gemm_bf16_nt", sc["hd"], ops["Acat"][i, ti * rp:(ti + 1) * rp], T, rp, d, d, d, hip.EPI_BF16, None, sc["ut"], None, None, None, None, None,
-                     1.0, 0, 0, 0)
+            hip.gemm_nt(sc["hd"], ops["Acat"][i, ti * rp:(ti + 1) * rp], T, rp, d, hip.EPI_BF16, sc["ut"])
             u[:, ti * rp:(ti + 1) * rp].copy_(sc["ut"])
         Xc = sc["Xc"]
         Xc[:, :d].copy_(h.view(T, d))
@@ -449,16 +448,16 @@ class ArenaModule(nn.Module):
         p_ = float(self._lora["dropout"])
         sc = self._lora_scratch_for(T, dev)
         du = torch.empty(T, Rp, dtype=torch.bfloat16, device=dev)
-        hip.call("oneprot_gemm_bf16_nt", dqkv, ops["BsT"][i], T, Rp, 3 * d, 3 * d, 3 * d, hip.EPI_BF16, None, du, None, None, None, None, None, 1.0, 0, 0, 0)
-        hip.call("oneprot_gemm_bf16_tn", dqkv, u, T, 3 * d, Rp, 3 * d, Rp, raw[1][i], None, ws_tn, ws_tn.numel(), 0)            # dqkv^T u
+        hip.gemm_nt(dqkv, ops["BsT"][i], T, Rp, 3 * d, hip.EPI_BF16, du)
+        hip.gemm_tn(dqkv, u, T, 3 * d, Rp, raw[1][i], None, ws_tn)            # dqkv^T u
         dhd = torch.empty(T, d, dtype=torch.bfloat16, device=dev)
         dut = sc["ut"]
         for ti in range(len(self._lora["targets"])):
             stream_id = self._lora_stream(call_id, i, ti)
             dut.copy_(du[:, ti * rp:(ti + 1) * rp])
             hip.call("oneprot_dropout_bf16", h, sc["hd"], T * d, p_, self._lora_seed, stream_id)                                  # the forward's dropout_t(h) again
-            hip.call("oneprot_gemm_bf16_tn", dut, sc["hd"], T, rp, d, rp, d, raw[0][i, ti * rp:(ti + 1) * rp], None, ws_tn, ws_tn.numel(), 0)      # du_t^T dropout_t(h)
-            hip.call("oneprot_gemm_bf16_nt", dut, ops["AtT"][i, ti], T, d, rp, rp, rp, hip.EPI_BF16, None, dhd, None, None, None, None, None, 1.0, 0, 0, 0)
+            hip.gemm_tn(dut, sc["hd"], T, rp, d, raw[0][i, ti * rp:(ti + 1) * rp], None, ws_tn)      # du_t^T dropout_t(h)
+            hip.gemm_nt(dut, ops["AtT"][i, ti], T, d, rp, hip.EPI_BF16, dhd)
             if dh16 is not None:
                 hip.call("oneprot_dropout_bwd_add_bf16", dhd, dh16, T * d, p_, self._lora_seed, stream_id)
             else:
@@ -839,18 +838,17 @@ class EsmTransformer(ArenaModule):
                         bufs["z"] = torch.empty(T, f, dtype=torch.uint8, device=dev)
                     z = bufs["z"]
             if pre is None:
-                hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "attention.LayerNorm.weight"), self.view(p + "attention.LayerNorm.bias"), h1, None,
-                         m1, r1, T, d, eps)
+                hip.layernorm_fwd(x, self.view(p + "attention.LayerNorm.weight"), self.view(p + "attention.LayerNorm.bias"), T, d, eps, y16=h1, mean=m1, rstd=r1)
             w_qkv, b_qkv, w_o = self._qkv_operands(i)
             if lora_two:      # peft's two branches in one launch: [h1 | dropout(h1) A^T] x [W | s B]^T  (K = Kc)
                 xc, lora_u = self._lora_branch_operand(i, h1, T, lora_call)
                 kc = self._lora_ops["Kc"]
-                hip.call("oneprot_gemm_bf16_nt", xc, self._lora_ops["Wc"][i], T, 3 * dp, kc, kc, kc, hip.EPI_QKV_ROPE, b_qkv, q, k, v, None, cos, sin,
-                         q_scale * hip.LOG2E, L, H, hd)
+                hip.gemm_nt(xc, self._lora_ops["Wc"][i], T, 3 * dp, kc, hip.EPI_QKV_ROPE, q, bias=b_qkv, out1=k, out2=v, rope=(cos, sin, L, H, hd),
+                            q_scale=q_scale * hip.LOG2E)
                 if save:
                     st["lora_u"] = lora_u
             else:
-                hip.call("oneprot_gemm_bf16_nt", h1, w_qkv, T, 3 * dp, d, d, d, hip.EPI_QKV_ROPE, b_qkv, q, k, v, None, cos, sin, q_scale * hip.LOG2E, L, H, hd)
+                hip.gemm_nt(h1, w_qkv, T, 3 * dp, d, hip.EPI_QKV_ROPE, q, bias=b_qkv, out1=k, out2=v, rope=(cos, sin, L, H, hd), q_scale=q_scale * hip.LOG2E)
             lay.attn_fwd(q, k, v, ctx_, lse, H, hd)
             if save:
                 x_mid = f32(T, d)
@@ -874,11 +872,9 @@ class EsmTransformer(ArenaModule):
                 if save:
                     st["mean2"], st["rstd2"] = stats2[0], stats2[1]
             else:
-                hip.call("oneprot_gemm_bf16_nt", ctx_, w_o, T, d, dp, dp, dp, hip.EPI_BIAS_RESID,
-                         self.view(p + "attention.output.dense.bias"), x_mid, None, None, x, None, None, 1.0, 0, 0, 0)
-                hip.call("oneprot_layernorm_fwd", x_mid, 0, self.view(p + "LayerNorm.weight"), self.view(p + "LayerNorm.bias"), h2, None, m2, r2, T, d, eps)
-            hip.call("oneprot_gemm_bf16_nt", h2, self._w16(p + "intermediate.dense.weight"), T, f, d, d, d, hip.EPI_BIAS_GELU,
-                     self.view(p + "intermediate.dense.bias"), u, z, None, None, None, None, 1.0, 0, 0, 0)
+                hip.gemm_nt(ctx_, w_o, T, d, dp, hip.EPI_BIAS_RESID, x_mid, bias=self.view(p + "attention.output.dense.bias"), aux=x)
+                hip.layernorm_fwd(x_mid, self.view(p + "LayerNorm.weight"), self.view(p + "LayerNorm.bias"), T, d, eps, y16=h2, mean=m2, rstd=r2)
+            hip.gemm_nt(h2, self._w16(p + "intermediate.dense.weight"), T, f, d, hip.EPI_BIAS_GELU, u, bias=self.view(p + "intermediate.dense.bias"), out1=z)
             if save and _GELU_CODE_DROP_BITS:      # experiment hook (tests: what the one-byte gelu' codes cost the gradient): keep only the top 8 - n bits
                 nb = _GELU_CODE_DROP_BITS
                 z.add_(1 << (nb - 1)).bitwise_and_(0xFF & ~((1 << nb) - 1))
@@ -891,8 +887,7 @@ class EsmTransformer(ArenaModule):
                          self.view(pn + "weight"), self.view(pn + "bias"), eps, pre[0], pre[1], *sched_ws)
             else:
                 pre = None
-                hip.call("oneprot_gemm_bf16_nt", u, self._w16(p + "output.dense.weight"), T, d, f, f, f, hip.EPI_BIAS_RESID,
-                         self.view(p + "output.dense.bias"), x_out, None, None, x_mid, None, None, 1.0, 0, 0, 0)
+                hip.gemm_nt(u, self._w16(p + "output.dense.weight"), T, d, f, hip.EPI_BIAS_RESID, x_out, bias=self.view(p + "output.dense.bias"), aux=x_mid)
             if save:
                 st["x_mid"] = x_mid
                 layers[i] = st
@@ -943,37 +938,33 @@ class EsmTransformer(ArenaModule):
             st = saved["layers"][i]
             p = f"encoder.layer.{i}."
             # ---- FFN2: x_out = x_mid + u W2^T + b2        (weight grad + bias grad in one TN launch)
-            self._wgrad(g16, st["u"], T, d, f, d, f, gv(p + "output.dense.weight"), gv(p + "output.dense.bias"), ws_tn)
-            hip.call("oneprot_gemm_bf16_nt", g16, self._bf16_T[(i, "w2")], T, f, d, d, d, hip.EPI_GELU_BWD, None, dz, None, None, st["z"], None, None,
-                     1.0, 0, 0, 0)
+            self._wgrad(g16, st["u"], T, d, f, gv(p + "output.dense.weight"), gv(p + "output.dense.bias"), ws_tn)
+            hip.gemm_nt(g16, self._bf16_T[(i, "w2")], T, f, d, hip.EPI_GELU_BWD, dz, aux=st["z"])
             # ---- FFN1: z = h2 W1^T + b1
-            self._wgrad(dz, st["h2"], T, f, d, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
-            hip.call("oneprot_gemm_bf16_nt", dz, self._bf16_T[(i, "w1")], T, d, f, f, f, hip.EPI_BF16, None, dh, None, None, None, None, None, 1.0, 0, 0, 0)
+            self._wgrad(dz, st["h2"], T, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
+            hip.gemm_nt(dz, self._bf16_T[(i, "w1")], T, d, f, hip.EPI_BF16, dh)
             # ---- LN2 (input x_mid): g += LN'(dh); also refreshes the bf16 copy g16
-            hip.call("oneprot_layernorm_bwd", dh, 0, None, 0, st["x_mid"], 0, self.view(p + "LayerNorm.weight"), st["mean2"], st["rstd2"], g, g, g16,
-                     gv(p + "LayerNorm.weight"), gv(p + "LayerNorm.bias"), ws_ln, T, d, 0)
+            hip.layernorm_bwd(dh, 0, st["x_mid"], self.view(p + "LayerNorm.weight"), st["mean2"], st["rstd2"], g, gv(p + "LayerNorm.weight"), gv(p + "LayerNorm.bias"),
+                              ws_ln, T, d, add_to=g, dx16=g16)
             # ---- out-proj: x_mid = x_in + ctx Wo^T + bo
-            hip.call("oneprot_gemm_bf16_tn", g16, st["ctx"], T, d, dp, d, dp, gw_o if self._padded else gv(p + "attention.output.dense.weight"),
-                     gv(p + "attention.output.dense.bias"), ws_tn, ws_tn.numel(), 0)
-            hip.call("oneprot_gemm_bf16_nt", g16, self._bf16_T[(i, "o")], T, dp, d, d, d, hip.EPI_BF16, None, dctx, None, None, None, None, None, 1.0, 0, 0, 0)
+            hip.gemm_tn(g16, st["ctx"], T, d, dp, gw_o if self._padded else gv(p + "attention.output.dense.weight"), gv(p + "attention.output.dense.bias"), ws_tn)
+            hip.gemm_nt(g16, self._bf16_T[(i, "o")], T, dp, d, hip.EPI_BF16, dctx)
             # ---- attention
             lay.attn_bwd(st, dctx, q_scale, dqkv, ws_at, H, hd)
             # ---- QKV projection
             o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
             ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
-            hip.call("oneprot_gemm_bf16_tn", dqkv, st["h1"], T, 3 * dp, d, 3 * dp, d, gw_qkv if self._padded else gflat[o:o + n],
-                     gb_qkv if self._padded else gflat[ob:ob + nb], ws_tn, ws_tn.numel(), 0)
+            hip.gemm_tn(dqkv, st["h1"], T, 3 * dp, d, gw_qkv if self._padded else gflat[o:o + n], gb_qkv if self._padded else gflat[ob:ob + nb], ws_tn)
             if self._padded:
                 gv(p + "attention.output.dense.weight").copy_(gw_o[:, colmap])
                 gflat[o:o + n].view(3 * d, d).copy_(gw_qkv[rowmap])
                 gflat[ob:ob + nb].copy_(gb_qkv[rowmap])
-            hip.call("oneprot_gemm_bf16_nt", dqkv, self._bf16_T[(i, "qkv")], T, d, 3 * dp, 3 * dp, 3 * dp, hip.EPI_BF16, None, dh, None, None, None, None, None,
-                     1.0, 0, 0, 0)
+            hip.gemm_nt(dqkv, self._bf16_T[(i, "qkv")], T, d, 3 * dp, hip.EPI_BF16, dh)
             if lora_raw is not None:      # two-branch LoRA: adapter gradients, and dh += mask * (du A) / keep
                 self._lora_branch_backward(i, st["h1"], st["lora_u"], dqkv, T, saved["lora_call"], ws_tn, lora_raw, dh16=dh)
             # ---- LN1 (input x_in)
-            hip.call("oneprot_layernorm_bwd", dh, 0, None, 0, st["x_in"], 0, self.view(p + "attention.LayerNorm.weight"), st["mean1"], st["rstd1"], g, g, g16,
-                     gv(p + "attention.LayerNorm.weight"), gv(p + "attention.LayerNorm.bias"), ws_ln, T, d, 0)
+            hip.layernorm_bwd(dh, 0, st["x_in"], self.view(p + "attention.LayerNorm.weight"), st["mean1"], st["rstd1"], g, gv(p + "attention.LayerNorm.weight"),
+                              gv(p + "attention.LayerNorm.bias"), ws_ln, T, d, add_to=g, dx16=g16)
             saved["layers"][i] = st = None      # release this layer's activations
             if bounds is not None:
                 bounds.pop(i, None)      # ... and, under its bottom layer, the segment's boundary record

@@ -2,10 +2,16 @@
 
 There is no CPU fallback: if the shared library is missing, or a kernel returns a non-zero status, this module
 raises.  torch is used only as the owner of device memory and streams (tensor.data_ptr(), current stream).
+
+The header is the single source of the ABI: the ctypes signatures (_SIGS) and the expected element type of every pointer argument (_PTR_DTYPES) are
+parsed from it at import, so a new entry point is declared there, defined in csrc/, and needs nothing here unless one of its void* is not bf16
+(_BYTE_PTRS / _FLAG_TYPED_PTRS).  call(name, *positional) launches any entry point; gemm_nt / gemm_tn / layernorm_fwd / layernorm_bwd are keyword
+launchers of the four widest ones and end in the same call().
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
+import re
+from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 import torch
 
@@ -26,137 +32,67 @@ class HipKernelError(RuntimeError):
     pass
 
 
-P, I, L64, F, SZ = c_void_p, c_int, c_int64, c_float, c_size_t
-U64 = ctypes.c_uint64
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "oneprot_hip.h")      # where csrc/build.sh reads it too
 
-# name -> (restype, argtypes)    (mirrors include/oneprot_hip.h line by line)
-_SIGS = {
-    "oneprot_abi_version": (I, []),
-    "oneprot_esm_embed_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
-    "oneprot_esm_embed_bwd_workspace": (SZ, [I, I, I]),
-    "oneprot_esm_embed_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
-    "oneprot_bert_embed_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, F, P]),
-    "oneprot_pool_fwd": (I, [P, P, I, P, I, I, I, I, P]),
-    "oneprot_pool_bwd": (I, [P, P, I, P, P, I, I, I, I, P]),
-    "oneprot_embed_scatter_sorted": (I, [P, P, P, P, L64, I, I, I, P, P]),
-    "oneprot_rowsum_f32": (I, [P, P, I, L64, P]),
-    "oneprot_attnpool_fwd": (I, [P, P, I, P, P, P, P, I, I, I, P]),
-    "oneprot_attnpool_bwd_workspace": (SZ, [I, I]),
-    "oneprot_attnpool_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
-    "oneprot_layernorm_fwd": (I, [P, I, P, P, P, P, P, P, L64, I, F, P]),
-    "oneprot_layernorm_bwd_workspace": (SZ, [I]),
-    "oneprot_layernorm_bwd": (I, [P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, L64, I, I, P]),
-    "oneprot_lnpool_fwd": (I, [P, P, I, P, P, P, P, P, P, P, P, I, I, I, F, I, P]),
-    "oneprot_gemm_bf16_nt": (I, [P, P, L64, I, I, I, I, I, P, P, P, P, P, P, P, F, I, I, I, P]),
-    "oneprot_gemm_ln_pack_weight": (I, [P, P, I, I, P]),
-    "oneprot_gemm_bf16_nt_resid_ln": (I, [P, P, L64, I, I, I, P, P, P, P, P, F, P, P, P, P]),
-    "oneprot_sched_workspace_bytes": (SZ, [L64]),
-    "oneprot_alloc_uncached": (I, [ctypes.POINTER(c_void_p), SZ]),
-    "oneprot_free_uncached": (I, [P]),
-    "oneprot_sched_workspace_init": (I, [P, SZ, P]),
-    "oneprot_dynamic_tiles": (None, [P, SZ]),
-    "oneprot_sched_late_draws": (I, [P]),
-    "oneprot_sched_epoch": (L64, [P]),
-    "oneprot_gemm_bf16_nt_resid_ln8": (I, [P, P, L64, I, I, I, I, P, P, P, P, P, F, P, P, P, SZ, P]),
-    "oneprot_gemm_resid_ln8_eligible": (I, [L64, I, I]),
-    "oneprot_gemm_resid_ln8_error": (I, [P]),
-    "oneprot_gemm_resid_ln8_error_clear": (I, [P, P]),
-    "oneprot_gemm_resid_ln8_poll_bound": (None, [I]),
-    "oneprot_gemm_ln_form": (None, [I]),
-    "oneprot_gemm_ln_form_get": (I, []),
-    "oneprot_gemm_force_shape": (None, [I]),
-    "oneprot_gemm_tune": (None, [I, I]),
-    "oneprot_gemm_bf16_tn_workspace": (SZ, [I, I]),
-    "oneprot_gemm_tn_variant": (None, [I]),
-    "oneprot_cu_reserve": (None, [I]),
-    "oneprot_gemm_bf16_tn": (I, [P, P, L64, I, I, I, I, P, P, P, SZ, I, P]),
-    "oneprot_sgemm": (I, [P, P, P, I, I, I, I, I, F, I, P]),
-    "oneprot_attn_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
-    "oneprot_attn_fwd_dropout": (I, [P, P, P, P, P, P, I, I, I, I, F, U64, U64, P]),
-    "oneprot_attn_dropout_keep": (I, [P, I, I, I, F, U64, U64, P]),
-    "oneprot_attn_bwd_dropout": (I, [P, P, P, P, P, P, P, P, P, F, P, P, I, I, I, I, F, U64, U64, P]),
-    "oneprot_attn_bwd_workspace": (SZ, [I, I, I]),
-    "oneprot_attn_bwd": (I, [P, P, P, P, P, P, P, P, P, F, P, P, I, I, I, I, P]),
-    "oneprot_attn_force_bwd_path": (None, [I]),
-    "oneprot_attn_force_fwd_path": (None, [I]),
-    "oneprot_gelu_f32": (I, [P, P, L64, P]),
-    "oneprot_gelu_bwd_f32": (I, [P, P, P, L64, P]),
-    "oneprot_l2norm_fwd": (I, [P, P, P, I, I, F, P]),
-    "oneprot_l2norm_bwd": (I, [P, P, P, P, I, I, F, F, P]),
-    "oneprot_ce_fwd_bwd": (I, [P, P, P, I, I, I, F, P]),
-    "oneprot_siglip_fwd_bwd": (I, [P, P, P, I, F, I, P]),
-    "oneprot_siglip_fwd_bwd_dev": (I, [P, P, P, I, P, I, P]),
-    "oneprot_diag_rank": (I, [P, P, P, I, P]),
-    "oneprot_abs_sum": (I, [P, P, P, L64, F, P]),
-    "oneprot_dot_f32": (I, [P, P, P, P, L64, F, P]),
-    "oneprot_l1_bwd": (I, [P, P, L64, F, P, I, P]),
-    "oneprot_scale_by_device_scalar": (I, [P, L64, P, P]),
-    "oneprot_dropout_bf16": (I, [P, P, L64, F, U64, U64, P]),
-    "oneprot_dropout_bwd_add_bf16": (I, [P, P, L64, F, U64, U64, P]),
-    "oneprot_dropout_bwd_add_f32": (I, [P, P, L64, F, U64, U64, P]),
-    "oneprot_dropout_f32": (I, [P, P, L64, F, U64, U64, P]),
-    "oneprot_dropout_add_f32": (I, [P, P, P, L64, F, U64, U64, P]),
-    "oneprot_dropout_add_layernorm_fwd": (I, [P, P, P, P, P, P, P, P, P, L64, I, F, F, U64, U64, P]),
-    "oneprot_key_padding_bias": (I, [P, P, L64, I, P]),
-    "oneprot_sumsq_workspace": (SZ, []),
-    "oneprot_sumsq": (I, [P, L64, P, P, P]),
-    "oneprot_clip_coef": (I, [P, F, P, P, P, P]),
-    "oneprot_adam_step": (I, [P, P, P, P, L64, F, F, F, F, F, I, P, P]),
-    "oneprot_cast_f32_to_bf16": (I, [P, P, L64, P]),
-    "oneprot_transpose_cast_f32_to_bf16": (I, [P, P, I, I, P]),
-    "oneprot_transpose_cast_f32_to_bf16_batched": (I, [P, P, I, I, L64, L64, I, P]),
-    "oneprot_colsum_workspace": (SZ, [I]),
-    "oneprot_colsum_bf16": (I, [P, P, P, L64, I, I, P]),
-    "oneprot_esm_embed_packed_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
-    "oneprot_esm_embed_packed_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
-    "oneprot_attn_varlen_fwd": (I, [P, P, P, P, P, I, P, P, I, I, I, I, P]),
-    "oneprot_attn_varlen_bwd_workspace": (SZ, [I, I]),
-    "oneprot_attn_varlen_bwd": (I, [P, P, P, P, P, I, P, P, P, P, P, F, P, P, I, I, I, I, P]),
-    "oneprot_attn_varlen_fwd_dropout": (I, [P, P, P, P, P, I, P, P, I, I, I, I, F, U64, U64, P]),
-    "oneprot_attn_varlen_bwd_dropout": (I, [P, P, P, P, P, I, P, P, P, P, P, F, P, P, I, I, I, I, F, U64, U64, P]),
-    "oneprot_bert_embed_packed_fwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
-    "oneprot_segment_possum_f32": (I, [P, P, P, I, I, I, I, P]),
-    "oneprot_pool_packed_fwd": (I, [P, P, P, I, P, I, I, I, I, P]),
-    "oneprot_pool_packed_bwd": (I, [P, P, P, I, P, P, I, I, I, I, P]),
-    "oneprot_lnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, P, P, P, I, I, I, F, I, P]),
-    "oneprot_lnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
-    "oneprot_attnpool_packed_fwd": (I, [P, P, P, I, P, P, P, P, I, I, I, P]),
-    "oneprot_attnpool_packed_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
-    "oneprot_sim_pair_dot": (I, [P, P, P, I, I, P]),
-    "oneprot_sim_rank": (I, [P, P, P, I, I, I, I, P, P, P]),
-    "oneprot_sim_topk_workspace": (SZ, [I, I, I]),
-    "oneprot_sim_topk": (I, [P, P, I, I, I, I, P, P, P, SZ, P]),
-    "oneprot_msa_embed_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, F, P]),
-    "oneprot_msa_row_scores": (I, [P, P, P, I, I, I, I, I, F, P]),
-    "oneprot_msa_row_context_workspace": (SZ, [I, I, I, I]),
-    "oneprot_msa_row_context": (I, [P, P, P, P, P, SZ, I, I, I, I, I, P]),
-    "oneprot_msa_col_attn": (I, [P, P, P, I, I, I, I, I, F, P]),
-    "oneprot_msa_row_context_dropout": (I, [P, P, P, P, P, SZ, I, I, I, I, I, I, F, U64, U64, P]),
-    "oneprot_msa_col_attn_dropout": (I, [P, P, P, I, I, I, I, I, F, F, U64, U64, P]),
-}
-MSA_MAX_LEN, MSA_MAX_ROWS = 1024, 128      # ONEPROT_MSA_MAX_LEN / ONEPROT_MSA_MAX_ROWS of include/oneprot_hip.h
+_SCALARS = {"int": c_int, "int64_t": c_int64, "size_t": c_size_t, "float": c_float, "uint64_t": c_uint64}
+_RETURNS = {"int": c_int, "size_t": c_size_t, "int64_t": c_int64, "void": None}
+# Element type of a pointer argument: f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a flag argument / epilogue id.
+# A typed pointer says it itself and a void* is bf16 storage (the header's convention).  The void* that are not bf16 are named here, and nowhere else:
+_PTR_LETTER = {"float": "f", "int64_t": "l", "int": "i", "void": "h"}
+_BYTE_PTRS = {"workspace", "sched_ws", "keep"}                                       # by parameter name, in every entry point
+_FLAG_TYPED_PTRS = {("oneprot_gemm_bf16_nt", "out0"), ("oneprot_gemm_bf16_nt", "out1"), ("oneprot_gemm_bf16_nt", "aux"),
+                    ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x")}
 
-# Expected element type of every pointer argument, in order (f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a
-# flag argument / epilogue id).  The C side validates shapes and alignment but cannot see a tensor's dtype, device or strides: a strided view or an
-# fp16 tensor would compute garbage silently, so the binding refuses them (HipKernelError) before the launch.
-_PTR_DTYPES = {
-    "oneprot_esm_embed_fwd": "lfff", "oneprot_esm_embed_bwd": "lfffb", "oneprot_bert_embed_fwd": "lffffffh", "oneprot_pool_fwd": "flf",
-    "oneprot_pool_bwd": "flfh", "oneprot_embed_scatter_sorted": "flllf", "oneprot_rowsum_f32": "ff", "oneprot_attnpool_fwd": "flffff",
-    "oneprot_attnpool_bwd": "fffffffb", "oneprot_layernorm_fwd": "*ffhfff", "oneprot_layernorm_bwd": "*f*fffffhffb", "oneprot_lnpool_fwd": "flffffffhf",
-    "oneprot_gemm_bf16_nt": "hhf**h*ff", "oneprot_gemm_ln_pack_weight": "hh", "oneprot_gemm_bf16_nt_resid_ln": "hhfffffhff", "oneprot_gemm_bf16_nt_resid_ln8": "hhfffffhfb", "oneprot_sched_workspace_init": "b", "oneprot_gemm_resid_ln8_error_clear": "b", "oneprot_gemm_bf16_tn": "hhffb", "oneprot_sgemm": "fff", "oneprot_attn_fwd": "hhhfhf",
-    "oneprot_attn_bwd": "hhhfhhfffhb", "oneprot_attn_bwd_dropout": "hhhfhhfffhb", "oneprot_gelu_f32": "ff", "oneprot_gelu_bwd_f32": "fff", "oneprot_l2norm_fwd": "fff", "oneprot_l2norm_bwd": "ffff",
-    "oneprot_ce_fwd_bwd": "fff", "oneprot_siglip_fwd_bwd": "fff", "oneprot_siglip_fwd_bwd_dev": "ffff", "oneprot_diag_rank": "fii", "oneprot_abs_sum": "ffb", "oneprot_dot_f32": "fffb", "oneprot_l1_bwd": "fff",
-    "oneprot_scale_by_device_scalar": "ff", "oneprot_key_padding_bias": "lf", "oneprot_dropout_bf16": "hh", "oneprot_dropout_bwd_add_bf16": "hh", "oneprot_dropout_bwd_add_f32": "hf", "oneprot_dropout_f32": "ff", "oneprot_dropout_add_f32": "fff", "oneprot_dropout_add_layernorm_fwd": "fffffhfff", "oneprot_attn_fwd_dropout": "hhhfhf", "oneprot_attn_dropout_keep": "b", "oneprot_sumsq": "ffb", "oneprot_clip_coef": "fffb", "oneprot_adam_step": "fffff",
-    "oneprot_cast_f32_to_bf16": "fh", "oneprot_transpose_cast_f32_to_bf16": "fh", "oneprot_transpose_cast_f32_to_bf16_batched": "fh", "oneprot_colsum_bf16": "hfb",
-    "oneprot_esm_embed_packed_fwd": "lifffffff", "oneprot_esm_embed_packed_bwd": "lfffb", "oneprot_attn_varlen_fwd": "hhhiihf",
-    "oneprot_attn_varlen_bwd": "hhhiihhfffhb", "oneprot_lnpool_packed_fwd": "flifffffff", "oneprot_lnpool_packed_bwd": "fiffffffhffb",
-    "oneprot_attnpool_packed_fwd": "fliffff", "oneprot_attnpool_packed_bwd": "ffifffffb",
-    "oneprot_attn_varlen_fwd_dropout": "hhhiihf", "oneprot_attn_varlen_bwd_dropout": "hhhiihhfffhb", "oneprot_bert_embed_packed_fwd": "liffffffh",
-    "oneprot_segment_possum_f32": "fif", "oneprot_pool_packed_fwd": "flif", "oneprot_pool_packed_bwd": "flifh",
-    "oneprot_sim_pair_dot": "fff", "oneprot_sim_rank": "fffii", "oneprot_sim_topk": "ffflb",
-    "oneprot_msa_embed_fwd": "lffffff", "oneprot_msa_row_scores": "hff", "oneprot_msa_row_context": "fhfhb", "oneprot_msa_col_attn": "hfh",
-    "oneprot_msa_row_context_dropout": "fhfhb", "oneprot_msa_col_attn_dropout": "hfh",
-}
+
+def _parse_header(text, where=HEADER_PATH):
+    """({entry point: (restype, [argtypes])}, {entry point: pointer letters, the trailing stream excluded}, {ONEPROT_<NAME>: int of a #define})
+    of the C declarations in `text`.  A declaration it cannot map raises HipLibraryMissing: nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+ONEPROT_(\w+)\s+(\d+)\s*$", text, flags=re.M)}
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    sigs, kinds = {}, {}
+    for m in re.finditer(r"([^;{}]*?)\b(oneprot_\w+)\s*\(([^;{}]*?)\)\s*;", text):
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        decl = " ".join(m.group(0).split())
+        if ret not in _RETURNS:
+            raise HipLibraryMissing(f"{where}: cannot map the return type of `{decl}`")
+        args, letters = [], ""
+        plist = [] if params == "void" else params.split(",")
+        for k, prm in enumerate(plist):
+            pm = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\**)\s*(\w+)\s*", prm)
+            ctype, stars, pname = pm.groups() if pm else (None, "", None)
+            if stars == "" and ctype in _SCALARS:
+                args.append(_SCALARS[ctype])
+            elif stars == "**" and ctype == "void":
+                args.append(ctypes.POINTER(c_void_p))
+            elif stars == "*" and ctype in _PTR_LETTER:
+                args.append(c_void_p)
+                if not (pname == "stream" and k == len(plist) - 1):
+                    letters += "b" if pname in _BYTE_PTRS else "*" if (name, pname) in _FLAG_TYPED_PTRS else _PTR_LETTER[ctype]
+            else:
+                raise HipLibraryMissing(f"{where}: cannot map parameter `{prm.strip()}` of `{decl}`")
+        sigs[name] = (_RETURNS[ret], args)
+        if letters:
+            kinds[name] = letters
+    unparsed = sorted(set(re.findall(r"\b(oneprot_\w+)\s*\(", text)) - set(sigs))
+    if unparsed:
+        raise HipLibraryMissing(f"{where}: cannot parse the declaration of {', '.join(unparsed)}")
+    return sigs, kinds, consts
+
+
+def _load_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return _parse_header(f.read())
+    except OSError as e:
+        raise HipLibraryMissing(f"{HEADER_PATH}: the C header the binding is derived from cannot be read ({e})") from None
+
+
+# name -> (restype, argtypes) and name -> pointer letters, both derived from include/oneprot_hip.h.  The C side validates shapes and alignment but cannot
+# see a tensor's dtype, device or strides: a strided view or an fp16 tensor would compute garbage silently, so the binding refuses them (HipKernelError)
+# before the launch.
+_SIGS, _PTR_DTYPES, _consts = _load_header()
+MSA_MAX_LEN, MSA_MAX_ROWS = _consts["MSA_MAX_LEN"], _consts["MSA_MAX_ROWS"]
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 
 _lib = None
@@ -258,6 +194,28 @@ def call(name, *args):
 
 def query(name, *args):
     return getattr(lib(), name)(*args)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Keyword launchers of the four widest entry points.  Each only orders its arguments as include/oneprot_hip.h declares them and hands them to call().
+def gemm_nt(a, w, M, N, K, epi, out0, *, bias=None, out1=None, out2=None, aux=None, lda=None, ldb=None, rope=None, q_scale=1.0):
+    """out0 (, out1, out2) = epilogue `epi` of a[M,K] w[N,K]^T.  lda / ldb default to K; rope = (cos, sin, L, H, hd) for EPI_QKV_ROPE."""
+    cos, sin, L, H, hd = rope if rope is not None else (None, None, 0, 0, 0)
+    call("oneprot_gemm_bf16_nt", a, w, M, N, K, K if lda is None else lda, K if ldb is None else ldb, epi, bias, out0, out1, out2, aux, cos, sin, q_scale, L, H, hd)
+
+
+def gemm_tn(dY, X, M, N, K, dW, dbias, ws, *, ldy=None, ldx=None, accumulate=0):
+    """dW[N,K] (+)= dY[M,N]^T X[M,K], dbias[N] (+)= column sums of dY (optional).  ldy defaults to N, ldx to K; ws from oneprot_gemm_bf16_tn_workspace."""
+    call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N if ldy is None else ldy, K if ldx is None else ldx, dW, dbias, ws, ws.numel(), accumulate)
+
+
+def layernorm_fwd(x, gamma, beta, T, d, eps, *, y16=None, y32=None, mean=None, rstd=None, x_is_bf16=0):
+    call("oneprot_layernorm_fwd", x, x_is_bf16, gamma, beta, y16, y32, mean, rstd, T, d, eps)
+
+
+def layernorm_bwd(dy, dy_mode, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, T, d, *, wrow=None, L=0, x_is_bf16=0, add_to=None, dx16=None, accumulate=0):
+    """dy_mode 0: dy bf16 [T,d]; 1: fp32 [T,d]; 2: dy[t] = dy[t // L] * wrow[t].  dx = (add_to or 0) + LN'(dy), dx16 its optional bf16 copy."""
+    call("oneprot_layernorm_bwd", dy, dy_mode, wrow, L, x, x_is_bf16, gamma, mean, rstd, add_to, dx, dx16, dgamma, dbeta, ws, T, d, accumulate)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

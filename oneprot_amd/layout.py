@@ -90,7 +90,7 @@ class _Layout:
         lnw, (gw, gb) = self._final_ln(tr)[0], self._final_ln(tr, gflat)
         ws = _ws(hip.query("oneprot_layernorm_bwd_workspace", d), dev)
         if mode == 2:
-            hip.call("oneprot_layernorm_bwd", dhidden, 1, None, 0, x_final, 0, lnw, mean, rstd, None, g, g16, gw, gb, ws, self.T, d, 0)
+            hip.layernorm_bwd(dhidden, 1, x_final, lnw, mean, rstd, g, gw, gb, ws, self.T, d, dx16=g16)
         else:                                           # dy[t] = dpooled[sequence of t] * wrow[t]
             self._lnpool_bwd(dpooled, wrow, x_final, lnw, mean, rstd, g, g16, gw, gb, ws, d)
         return g, g16
@@ -125,7 +125,7 @@ class PaddedLayout(_Layout):
                  tr.config.layer_norm_eps, mode)
 
     def _lnpool_bwd(self, dpooled, wrow, x, lnw, mean, rstd, g, g16, gw, gb, ws, d):
-        hip.call("oneprot_layernorm_bwd", dpooled, 2, wrow, self.L, x, 0, lnw, mean, rstd, None, g, g16, gw, gb, ws, self.T, d, 0)
+        hip.layernorm_bwd(dpooled, 2, x, lnw, mean, rstd, g, gw, gb, ws, self.T, d, wrow=wrow, L=self.L, dx16=g16)
 
     def _pool(self, x, pad, pooled, d, mode):
         hip.call("oneprot_pool_fwd", x, self.ids, pad, pooled, self.B, self.L, d, mode)

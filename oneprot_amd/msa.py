@@ -192,9 +192,6 @@ class MsaTransformer(ArenaModule):
         if not tokens.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
 
-    def _gemm(self, a, w, M, N, K, epi, bias, out0, aux=None):
-        hip.call("oneprot_gemm_bf16_nt", a, w, M, N, K, K, K, epi, bias, out0, None, None, aux, None, None, 1.0, 0, 0, 0)
-
     @torch.no_grad()
     def run_layers(self, tokens, save=False, drop=False):
         """tokens int64 [B, R, L] -> (pre-final-LayerNorm hidden state fp32 [B*R*L, d], None).  drop=True: fair-esm's train-mode forward -- one call id is
@@ -233,13 +230,13 @@ class MsaTransformer(ArenaModule):
                 p = f"layers.{i}.{blk}."
                 if self.stages is not None:
                     self.stages.append((blk[:3], i, x.clone()))
-                hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
+                hip.layernorm_fwd(x, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), T, d, eps, y16=h)
                 if blk == "column_self_attention" and R == 1:       # one row: softmax over a single key (fair-esm ColumnSelfAttention.forward)
-                    self._gemm(h, self._w16(p + "layer.v_proj.weight"), T, d, d, hip.EPI_BF16, self.view(p + "layer.v_proj.bias"), ctx)
+                    hip.gemm_nt(h, self._w16(p + "layer.v_proj.weight"), T, d, d, hip.EPI_BF16, ctx, bias=self.view(p + "layer.v_proj.bias"))
                 else:
                     o, n = self.span(p + "layer.q_proj.weight", p + "layer.v_proj.weight")
                     ob, nb = self.span(p + "layer.q_proj.bias", p + "layer.v_proj.bias")
-                    self._gemm(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_BF16, self.flat.data[ob:ob + nb], qkv)
+                    hip.gemm_nt(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_BF16, qkv, bias=self.flat.data[ob:ob + nb])
                     if blk == "row_self_attention":
                         for b0, b1 in groups:
                             t0, t1 = b0 * R * L, b1 * R * L
@@ -259,21 +256,21 @@ class MsaTransformer(ArenaModule):
                     one_row = blk == "column_self_attention" and R == 1
                     self.stages.append((blk[:3] + (".v" if one_row else ".qkv"), i, (ctx if one_row else qkv).clone()))
                 if drop:        # NormalizedResidualBlock: x = residual + dropout(layer(layer_norm(x))) -- the add leaves the GEMM epilogue so that the mask sits between
-                    self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_F32, self.view(p + "layer.out_proj.bias"), y)
+                    hip.gemm_nt(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_F32, y, bias=self.view(p + "layer.out_proj.bias"))
                     hip.call("oneprot_dropout_add_f32", y, x, x, T * d, p_h, seed, self._drop_stream(call, i, 1 if blk == "row_self_attention" else 3))
                 else:
-                    self._gemm(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, self.view(p + "layer.out_proj.bias"), x, aux=x)
+                    hip.gemm_nt(ctx, self._w16(p + "layer.out_proj.weight"), T, d, d, hip.EPI_BIAS_RESID, x, bias=self.view(p + "layer.out_proj.bias"), aux=x)
             p = f"layers.{i}.feed_forward_layer."
             if self.stages is not None:
                 self.stages.append(("ffn", i, x.clone()))
-            hip.call("oneprot_layernorm_fwd", x, 0, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), h, None, None, None, T, d, eps)
-            self._gemm(h, self._w16(p + "layer.fc1.weight"), T, f, d, hip.EPI_BIAS_GELU, self.view(p + "layer.fc1.bias"), u)
+            hip.layernorm_fwd(x, self.view(p + "layer_norm.weight"), self.view(p + "layer_norm.bias"), T, d, eps, y16=h)
+            hip.gemm_nt(h, self._w16(p + "layer.fc1.weight"), T, f, d, hip.EPI_BIAS_GELU, u, bias=self.view(p + "layer.fc1.bias"))
             if drop:            # FeedForwardNetwork: fc2(activation_dropout(gelu(fc1(x)))), then the block's own dropout
                 hip.call("oneprot_dropout_bf16", u, u_drop, T * f, p_f, seed, self._drop_stream(call, i, 4))
-                self._gemm(u_drop, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_F32, self.view(p + "layer.fc2.bias"), y)
+                hip.gemm_nt(u_drop, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_F32, y, bias=self.view(p + "layer.fc2.bias"))
                 hip.call("oneprot_dropout_add_f32", y, x, x, T * d, p_h, seed, self._drop_stream(call, i, 5))
             else:
-                self._gemm(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, self.view(p + "layer.fc2.bias"), x, aux=x)
+                hip.gemm_nt(u, self._w16(p + "layer.fc2.weight"), T, d, f, hip.EPI_BIAS_RESID, x, bias=self.view(p + "layer.fc2.bias"), aux=x)
         if self.stages is not None:
             self.stages.append(("out", self.n_layers, x.clone()))
         return x, None
@@ -285,8 +282,7 @@ class MsaTransformer(ArenaModule):
         x, _ = self.run_layers(tokens, drop=drop)
         B, R, L = tokens.shape
         y = torch.empty_like(x)
-        hip.call("oneprot_layernorm_fwd", x, 0, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), None, y, None, None,
-                 B * R * L, self.d, self.config.layer_norm_eps)
+        hip.layernorm_fwd(x, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), B * R * L, self.d, self.config.layer_norm_eps, y32=y)
         return {"representations": {self.n_layers: y.view(B, R, L, self.d)}}
 
     @classmethod
