@@ -399,6 +399,45 @@ int oneprot_msa_row_context_dropout(const float* S, const void* qkv, const float
                                     int L, int H, int hd, int b_first, float p, uint64_t seed, uint64_t stream_id, void* stream);
 int oneprot_msa_col_attn_dropout(const void* qkv, const float* key_bias, void* ctx, int B, int R, int L, int H, int hd, float scale, float p, uint64_t seed,
                                  uint64_t stream_id, void* stream);
+/* Ragged batches: a stream of n MSAs, each a dense R_b x L_b block at its own depth and length (host type oneprot_amd.packing.PackedMsa).  Token
+   t = cu_tokens[b] + r * L_b + l of a stream of T_pad rows (a multiple of 256), the tail [T_tokens, T_pad) filled with the pad id.  What is cut is an MSA's
+   trailing all-pad rows and columns, and the cut is exact: in the published forward such a row has q = 0 and is an excluded key of the column attention,
+   such a column is a masked key of the row attention (row 0 is padded there), and positions and the row embedding do not look past a token's own row
+   (fair-esm RowSelfAttention.compute_attention_weights, ColumnSelfAttention.compute_attention_update, LearnedPositionalEmbedding).  Each call below
+   gives, at every position of a block, the bits its padded twin above gives there on the padded batch.  One number of the padded batch is kept: the
+   row scale hd^-1/2 / sqrt(R) of RowSelfAttention.align_scaling uses the PADDED row count, so `scale` is the caller's.
+   geo: int64 [n, 8] on the device, 16-byte aligned, one row per MSA of the call in launch order (the host puts the longest first):
+     {tok0, R_b, L_b, s0, p0, vt0, b, 0} = first token of the block in the stream; its shape; where its S [H, L_b, L_b] starts (fp32 elements of S), where
+     its P [H, L_b, Lp_b] and Vt [H, R_b, 64, Lp_b] start (bf16 elements from the start of the workspace, Lp_b = L_b rounded up to 32); the MSA's index
+     (for the dropout streams).  The table lives on the device and is NOT validated: the host type builds it.  max_R / max_L: the largest R_b / L_b of
+     the call (the launch grid; a work-group outside its own MSA's extent leaves before any barrier).  n * H <= 65535, max_L <= ONEPROT_MSA_MAX_LEN.
+   Every ragged attention call writes the tail rows of ctx as 0, as oneprot_attn_varlen_fwd does. */
+/* oneprot_msa_embed_fwd per block: row index and position count run inside the token's own R_b x L_b block (fair-esm MSATransformer.forward,
+   LearnedPositionalEmbedding); cu_tokens int32 [n + 1], row_lens int32 [n] = L_b; tail rows of x are written as 0.  max_R <= n_rows,
+   max_L + pad_id + 1 <= n_pos. */
+int oneprot_msa_embed_ragged_fwd(const int64_t* tokens, const int* cu_tokens, const int* row_lens, const float* tok_table, const float* pos_table,
+                                 const float* row_table, const float* gamma, const float* beta, float* x, int n, int T_pad, int max_R, int max_L, int d, int vocab,
+                                 int n_pos, int n_rows, int pad_id, float eps, void* stream);
+/* oneprot_msa_row_scores per block (fair-esm RowSelfAttention.compute_attention_weights): S = the concatenation of the per-MSA [H, L_b, L_b] maps at
+   their s0; rows r = 0 .. R_b - 1 in that order, no split, no atomics. */
+int oneprot_msa_row_scores_ragged(const void* qkv, const float* key_bias, float* S, const int64_t* geo, int n, int max_L, int H, int hd, float scale, void* stream);
+/* oneprot_msa_row_context per block (fair-esm RowSelfAttention.compute_attention_update).  sum_l_lp = sum of L_b * Lp_b, sum_r_lp = sum of R_b * Lp_b over
+   the call's MSAs (both multiples of 32): the workspace holds H * (sum_l_lp + 64 * sum_r_lp) bf16 (the query returns 0 for invalid arguments). */
+size_t oneprot_msa_row_context_ragged_workspace(int64_t sum_l_lp, int64_t sum_r_lp, int H);
+int oneprot_msa_row_context_ragged(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes, const int64_t* geo,
+                                   int n, int max_R, int max_L, int64_t sum_l_lp, int64_t sum_r_lp, int H, int hd, int T_tokens, int T_pad, void* stream);
+/* oneprot_msa_col_attn per block (fair-esm ColumnSelfAttention.compute_attention_update), 1 <= R_b <= ONEPROT_MSA_MAX_ROWS: R_b = 1 has one live key, so
+   P = 1 and ctx = v, which is what the padded kernel gives that MSA inside a deeper batch. */
+int oneprot_msa_col_attn_ragged(const void* qkv, const float* key_bias, void* ctx, const int64_t* geo, int n, int max_R, int max_L, int H, int hd, float scale,
+                                int T_tokens, int T_pad, void* stream);
+/* Their train-mode twins (fair-esm `attn_probs = self.dropout_module(attn_probs)` in both attentions): the mask element of the padded batch the stream
+   stands for.  Row: keep(q = i, k = j, bh = (b_first + b) * H + h) with b the table's index; column: keep(q = i, k = j, bh = (b * H + h) * l_stride + l)
+   with l_stride the padded batch's L (max_L <= l_stride <= ONEPROT_MSA_MAX_LEN).  Refusals of p as above. */
+int oneprot_msa_row_context_ragged_dropout(const float* S, const void* qkv, const float* key_bias, void* ctx, void* workspace, size_t workspace_bytes,
+                                           const int64_t* geo, int n, int max_R, int max_L, int64_t sum_l_lp, int64_t sum_r_lp, int H, int hd, int T_tokens,
+                                           int T_pad, int b_first, float p, uint64_t seed, uint64_t stream_id, void* stream);
+int oneprot_msa_col_attn_ragged_dropout(const void* qkv, const float* key_bias, void* ctx, const int64_t* geo, int n, int max_R, int max_L, int H, int hd,
+                                        float scale, int T_tokens, int T_pad, int l_stride, float p, uint64_t seed, uint64_t stream_id, void* stream);
 
 #ifdef __cplusplus
 }

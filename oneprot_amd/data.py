@@ -10,13 +10,14 @@ checkpoint wire format (section 8f #3).
   foldseek letters 33..52; text: cls 2 / sep 3 / pad 0, body 5..vocab-1), seeded, optionally ragged with right padding; `packed=True` yields the
   same sequences as `ragged=True` (same seed) with the ESM sides as oneprot_amd.packing.PackedTokens streams; a text side stays padded unless
   `packed_text=True`, which packs it with BERT's pad id 0.  Modality "msa" (ref msa_dataset.py's batches): tokens [B, msa_depth, Lm] over the 33-symbol
-  alphabet, cls 0 in column 0, pad 1; ragged MSAs are shorter AND shallower (trailing rows fully padded); the MSA side is never packed.
+  alphabet, cls 0 in column 0, pad 1; ragged MSAs are shorter AND shallower (trailing rows fully padded); the MSA side stays padded unless `packed_msa=True`, which yields it as an
+  oneprot_amd.packing.PackedMsa (each MSA at its own depth and length; off by default, like `packed_text`, and independent of `packed`).
 * `save_checkpoint` / `load_weights_only` -- Lightning-style {"state_dict": {...}} files with the reference's key names
   (`network.<modality>.transformer....`), loaded exactly as ref src/train.py:73-82 does (optional 'model.' prefix, strict=True, weights only).
 """
 import torch
 
-from .packing import PackedTokens
+from .packing import PackedMsa, PackedTokens
 
 
 class CombinedLoader:
@@ -50,12 +51,13 @@ class SyntheticPairs:
     """Re-iterable synthetic (sequence, modality) batches for one modality."""
 
     def __init__(self, modality, batch_size, seq_len, mod_len=None, n_batches=1, seed=1881, device="cpu", ragged=False, text_vocab=30522, packed=False,
-                 packed_text=False, msa_depth=8):
+                 packed_text=False, msa_depth=8, packed_msa=False):
         self.modality, self.B, self.Ls, self.Lm = modality, batch_size, seq_len, mod_len or seq_len
         self.n, self.seed, self.device, self.text_vocab = n_batches, seed, device, text_vocab
         self.ragged, self.packed = ragged or packed, packed
         self.packed_text = bool(packed and packed_text)
         self.msa_depth = int(msa_depth)
+        self.packed_msa = bool(packed_msa)
 
     def __len__(self):
         return self.n
@@ -92,6 +94,8 @@ class SyntheticPairs:
                 mod = self._msa_frame(gen, self.B, self.msa_depth, self.Lm, self.ragged)
                 if self.packed:
                     seq = PackedTokens.from_padded(seq, pad_id=1)
+                if self.packed_msa:
+                    mod = PackedMsa.from_padded(mod, pad_id=1)
                 yield seq.to(self.device), mod.to(self.device), self.modality, None
                 continue
             if self.modality == "text":

@@ -22,7 +22,7 @@ from . import hip
 from . import layout
 from .layout import _ws
 from .esm import EsmTransformer, resolve_config, ModelConfig, recompute_plan
-from .packing import PackedTokens
+from .packing import PackedMsa, PackedTokens
 
 
 # ------------------------------------------------------------------------------------------------- small modules
@@ -619,7 +619,7 @@ class TextEncoder(BaseEncoder):
 
 class MsaEncoder(BaseEncoder):
     """ref msa_encoder.py:6-55: the frozen MSA Transformer tower (oneprot_amd/msa.py; esm_msa1b_t12_100M_UR50S architecture) behind the reference's
-    signature.  `forward(tokens[B, R, L] int64, padding id 1) -> float32 [B, output_dim]`: representation 12, then the masked mean over every non-pad
+    signature.  `forward(tokens[B, R, L] int64, padding id 1 -- or an oneprot_amd.packing.PackedMsa, a ragged batch of N MSAs) -> float32 [B, output_dim]`: representation 12, then the masked mean over every non-pad
     (r, l) (`use_all_msa=True`) or row 0 through `self.pooling`, then proj -> norm.  The tower is always frozen and its own `.training` stays False; parity with
     fair-esm is unpinned (no fair-esm, no checkpoint: tests/msa_ref.py is the oracle).  `d_model` follows the loaded architecture (768 for the published
     model, which the reference hard-codes).
@@ -657,6 +657,8 @@ class MsaEncoder(BaseEncoder):
         if mode not in (0, 1):
             raise NotImplementedError(f"MsaEncoder(use_all_msa=False): pooling_type {self.pooling_type!r} is not built for row 0 of the MSA; use 'mean' or 'cls' "
                                       "(use_all_msa=True ignores the pooling, as in the reference)")
+        if isinstance(tokens, PackedMsa):
+            return self._hidden_and_pooled_packed(tokens, mode, want_hidden)
         with torch.no_grad():
             x, _ = tr.run_layers(tokens, drop=bool(self.training and tr.dropout_enabled()))
             B, R, L = tokens.shape
@@ -669,6 +671,27 @@ class MsaEncoder(BaseEncoder):
             hip.call("oneprot_lnpool_fwd", x, ids, pad, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None, None, None,
                      None, hidden, B, n, d, tr.config.layer_norm_eps, mode)
         return (hidden.view(B, R, L, d) if (self.use_all_msa and want_hidden) else hidden), pooled
+
+    def _hidden_and_pooled_packed(self, pk, mode, want_hidden):
+        """a PackedMsa: (representation n_layers as a stream fp32 [T_pad, d] -- `pk.unpack` gives the [R_b, L_b, d] blocks; for row 0 the list of the N
+        [L_b, d] row-0 representations --, pooled [N, d] in MSA order).  Pooling per segment of the stream (oneprot_lnpool_packed_fwd, which walks a
+        segment of any length): every MSA's R_b * L_b tokens with cu_tokens as the segment table, or its row 0 gathered into a small stream of its own."""
+        tr = self.transformer
+        with torch.no_grad():
+            x, _ = tr.run_layers(pk, drop=bool(self.training and tr.dropout_enabled()))
+            N, d, dev, pad, ids, cu, T = len(pk), tr.d, pk.device, tr.config.padding_idx, pk.ids, pk.cu_tokens, pk.T_pad
+            if not self.use_all_msa:
+                idx, cu, _ = pk.row0()
+                x, ids, T = x.index_select(0, idx), ids.index_select(0, idx), idx.numel()
+            pooled, hidden = torch.empty(N, d, device=dev), (torch.empty(T, d, device=dev) if want_hidden else None)
+            hip.call("oneprot_lnpool_packed_fwd", x, ids, cu, pad, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None,
+                     None, None, hidden, N, T, d, tr.config.layer_norm_eps, mode)
+            if want_hidden and not self.use_all_msa:
+                c = [0]
+                for _, l in pk.shapes:
+                    c.append(c[-1] + l)
+                hidden = [hidden[a:b] for a, b in zip(c[:-1], c[1:])]
+        return hidden, pooled
 
     def forward(self, tokens):
         return self.apply_head(self.hidden_and_pooled(tokens, want_hidden=False)[1])

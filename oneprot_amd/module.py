@@ -22,7 +22,7 @@ from . import distributed as D
 from .loss import ClipLoss, SigLipLoss, l1_penalty
 from .metrics import RetrievalMetric
 from .optim import FusedAdam, clip_grad_norm_
-from .packing import PackedTokens, batch_size
+from .packing import PackedMsa, PackedTokens, batch_size
 
 try:                                                    # pragma: no cover  (not installed in the build image)
     from pytorch_lightning import LightningModule as _LightningBase
@@ -186,7 +186,7 @@ class OneProtLitModule(_Base):
     @staticmethod
     def _check_pair(sequence_inputs, modality_inputs, modality):
         """a pair whose towers take packed streams (oneprot_amd.packing) must still be a pair: the same number of sequences on both sides"""
-        if isinstance(sequence_inputs, PackedTokens) or isinstance(modality_inputs, PackedTokens):
+        if isinstance(sequence_inputs, (PackedTokens, PackedMsa)) or isinstance(modality_inputs, (PackedTokens, PackedMsa)):
             ns, nm = batch_size(sequence_inputs), batch_size(modality_inputs)
             if ns != nm:
                 raise ValueError(f"{modality} batch: the sequence tower has {ns} sequences and the {modality} tower {nm}; a contrastive pair needs the same number")

@@ -22,6 +22,13 @@ Per layer: LayerNorm -> one QKV GEMM (bf16 [T, 3d]) -> tied row attention (onepr
 the same with oneprot_msa_col_attn (R = 1: out_proj(v_proj(x)), as published); LayerNorm -> FFN-1 + GELU -> FFN-2 + residual.  The row-attention score
 map S [B, H, L, L] fp32 is the one large temporary (its bf16 probabilities and the transposed V of the same MSAs ride along in a workspace): the row
 attention runs in groups of whole MSAs so that S stays under ONEPROT_MSA_SCORE_BYTES (default 1 GiB); the grouping is a pure function of (B, R, L, budget) and cannot change a bit of the result (every MSA is computed by its own work-groups).
+
+RAGGED BATCHES.  `run_layers` / `forward` also take an oneprot_amd.packing.PackedMsa -- a stream of MSAs, each a dense R_b x L_b block at its own depth and
+length.  The row-wise stages run on the stream's T_pad rows as they are; the embedding and the two attentions use the *_ragged entry
+points (one kernel body behind two geometry decoders, csrc/msa.hip); the row scale and the one-row shortcut take R from `padded_shape`, the padded batch the
+stream stands for.  At every position of a block the attention calls give the padded batch's bits, dropped probabilities included; the hidden and activation
+dropout masks index the stream's own flat [T_pad, d] / [T_pad, f] element: the same distribution as the padded batch's, another draw.  A PackedTokens stream is
+refused as before.
 """
 import os
 import warnings
@@ -30,7 +37,7 @@ import torch
 
 from . import hip
 from .esm import ArenaModule, ModelConfig
-from .packing import PackedTokens
+from .packing import PackedMsa, PackedTokens
 
 MSA_DEFAULTS = dict(model_type="msa_transformer", num_layers=12, embed_dim=768, ffn_embed_dim=3072, attention_heads=12, max_positions=1024,
                     embed_positions_msa=True, msa_rows=1024, vocab_size=33, padding_idx=1, cls_idx=0, eos_idx=2, mask_idx=32, layer_norm_eps=1e-5)
@@ -53,6 +60,22 @@ def plan_groups(B, R, L, H, budget=None):
     per = 4 * H * L * L
     g = max(1, min(B, budget // per))
     return [(b0, min(b0 + g, B)) for b0 in range(0, B, g)]
+
+
+def plan_groups_ragged(shapes, H, budget=None):
+    """plan_groups for a ragged batch: [(b0, b1), ...] consecutive groups of whole MSAs whose fp32 score maps, sum of 4 * H * L_b^2 bytes, fit `budget`
+    together (an MSA whose own map does not is a group by itself).  A pure function of the shapes [(R_b, L_b)], H and the budget; every MSA is computed by
+    its own work-groups, so the grouping cannot change a bit."""
+    budget = score_bytes_budget() if budget is None else int(budget)
+    groups, b0, used = [], 0, 0
+    for b, (_, l) in enumerate(shapes):
+        per = 4 * H * l * l
+        if b > b0 and used + per > budget:
+            groups.append((b0, b))
+            b0, used = b, 0
+        used += per
+    groups.append((b0, len(shapes)))
+    return groups
 
 
 def upgrade_fair_esm_state_dict(sd):
@@ -85,7 +108,7 @@ def config_from_args(args):
 
 class MsaTransformer(ArenaModule):
     final_layer_norm = True
-    accepts_packed = False
+    accepts_packed = False                # no PackedTokens stream (an ESM / BERT input); its own packed input is the PackedMsa
     max_rows = hip.MSA_MAX_ROWS           # deepest MSA the column-attention kernel takes in one pass
 
     def __init__(self, config):
@@ -181,10 +204,23 @@ class MsaTransformer(ArenaModule):
         """every refusal, before anything touches the device"""
         if isinstance(tokens, PackedTokens):
             raise NotImplementedError("MsaEncoder: packed token streams are an ESM-tower input; the MSA tower takes padded [B, R, L] tokens")
+        cfg = self.config
+        if isinstance(tokens, PackedMsa):               # a ragged batch: the type has refused the kernels' own limits; here the checkpoint's
+            if tokens.pad_id != cfg.padding_idx:
+                raise ValueError(f"MsaEncoder: the stream was packed with pad id {tokens.pad_id}, the tower's is {cfg.padding_idx}")
+            R, L = (max(v) for v in zip(*tokens.shapes))
+            if L > cfg.max_positions:
+                raise ValueError(f"sequence length {L} exceeds max_positions {min(cfg.max_positions, hip.MSA_MAX_LEN)}")
+            if R > cfg.msa_rows:
+                raise NotImplementedError(f"MSA depth {R}: the column-attention kernel takes up to {min(self.max_rows, cfg.msa_rows)} rows in one pass")
+            if len(tokens) * self.H > 65535:
+                raise ValueError(f"{len(tokens)} MSAs in one stream: the attention kernels take up to {65535 // self.H}")
+            if not tokens.is_cuda:
+                raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
+            return
         if tokens.dim() != 3:
             raise ValueError(f"MSA tokens must be [B, R, L], got {tuple(tokens.shape)}")
         B, R, L = tokens.shape
-        cfg = self.config
         if L > cfg.max_positions or L > hip.MSA_MAX_LEN:
             raise ValueError(f"sequence length {L} exceeds max_positions {min(cfg.max_positions, hip.MSA_MAX_LEN)}")
         if R > self.max_rows or R > cfg.msa_rows:
@@ -195,23 +231,37 @@ class MsaTransformer(ArenaModule):
     @torch.no_grad()
     def run_layers(self, tokens, save=False, drop=False):
         """tokens int64 [B, R, L] -> (pre-final-LayerNorm hidden state fp32 [B*R*L, d], None).  drop=True: fair-esm's train-mode forward -- one call id is
-        drawn and every dropout site applies its mask (module docstring)."""
+        drawn and every dropout site applies its mask (module docstring).
+        tokens a PackedMsa -> the same on its stream, fp32 [T_pad, d]: every row-wise stage runs on the T_pad rows as they are, the embedding and the two
+        attentions follow the blocks (the *_ragged entry points), R of the row scale and of the one-row shortcut is the padded batch's."""
         self.check_input(tokens)
         if save:
             raise NotImplementedError("the MSA tower is frozen: there is no backward")
         self._refresh_bf16_mirror()
         cfg = self.config
-        tokens = tokens.contiguous()
-        B, R, L = tokens.shape
-        T, d, f, H, hd, dev = B * R * L, self.d, self.f, self.H, self.hd, tokens.device
+        pk = tokens if isinstance(tokens, PackedMsa) else None
+        if pk is not None:
+            tokens, (R, L), B = pk.ids, pk.padded_shape, len(pk)
+            T, Tn = pk.T_pad, pk.n_tokens
+        else:
+            tokens = tokens.contiguous()
+            B, R, L = tokens.shape
+            T = B * R * L
+        d, f, H, hd, dev = self.d, self.f, self.H, self.hd, tokens.device
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
         eps, pad = cfg.layer_norm_eps, cfg.padding_idx
         kb, x = f32(T), f32(T, d)
         hip.call("oneprot_key_padding_bias", tokens, kb, T, pad)
-        hip.call("oneprot_msa_embed_fwd", tokens, self.view("embed_tokens.weight"), self.view("embed_positions.weight"), self.view("msa_position_embedding"),
-                 self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, R, L, d, cfg.vocab_size,
-                 cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
+        if pk is not None:
+            whole = pk.tables(H)[0]                     # the whole stream as one call: embedding bounds and the column attention
+            hip.call("oneprot_msa_embed_ragged_fwd", tokens, pk.cu_tokens, pk.row_lens(), self.view("embed_tokens.weight"), self.view("embed_positions.weight"),
+                     self.view("msa_position_embedding"), self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, T,
+                     whole["max_R"], whole["max_L"], d, cfg.vocab_size, cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
+        else:
+            hip.call("oneprot_msa_embed_fwd", tokens, self.view("embed_tokens.weight"), self.view("embed_positions.weight"), self.view("msa_position_embedding"),
+                     self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, R, L, d, cfg.vocab_size,
+                     cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
         if drop:
             call, seed = self._next_drop_call(), self._drop_seed
             p_h, p_a, p_f = self._drop_probs()
@@ -219,10 +269,16 @@ class MsaTransformer(ArenaModule):
                                                         # its operands __restrict__ and the header does not allow y = x for it, unlike the fp32 kernels)
             # MSATransformer.forward: emb_layer_norm_before -> dropout_module -> x * (1 - padding_mask); the kernel above has zeroed the padding already
             hip.call("oneprot_dropout_f32", x, x, T * d, p_h, seed, self._drop_stream(call, -1, 0))
-        groups = plan_groups(B, R, L, H)
-        gmax = max(b1 - b0 for b0, b1 in groups)
-        S = f32(gmax, H, L, L)
-        ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", gmax, R, L, H), dtype=torch.uint8, device=dev)     # probabilities + V transposed, per group
+        if pk is not None:
+            groups = pk.tables(H, plan_groups_ragged(pk.shapes, H))
+            S = f32(max(g["s_elems"] for g in groups))
+            ws = torch.empty(max(hip.query("oneprot_msa_row_context_ragged_workspace", g["sum_l_lp"], g["sum_r_lp"], H) for g in groups), dtype=torch.uint8,
+                             device=dev)
+        else:
+            groups = plan_groups(B, R, L, H)
+            gmax = max(b1 - b0 for b0, b1 in groups)
+            S = f32(gmax, H, L, L)
+            ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", gmax, R, L, H), dtype=torch.uint8, device=dev)     # probabilities + V transposed, per group
         h, qkv, ctx, u = b16(T, d), b16(T, 3 * d), b16(T, d), b16(T, f)
         row_scale = hd ** -0.5 / R ** 0.5               # R = the padded row count, as published
         for i in range(self.n_layers):
@@ -237,7 +293,22 @@ class MsaTransformer(ArenaModule):
                     o, n = self.span(p + "layer.q_proj.weight", p + "layer.v_proj.weight")
                     ob, nb = self.span(p + "layer.q_proj.bias", p + "layer.v_proj.bias")
                     hip.gemm_nt(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_BF16, qkv, bias=self.flat.data[ob:ob + nb])
-                    if blk == "row_self_attention":
+                    if pk is not None and blk == "row_self_attention":
+                        for g in groups:
+                            hip.call("oneprot_msa_row_scores_ragged", qkv, kb, S, g["geo"], g["n"], g["max_L"], H, hd, row_scale)
+                            geom = (g["geo"], g["n"], g["max_R"], g["max_L"], g["sum_l_lp"], g["sum_r_lp"], H, hd, Tn, T)
+                            if drop:
+                                hip.call("oneprot_msa_row_context_ragged_dropout", S, qkv, kb, ctx, ws, ws.numel(), *geom, g["b_first"], p_a, seed,
+                                         self._drop_stream(call, i, 0))
+                            else:
+                                hip.call("oneprot_msa_row_context_ragged", S, qkv, kb, ctx, ws, ws.numel(), *geom)
+                    elif pk is not None:                # the column attention: one call over the stream; a block of one row inside a deeper batch is the kernel's
+                        geom = (whole["geo"], B, whole["max_R"], whole["max_L"], H, hd, hd ** -0.5, Tn, T)
+                        if drop:
+                            hip.call("oneprot_msa_col_attn_ragged_dropout", qkv, kb, ctx, *geom, L, p_a, seed, self._drop_stream(call, i, 2))
+                        else:
+                            hip.call("oneprot_msa_col_attn_ragged", qkv, kb, ctx, *geom)
+                    elif blk == "row_self_attention":
                         for b0, b1 in groups:
                             t0, t1 = b0 * R * L, b1 * R * L
                             hip.call("oneprot_msa_row_scores", qkv[t0:t1], kb[t0:t1], S, b1 - b0, R, L, H, hd, row_scale)
@@ -280,9 +351,11 @@ class MsaTransformer(ArenaModule):
         """MSATransformer-compatible call: {"representations": {n_layers: [B, R, L, d]}} (the last representation, after emb_layer_norm_after);
         drop=True: with fair-esm's train-mode dropouts (run_layers)"""
         x, _ = self.run_layers(tokens, drop=drop)
-        B, R, L = tokens.shape
         y = torch.empty_like(x)
-        hip.layernorm_fwd(x, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), B * R * L, self.d, self.config.layer_norm_eps, y32=y)
+        hip.layernorm_fwd(x, self.view("emb_layer_norm_after.weight"), self.view("emb_layer_norm_after.bias"), x.shape[0], self.d, self.config.layer_norm_eps, y32=y)
+        if isinstance(tokens, PackedMsa):               # the representation as the stream [T_pad, d] (PackedMsa.unpack gives the blocks)
+            return {"representations": {self.n_layers: y}}
+        B, R, L = tokens.shape
         return {"representations": {self.n_layers: y.view(B, R, L, self.d)}}
 
     @classmethod

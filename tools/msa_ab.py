@@ -14,7 +14,11 @@ Per-kernel shares come from a kernel trace taken in a run of its own:
 --dropout: a second comparison at the same two shapes, HIP against HIP -- the default forward and the forward with fair-esm's train-mode dropouts
 (`drop=True`: masked row / column probabilities, six Philox passes per layer), alternating in one process; the medians and their ratio are ADDED to the JSON
 written before under "dropout_ab" (the other keys stay).  A record of the cost, not a gate.
-usage: msa_ab.py [--only NAME[,NAME]] [--reps 5] [--out profiles/msa_encoder.json] [--small] [--hip-only] [--dropout]"""
+--ragged: a third comparison at the same two shapes, HIP against HIP -- the padded [B, R, L] batch against the same MSAs as an oneprot_amd.packing.PackedMsa
+(each MSA at its own depth and length), alternating in one process; ADDED to the JSON written before under "ragged_ab".  Two cases per shape: "ragged", the
+MSAs drawn by SyntheticPairs' ragged rule (seed 50) -- GATE: the packed median is lower than the padded median by more than the larger of the two spreads --
+and "control", the same frames with no padding at all, where only the packed / padded ratio is recorded (the cost of the geometry decoder at full blocks).
+usage: msa_ab.py [--only NAME[,NAME]] [--reps 5] [--out profiles/msa_encoder.json] [--small] [--hip-only] [--dropout] [--ragged]"""
 import argparse
 import csv
 import glob
@@ -105,6 +109,40 @@ def run_dropout_ab(tr, name, reps, small):
     return out
 
 
+def run_ragged_ab(tr, name, reps, small):
+    """padded against packed on the same MSAs: the ragged draw (gated) and the full frames (control)"""
+    import torch
+    from oneprot_amd.data import SyntheticPairs
+    from oneprot_amd.packing import PackedMsa
+    B, R, L = (SMALL if small else SHAPES)[name]
+    n = tr.n_layers
+    out = {"B": B, "R": R, "L": L}
+    for case, ragged in (("ragged", True), ("control", False)):
+        tok = SyntheticPairs._msa_frame(torch.Generator().manual_seed(50), B, R, L, ragged).cuda()
+        pk = PackedMsa.from_padded(tok)
+        variants = {"padded": lambda: tr(tok)["representations"][n], "packed": lambda: tr(pk)["representations"][n]}
+        res = {k: f() for k, f in variants.items()}                    # warm-up (builds the packed batch's device tables once, as a data loader's batch would carry them)
+        torch.cuda.synchronize()
+        diff = max(float((a - b[:r, :l]).abs().max()) for a, b, (r, l) in zip(pk.unpack(res["packed"]), res["padded"], pk.shapes))
+        del res
+        ms = {k: [] for k in variants}
+        for _ in range(reps):
+            for k, f in variants.items():                              # alternating
+                timed(f, ms[k])
+        c = out[case] = {"tokens_padded": B * R * L, "tokens_packed": pk.n_tokens, "stream_rows": pk.T_pad, "token_ratio": pk.T_pad / (B * R * L),
+                         "score_element_ratio": sum(l * l for _, l in pk.shapes) / (B * L * L),
+                         "score_work_ratio": sum(r * l * l for r, l in pk.shapes) / (B * R * L * L), "max_abs_difference_packed_vs_padded": diff}
+        for k in variants:
+            c[k] = stats(ms[k])
+        c["packed_over_padded"] = c["packed"]["median_ms"] / c["padded"]["median_ms"]
+        if ragged:
+            allowed = max(c["padded"]["spread_ms"], c["packed"]["spread_ms"])
+            c["gate"] = {"rule": "packed median < padded median - max(spread of either)", "margin_ms": allowed,
+                         "passed": bool(c["packed"]["median_ms"] < c["padded"]["median_ms"] - allowed)}
+        torch.cuda.empty_cache()
+    return out
+
+
 def fold_trace(trace_dir, out_path):
     groups = (("k_msa_row_scores", "msa_row_scores"), ("k_msa_row_softmax", "msa_row_context"), ("k_msa_v_transpose", "msa_row_context"),
               ("k_msa_row_pv", "msa_row_context"), ("k_msa_col_attn", "msa_col_attn"), ("k_msa_embed", "msa_embed"),
@@ -135,6 +173,7 @@ def main():
     ap.add_argument("--hip-only", action="store_true", help="run the HIP variant alone (for the kernel trace)")
     ap.add_argument("--fold-trace", default=None)
     ap.add_argument("--dropout", action="store_true", help="default forward against the forward with the train-mode dropouts; adds dropout_ab to --out")
+    ap.add_argument("--ragged", action="store_true", help="padded batch against the same MSAs as a PackedMsa; adds ragged_ab to --out")
     a = ap.parse_args()
     if a.fold_trace:
         return fold_trace(a.fold_trace, a.out)
@@ -152,6 +191,16 @@ def main():
             ab[name] = run_dropout_ab(tr, name, max(a.reps, 1), a.small)
             print(name, json.dumps(ab[name]), flush=True)
             torch.cuda.empty_cache()
+        if a.out != "/dev/null":
+            json.dump(doc, open(a.out, "w"), indent=1)
+        return
+    if a.ragged:
+        doc = json.load(open(a.out)) if a.out != "/dev/null" and os.path.exists(a.out) else {}
+        ab = doc["ragged_ab"] = {"device": torch.cuda.get_device_name(0), "small_shapes": a.small,
+                                 "variants": "MsaTransformer.forward(tokens [B, R, L]) against forward(PackedMsa.from_padded(tokens)), alternating in one process"}
+        for name in a.only.split(","):
+            ab[name] = run_ragged_ab(tr, name, max(a.reps, 1), a.small)
+            print(name, json.dumps(ab[name]), flush=True)
         if a.out != "/dev/null":
             json.dump(doc, open(a.out, "w"), indent=1)
         return
