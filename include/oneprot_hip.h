@@ -139,7 +139,8 @@ int oneprot_gemm_bf16_nt_resid_ln8(const void* A, const void* W, int64_t M, int 
    work-groups on 64-row tiles, two per CU (measured 5-9 % slower: kept as a tested variant).  Bit-identical results.  oneprot_gemm_ln_form_get: the current form. */
 void oneprot_gemm_ln_form(int form);
 int oneprot_gemm_ln_form_get(void);
-/* test / tuning hook: force the block shape of oneprot_gemm_bf16_nt (0..5, see csrc/gemm_nt.hip; -1 = heuristic). */
+/* test / tuning hook: force the kernel form of oneprot_gemm_bf16_nt (negative = heuristic; 0..8 per-tile block shapes, 17 / 19 / 20 = 1 / 3 / 4 with direct
+ * stores, 32 (+ 64 * n) ping-pong, 40 / 41 / 42 the 8-phase forms: see csrc/gemm_nt.hip).  With any other id set, oneprot_gemm_bf16_nt returns OP_EINVAL. */
 void oneprot_gemm_force_shape(int shape);
 /* test / tuning hook: L2 super-tile of the per-tile kernels (sup_m row panels x sup_n column tiles per XCD at a time; <= 0 keeps a value). */
 void oneprot_gemm_tune(int sup_m, int sup_n);

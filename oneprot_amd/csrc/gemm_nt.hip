@@ -440,7 +440,8 @@ static int launch_shape_full(GemmArgs a, hipStream_t s) {
   return launch_status();
 }
 
-// FULL-tile specialisation only for the shapes the heuristic picks (keeps the number of kernel instantiations down)
+// FULL-tile specialisation (TRY_FULL) only for the shapes the heuristic picks and their direct-store forms -- 1, 3, 4, 17, 19, 20 -- which keeps the number of
+// kernel instantiations down; shapes 0, 2, 5, 6, 7 have the masked form only
 template <int EPI, int WM, int WN, int MT, int NTW, int BKT, int NSTAGE, int EPH, int MINW, bool PIPE, bool TRY_FULL = false, bool TRY_DIRECT = false>
 static int launch_shape(GemmArgs a, hipStream_t s) {
   typedef Shape<WM, WN, MT, NTW, BKT, NSTAGE, EPH> S;
@@ -970,7 +971,6 @@ __global__ void __launch_bounds__(512, 2) k_gemm_nt_pp(const GemmArgs p, int g8)
   }
 }
 
-static int g_pp_ring = 6;            // tuning hook (oneprot_gemm_force_shape(32 + 64 * ring))
 template <int EPI, bool GRAD, int NB>
 static int launch_pp3(GemmArgs a, hipStream_t s) {
   constexpr int LDS = 3 * (256 + 128) * 128;       // three 48 KB stage buffers (NB is a spare template slot for A/B variants)
@@ -1016,15 +1016,24 @@ static bool pp_eligible(const GemmArgs& a) {
 
 static int g_force_shape = -1;     // test / tuning hook, see launch_gemm
 extern "C" void oneprot_gemm_force_shape(int shape) { g_force_shape = shape; }
+// the ids launch_gemm knows (negative = automatic, as ever; 32 + 64 * ring is the ping-pong form, as the round-2 A/B tools name it); oneprot_gemm_bf16_nt refuses
+// every other id before anything is launched (an unknown id used to run shape 0 silently)
+static bool force_shape_exists(int id) {
+  return id <= 8 || id == 17 || id == 19 || id == 20 || (id >= 32 && (id & 63) == 32) || (id >= 40 && id <= 42);
+}
 
-// shapes: 0 = 128x128 (BK32, 3 stages, pipelined fragments, 48 KB LDS -> 3 blocks/CU)     1 = 256x128 (BK32, 3 stages, 72 KB -> 2 blocks/CU)
-//         2 = 256x256 (BK32, 4 stages, pipelined fragments, 128 KB)   3 = 128x128 BK64 2 stages (first version; still the best for long K)
-//         4 = 256x256 BK64 2 stages, pipelined fragments               5 = 256x256 BK32 4 stages, plain loop
-//         16 + s = shape s with the direct-store epilogue (17, 19, 20);  32 = persistent ping-pong form (opt-in: see k_gemm_nt_pp)
-// Heuristic from in-process A/B on the training shapes (tools/gemm_ab.py; all shapes lie within ~10 % of each other, vendor hipBLASLt
-// runs the same plain shapes at 650-1030 TFLOP/s): long K -> 3, wide N with short K -> 4 (20 for the single-output GELU), otherwise 1; small
-// problems -> 0.  The direct-store and ping-pong forms tie with these elsewhere (round-2 A/B: every form is bound by the same L2 -> LDS fill
-// latency), so they are only selected where they measured faster.
+// Forms (ids as oneprot_gemm_force_shape takes them), and which of them the automatic choice reaches:
+//   41 / 40   persistent 8-phase kernels of gemm_nt8.hip, 256 x 320 / 256 x 256 tiles: AUTOMATIC for every whole-tile problem of at least 192 tiles (below);
+//   42        40 with merged phases: measured equal, forced only.  Forced, 40-42 take any whole-tile problem and fall back to the per-tile choice otherwise
+//   per-tile kernels (k_gemm_nt), AUTOMATIC for everything else:
+//    0   128x128, BK32, 3 stages, pipelined fragments, 48 KB LDS -> 3 blocks/CU: M < 2048 (small problems)
+//   19   3 with the direct-store epilogue: BIAS_RESID            3   128x128, BK64, 2 stages: K >= 1024 (the best per-tile form for long K)
+//   20   4 with the direct-store epilogue: N >= 2048, forward-only GELU      4   256x256, BK64, 2 stages, pipelined fragments: N >= 2048 otherwise
+//    1   256x128, BK32, 3 stages, 72 KB -> 2 blocks/CU: the rest (N = 640-class outputs)
+//   The remaining forms are never chosen automatically; they run only when forced.  Round-2 A/B (tools/gemm_ab.py) found every per-tile form within ~10 %
+//   of the others, all bound by the same L2 -> LDS fill latency (DESIGN.md section 6 at the time, now NOTEBOOK.md section 6b), and none of these faster anywhere:
+//    2   256x256, BK32, 4 stages, pipelined fragments, 128 KB     5   2 with the plain loop     6 / 7   256x256 as 4 waves x (128x128), BK64 x2 / BK32 x4
+//    8   register-staged 256x256 (k_gemm_nt_rs; else 20)         17   1 with the direct-store epilogue     32   persistent ping-pong (k_gemm_nt_pp; else 17)
 template <int EPI>
 static int launch_gemm(const GemmArgs& a, hipStream_t s) {
   int shape;
@@ -1043,10 +1052,7 @@ static int launch_gemm(const GemmArgs& a, hipStream_t s) {
   else if (a.K >= 1024) shape = 3;
   else if (a.N >= 2048) shape = (EPI == ONEPROT_EPI_BIAS_GELU && a.out1 == nullptr) ? 20 : 4;      // forward-only GELU (frozen tower): direct-store form, -6 %
   else shape = 1;
-  if (shape >= 32 && (shape & 63) == 32) {            // ping-pong form; 32 + 64 * ring selects the ring depth (4..6) for A/B runs
-    if (shape >> 6) g_pp_ring = shape >> 6;
-    shape = 32;
-  }
+  if (shape >= 32 && (shape & 63) == 32) shape = 32;      // ping-pong form (the ring depth 32 + 64 * ring once selected is fixed at three buffers)
   if (shape >= 40 && shape <= 42) {      // 8-phase form (gemm_nt8.hip): 256 x 256 / 256 x 320 tiles; anything it is not built for takes the per-tile forms
     const int rc = launch_gemm8(EPI, a, shape - 40, 0, s);
     if (rc != G8_NOT_ELIGIBLE) return rc;
@@ -1072,7 +1078,8 @@ static int launch_gemm(const GemmArgs& a, hipStream_t s) {
     case 3: return launch_shape<EPI, 2, 2, 4, 4, 64, 2, 64, 2, false, true>(a, s);
     case 2: return launch_shape<EPI, 2, 4, 8, 4, 32, 4, 32, 2, true>(a, s);
     case 1: return launch_shape<EPI, 4, 2, 4, 4, 32, 3, 32, 4, false, true>(a, s);
-    default: return launch_shape<EPI, 2, 2, 4, 4, 32, 3, 32, 3, true>(a, s);
+    case 0: return launch_shape<EPI, 2, 2, 4, 4, 32, 3, 32, 3, true>(a, s);
+    default: return OP_EINVAL;      // (not reached: force_shape_exists)
   }
 }
 
@@ -1136,6 +1143,7 @@ extern "C" int oneprot_gemm_bf16_nt(const void* A, const void* Bw, int64_t M, in
   if (!A || !Bw || !out0 || M <= 0 || N <= 0 || K <= 0 || M > 0x7fffffff) return OP_EINVAL;
   if ((N & 7) || (K & 7) || (lda & 7) || (ldb & 7) || lda < K || ldb < K) return OP_EINVAL;
   if (((uintptr_t)A | (uintptr_t)Bw | (uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 | (uintptr_t)aux | (uintptr_t)bias) & 15) return OP_EINVAL;
+  if (!force_shape_exists(g_force_shape)) return OP_EINVAL;
   GemmArgs a;
   a.A = (const bf16_t*)A; a.B = (const bf16_t*)Bw; a.M = (int)M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.bias = bias;
   a.out0 = out0; a.out1 = out1; a.out2 = out2; a.aux = aux; a.cos = rope_cos; a.sin = rope_sin; a.q_scale = q_scale; a.L = L; a.H = H; a.hd = hd;

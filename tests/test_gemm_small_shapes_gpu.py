@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 from oneprot_amd import hip  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests import gemm_forms  # noqa: E402
 from tests.philox_ref import dropout_threshold, philox_keep  # noqa: E402
 
 DEV = "cuda"
@@ -65,17 +66,15 @@ def tol_tn(M):
 TOL_BF16 = (2 ** -7, 2e-2)
 
 
-# all 17 forced block shapes / all 5 weight-gradient variants (copies of the fixtures of test_kernels_gpu.py, which are not in a conftest)
-@pytest.fixture(params=[-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 17, 19, 20, 32, 40, 41, 42], ids=["auto", "128x128", "256x128", "256x256", "128x128bk64", "256x256bk64", "256x256nopipe", "4w128x128bk64",
-                                                                                     "4w128x128bk32", "regstaged256x256", "direct256x128", "direct128x128bk64", "direct256x256bk64", "pingpong",
-                                                                                     "8phase256x256", "8phase256x320", "8phase256x256merged"])
+# all 17 forced block shapes / all 5 weight-gradient variants (the lists test_kernels_gpu.py uses: tests/gemm_forms.py)
+@pytest.fixture(params=gemm_forms.ids(gemm_forms.NT_SHAPES), ids=gemm_forms.names(gemm_forms.NT_SHAPES))
 def gemm_shape(request):
     hip.query("oneprot_gemm_force_shape", request.param)
     yield request.param
     hip.query("oneprot_gemm_force_shape", -1)
 
 
-@pytest.fixture(params=[-1, 0, 1, 2, 3], ids=["auto", "dma64x2", "dma32x3", "regstaged", "8phase"])
+@pytest.fixture(params=gemm_forms.ids(gemm_forms.TN_VARIANTS), ids=gemm_forms.names(gemm_forms.TN_VARIANTS))
 def tn_variant(request):
     hip.query("oneprot_gemm_tn_variant", request.param)
     yield request.param

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from oneprot_amd import hip  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests import gemm_forms  # noqa: E402
 
 DEV = "cuda"
 
@@ -144,9 +145,7 @@ def _gemm_inputs(M, N, K, seed):
     return A, W, bias
 
 
-@pytest.fixture(params=[-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 17, 19, 20, 32, 40, 41, 42], ids=["auto", "128x128", "256x128", "256x256", "128x128bk64", "256x256bk64", "256x256nopipe", "4w128x128bk64",
-                                                                                     "4w128x128bk32", "regstaged256x256", "direct256x128", "direct128x128bk64", "direct256x256bk64", "pingpong",
-                                                                                     "8phase256x256", "8phase256x320", "8phase256x256merged"])
+@pytest.fixture(params=gemm_forms.ids(gemm_forms.NT_SHAPES), ids=gemm_forms.names(gemm_forms.NT_SHAPES))
 def gemm_shape(request):
     hip.query("oneprot_gemm_force_shape", request.param)
     yield request.param
@@ -202,6 +201,32 @@ def test_gemm_nt_epilogues(M, N, K, gemm_shape):
     dz = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_GELU_BWD, None, dz, None, None, z, None, None, 1.0, 0, 0, 0)
     assert_close(dz, ref * zdec, 2 ** -6, 3e-2, "gelu bwd")
+
+
+def test_gemm_force_shape_rejects_unknown_ids():
+    """A forced id that selects no kernel form is an error before anything is launched (it used to run shape 0 silently); every id of the fixture is accepted."""
+    M, N, K = 128, 128, 64
+    A, W, _ = _gemm_inputs(M, N, K, 3)
+    ref = A.float() @ W.float().t()
+    out = torch.full((M, N), float("nan"), device=DEV)
+    known = gemm_forms.ids(gemm_forms.NT_SHAPES)
+    try:
+        for shape in (9, 16, 18, 21, 31, 33, 39, 43, 99, 1 << 20):
+            assert shape not in known
+            hip.query("oneprot_gemm_force_shape", shape)
+            with pytest.raises(hip.HipKernelError):
+                hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, out, None, None, None, None, None, 1.0, 0, 0, 0)
+            assert bool(torch.isnan(out).all()), f"forced id {shape}: something was launched"
+        for shape in known + [32 + 64 * 4]:                      # (32 + 64 * ring: the ping-pong form as tools/ab/pp_check.py asks for it)
+            hip.query("oneprot_gemm_force_shape", shape)
+            out.fill_(float("nan"))
+            hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, out, None, None, None, None, None, 1.0, 0, 0, 0)
+            assert_close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), f"EPI_F32, forced id {shape}")
+    finally:
+        hip.query("oneprot_gemm_force_shape", -1)
+    out.fill_(float("nan"))
+    hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, out, None, None, None, None, None, 1.0, 0, 0, 0)
+    assert_close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), "EPI_F32 after the hook is back at -1")
 
 
 @pytest.mark.parametrize("form", [1, 0])
@@ -596,7 +621,7 @@ def test_gemm_qkv_rope_epilogue(B, L, H, hd, gemm_shape):
     assert_close(v.cpu(), y[2], 2 ** -7, 2e-2, "v")
 
 
-@pytest.fixture(params=[-1, 0, 1, 2, 3], ids=["auto", "dma64x2", "dma32x3", "regstaged", "8phase"])
+@pytest.fixture(params=gemm_forms.ids(gemm_forms.TN_VARIANTS), ids=gemm_forms.names(gemm_forms.TN_VARIANTS))
 def tn_variant(request):
     hip.query("oneprot_gemm_tn_variant", request.param)
     yield request.param
