@@ -440,6 +440,34 @@ int oneprot_msa_row_context_ragged_dropout(const float* S, const void* qkv, cons
 int oneprot_msa_col_attn_ragged_dropout(const void* qkv, const float* key_bias, void* ctx, const int64_t* geo, int n, int max_R, int max_L, int H, int hd,
                                         float scale, int T_tokens, int T_pad, int l_stride, float p, uint64_t seed, uint64_t stream_id, void* stream);
 
+/* ---------------- MSA input (ref src/data/datasets/msa_dataset.py:42-58: read_msa, greedy_select, the two tokenizers) ------------------------------
+ * A batch of n alignments as one byte stream.  msa_bytes: uint8, 16-byte aligned, n_bytes long; MSA b holds N_b rows of L_b letters (insertions already
+ * removed), row j at byte0_b + j * stride_b with stride_b = L_b rounded up to 16 and the bytes [L_b, stride_b) of every row 0: the host pads, so that
+ * every 16-byte load is aligned and the padding is no mismatch.  table: int64 [n, 4] = {byte0_b (a multiple of 16), N_b, L_b, k_b} on the device, and
+ * table_host the same numbers in host memory: the entry points validate and size their launches from the host copy, the kernels read the device one
+ * (oneprot_amd.msa_data builds both from one array).  Refused with -1 before any launch: n outside 1..65535, N_b < 1, L_b outside 1..65535, k_b
+ * outside 1..k_max, k_max > 1024, a block outside [0, n_bytes), a workspace that is too small, a pointer that is not aligned. */
+/* ref src/data/utils/msa_utils.py:21-40 `greedy_select(msa, num_seqs, mode)` for every MSA of the batch, as an exact integer rule: S_j = the sum over
+   the rows chosen so far of the number of positions where that row and row j differ; every step picks the unselected j with the largest (min_mode 1:
+   smallest) S_j, the lowest j among equal S_j; the first pick is row 0 and min(k_b, N_b) rows are picked.  (The reference averages in fp64, which
+   orders equal sums by rounding noise: DESIGN.md section 7.)  indices int32 [n, k_max]: the picks in ascending order, -1 behind them; order (optional)
+   int32 [n, k_max]: the picks in the order made.  max over b of min(k_b, N_b) - 1 step launches and two small ones, all on `stream`, nothing read back.
+   workspace: 16-byte aligned, at least oneprot_msa_select_workspace(n, k_max, sum of N_b, largest N_b) bytes (0 for invalid arguments); not cleared. */
+size_t oneprot_msa_select_workspace(int n, int k_max, int64_t total_rows, int64_t max_rows);
+int oneprot_msa_select(const void* msa_bytes, const int64_t* table, void* workspace, int* indices, int* order, const int64_t* table_host,
+                       size_t workspace_bytes, int64_t n_bytes, int n, int k_max, int min_mode, void* stream);
+/* ref msa_dataset.py:54-56: fair-esm's MSA batch converter (`get_batch_converter(truncation_seq_length=1022)`, then `msa_input[:, :, :max_length]`) and
+   the HF ESM-2 tokenizer (`padding=True, truncation=True`) on row 0.  Row r of MSA b is row indices[b, r] of its block (int32 [n, k_max], the output
+   of oneprot_msa_select; min(k_b, N_b) rows are read), written as cls_id followed by byte_map[letter] (int32 [256]) for the first
+   Lt_b - 1 = min(L_b, 1022, max_length - 1) letters.  cu_tokens NULL: tokens int64 [n, R_max, Lt_max], pad_id outside the blocks.  cu_tokens int32
+   [n + 1] (device; the host derives it from the table): tokens int64 [T_pad], block b dense min(k_b, N_b) x Lt_b at cu_tokens[b] -- the ids of
+   oneprot_amd.packing.PackedMsa -- and pad_id from the end of the last block to T_pad.  seq_tokens (optional) int64 [n, Ls_max]: row 0 of the block
+   (not of the selection: greedy_select keeps row 0) as cls_id, the first Ls_b - 2 letters, eos_id, then pad_id, Ls_b = min(L_b + 2, max_length).
+   R_max / Lt_max / Ls_max below what the table needs, max_length < 2 and T_pad below the token count return -1. */
+int oneprot_msa_tokenize(const void* msa_bytes, const int64_t* table, const int* indices, const int* byte_map, int64_t* tokens, const int* cu_tokens,
+                         int64_t* seq_tokens, const int64_t* table_host, int64_t n_bytes, int n, int k_max, int R_max, int Lt_max, int Ls_max,
+                         int max_length, int64_t T_pad, int cls_id, int pad_id, int eos_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ _RETURNS = {"int": c_int, "size_t": c_size_t, "int64_t": c_int64, "void": None}
 # Element type of a pointer argument: f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a flag argument / epilogue id.
 # A typed pointer says it itself and a void* is bf16 storage (the header's convention).  The void* that are not bf16 are named here, and nowhere else:
 _PTR_LETTER = {"float": "f", "int64_t": "l", "int": "i", "void": "h"}
-_BYTE_PTRS = {"workspace", "sched_ws", "keep"}                                       # by parameter name, in every entry point
+_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes"}                          # by parameter name, in every entry point
 _FLAG_TYPED_PTRS = {("oneprot_gemm_bf16_nt", "out0"), ("oneprot_gemm_bf16_nt", "out1"), ("oneprot_gemm_bf16_nt", "aux"),
                     ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x")}
 
