@@ -6,13 +6,14 @@ module is in train mode, also for the frozen tower (ref text_encoder.py:56-62 ne
 `transformer.train_dropout = False` or ONEPROT_BERT_DROPOUT=0 run p = 0, which is what parity against the eval-mode reference is defined on
 (see _train_dropout below)."""
 import os
-import warnings
 
 import torch
 
 from . import hip
 from . import layout
-from .esm import ArenaModule, ModelConfig, load_weight_file, resolve_config, _Out
+from .arena import ModelConfig, load_weight_file, _Out
+from .esm import resolve_config
+from .lora import LoraArena
 from .packing import PackedTokens
 
 BERT_DEFAULTS = dict(model_type="bert", vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
@@ -83,10 +84,7 @@ class _BertPacked(layout.PackedLayout):
         return n
 
 
-_layout = layout.of      # _layout(tower, ids): the layout of a padded batch or a packed stream, one of tower.layouts
-
-
-class BertTransformer(ArenaModule):
+class BertTransformer(LoraArena):
     final_layer_norm = False      # post-LN model: pooling reads the last layer's output directly
     layouts = (_BertPadded, _BertPacked)      # layout.of(self, ids)
     accepts_packed = True         # run_layers / backward_layers take a PackedTokens stream (oneprot_amd.packing)
@@ -122,18 +120,6 @@ class BertTransformer(ArenaModule):
         self.reset_parameters()
 
     _load_ignore_suffixes = ("embeddings.position_ids",)
-
-    @torch.no_grad()
-    def reset_parameters(self):
-        std = getattr(self.config, "initializer_range", 0.02)
-        for name in self._spec:
-            v = self.view(name)
-            if name.endswith("LayerNorm.weight"):
-                v.fill_(1.0)
-            elif name.endswith(".bias"):
-                v.zero_()
-            else:
-                v.normal_(0.0, std)
 
     def _norope(self, L, dev):
         key = (L, dev)
@@ -185,7 +171,7 @@ class BertTransformer(ArenaModule):
         if not ids.is_cuda:
             raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback")
         self._refresh_bf16()
-        lay = _layout(self, ids)
+        lay = layout.of(self, ids)
         B, L = lay.B, lay.L
         if not lay.packed and L > cfg.max_position_embeddings:
             raise ValueError(f"sequence length {L} exceeds max_position_embeddings {cfg.max_position_embeddings}")
@@ -209,12 +195,9 @@ class BertTransformer(ArenaModule):
             saved["drop_call"] = drop_call
         q, k, v, ctx, u = b16(B, H, L, hd), b16(B, H, L, hd), b16(B, H, L, hd), b16(T, d), b16(T, f)
         eps = cfg.layer_norm_eps
-        lora_two = self._lora_two_branch()
-        if lora_two:
-            lora_call = self._lora_calls
-            self._lora_calls += 1
-            if save:
-                saved["lora_call"] = lora_call
+        lora_call = self._lora_next_call()
+        if save and lora_call is not None:
+            saved["lora_call"] = lora_call
         for i in range(self.n_layers):
             p = f"encoder.layer.{i}."
             if save:     # per layer: input (bf16), attention operands, the two pre-LN sums with their statistics, FFN intermediates
@@ -227,28 +210,19 @@ class BertTransformer(ArenaModule):
                 z = lse = m1 = r1 = m2 = r2 = None
                 s1 = s2 = tmp
                 y1, y16, x_out, h_out = x, h, x, h
-            o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
-            ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
+            (o, n), (ob, nb) = self._qkv_spans(i)
             # rotary tables (1, 0) turn the QKV epilogue into "q *= 1/sqrt(hd), head-major q/k/v" (scores scaled inside attention in HF: same product)
-            if lora_two:      # peft's two branches in one launch: [h | dropout(h) A^T] x [W | s B]^T  (esm.py, enable_lora)
-                xc, lora_u = self._lora_branch_operand(i, h, T, lora_call)
-                kc = self._lora_ops["Kc"]
-                hip.gemm_nt(xc, self._lora_ops["Wc"][i], T, 3 * d, kc, hip.EPI_QKV_ROPE, q, bias=self.flat.data[ob:ob + nb], out1=k, out2=v,
-                            rope=(one, zero, L, H, hd), q_scale=hd ** -0.5 * hip.LOG2E)
-                if save:
-                    st["lora_u"] = lora_u
-            else:
-                hip.gemm_nt(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_QKV_ROPE, q, bias=self.flat.data[ob:ob + nb], out1=k, out2=v,
-                            rope=(one, zero, L, H, hd), q_scale=hd ** -0.5 * hip.LOG2E)
+            lora_u = self._qkv_forward(i, h, self._bf16[o:o + n], self.flat.data[ob:ob + nb], T, 3 * d, (one, zero, L, H, hd), hd ** -0.5 * hip.LOG2E, q, k, v, lora_call)
+            if save:
+                st["lora_u"] = lora_u
+            lay.attn_fwd(q, k, v, ctx, lse, H, hd, drop=drop and (p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
             if drop:
-                lay.attn_fwd(q, k, v, ctx, lse, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
                 # s1 = x + dropout(ctx Wo^T + bo): the residual add leaves the GEMM epilogue so that the mask can sit between the two
                 hip.gemm_nt(ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, hip.EPI_F32, y_drop, bias=self.view(p + "attention.output.dense.bias"))
                 # ... and the LayerNorm that follows reads the sum where it is formed (one kernel; a frozen tower never writes the sum)
                 hip.call("oneprot_dropout_add_layernorm_fwd", y_drop, x, s1 if save else None, self.view(p + "attention.output.LayerNorm.weight"),
                          self.view(p + "attention.output.LayerNorm.bias"), y16, y1, m1, r1, T, d, eps, p_h, self._drop_seed, self._drop_stream(drop_call, i, 1))
             else:
-                lay.attn_fwd(q, k, v, ctx, lse, H, hd)
                 hip.gemm_nt(ctx, self._w16(p + "attention.output.dense.weight"), T, d, d, hip.EPI_BIAS_RESID, s1, bias=self.view(p + "attention.output.dense.bias"),
                             aux=x)
                 hip.layernorm_fwd(s1, self.view(p + "attention.output.LayerNorm.weight"), self.view(p + "attention.output.LayerNorm.bias"), T, d, eps,
@@ -282,12 +256,8 @@ class BertTransformer(ArenaModule):
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
         ws_ln = torch.empty(hip.query("oneprot_layernorm_bwd_workspace", d), dtype=torch.uint8, device=dev)
-        lora_raw = None
-        tn_shapes = ((3 * d, d), (f, d), (d, f), (d, d))
-        if "lora_call" in saved:                          # the forward ran peft's two-branch form (train mode, lora_dropout > 0)
-            lora_raw = self._lora_raw = self._lora_raw_buffers(dev)
-            tn_shapes += ((3 * d, self._lora_ops["Rp"]), (self._lora_ops["rp"], d))
-        ws_tn = self._tn_workspace(tn_shapes, dev)
+        lora_raw, lora_tn = self._lora_backward_setup(saved, dev)
+        ws_tn = self._tn_workspace(((3 * d, d), (f, d), (d, f), (d, d)) + lora_tn, dev)
         ws_at = lay.attn_workspace(H, dev)
         ds, ds16, gy = f32(T, d), b16(T, d), f32(T, d)
         dz, dctx, dqkv = b16(T, f), b16(T, d), b16(T, 3 * d)
@@ -322,13 +292,9 @@ class BertTransformer(ArenaModule):
             self._wgrad(da16, st["ctx"], T, d, d, gv(p + "attention.output.dense.weight"), gv(p + "attention.output.dense.bias"), ws_tn)
             hip.gemm_nt(da16, self._bf16_T[(i, "o")], T, d, d, hip.EPI_BF16, dctx)
             # ---- attention (no rotary: cos/sin = null)
-            if drop_call is not None:
-                lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd, drop=(p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
-            else:
-                lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd)
+            lay.attn_bwd(st, dctx, hd ** -0.5, dqkv, ws_at, H, hd, drop=drop_call is not None and (p_a, self._drop_seed, self._drop_stream(drop_call, i, 0)))
             # ---- QKV projection; g = ds (residual branch) + dqkv Wqkv
-            o, n = self.span(p + "attention.self.query.weight", p + "attention.self.value.weight")
-            ob, nb = self.span(p + "attention.self.query.bias", p + "attention.self.value.bias")
+            (o, n), (ob, nb) = self._qkv_spans(i)
             hip.gemm_tn(dqkv, st["x16"], T, 3 * d, d, gflat[o:o + n], gflat[ob:ob + nb], ws_tn)
             hip.gemm_nt(dqkv, self._bf16_T[(i, "qkv")], T, d, 3 * d, hip.EPI_BIAS_RESID, g, aux=ds)
             if lora_raw is not None:      # two-branch LoRA: adapter gradients, and g += mask * (du A) / keep
@@ -371,22 +337,15 @@ class BertTransformer(ArenaModule):
     def forward(self, input_ids=None, attention_mask=None, **_):
         """BertModel-compatible call returning .last_hidden_state; a packed input gives the stream's [T_pad, d] (tail rows: finite, meaningless)"""
         x, _ = self.run_layers(input_ids, save=False)
-        return _Out(_layout(self, input_ids).final_hidden(self, x))
+        return _Out(layout.of(self, input_ids).final_hidden(self, x))
 
     @classmethod
     def from_pretrained(cls, model_name_or_path, **_):
         cfg, path = resolve_bert_config(model_name_or_path)
-        model = cls(cfg)
         sd = load_weight_file(path)
-        if sd is None:
-            if os.environ.get("ONEPROT_ALLOW_RANDOM_INIT", "0") != "1":
-                raise OSError(f"no weights (model.safetensors / pytorch_model.bin) found for {model_name_or_path}; "
-                              "set ONEPROT_ALLOW_RANDOM_INIT=1 to build a randomly initialised model of that architecture")
-            warnings.warn(f"{model_name_or_path}: no weight file, using random initialisation")
-        else:
+        if sd is not None:
             sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in sd.items() if not k.startswith("cls.")}
-            missing, _ = model.load_state_dict(sd, strict=False)
-            missing = [m for m in missing if not (m.startswith("pooler.") or m.startswith("extra."))]
-            if missing:
-                raise OSError(f"checkpoint {model_name_or_path} lacks tensors: {missing[:5]}...")
+        model, missing, _ = cls._from_checkpoint(sd, model_name_or_path, "model.safetensors / pytorch_model.bin", ("pooler.", "extra."), cfg)
+        if missing:
+            raise OSError(f"checkpoint {model_name_or_path} lacks tensors: {missing[:5]}...")
         return model

@@ -22,7 +22,7 @@ from . import hip
 from . import layout
 from .layout import _ws
 from .esm import EsmTransformer, resolve_config, ModelConfig, recompute_plan
-from .packing import PackedMsa, PackedTokens
+from .packing import PackedTokens
 
 
 # ------------------------------------------------------------------------------------------------- small modules
@@ -348,13 +348,12 @@ class _EncodeFn(torch.autograd.Function):
             # the step and nothing has been accumulated yet -- then the arena gradient is installed as .grad here (autograd gets None for it)
             # and finished ranges are all-reduced while the lower layers are still in their backward.
             sync = getattr(tr, "_grad_overlap", None)
-            single = getattr(tr, "_live_apps", 1) == 1 and not getattr(tr, "_multi_app_step", False)
             if getattr(tr, "_live_apps", 1) > 1:
                 tr._multi_app_step = True
             tr._live_apps = max(getattr(tr, "_live_apps", 1) - 1, 0)
-            if tr._live_apps == 0 and not single:
+            if tr._live_apps == 0 and not lone:
                 tr._multi_app_step = False
-            if sync is not None and single and tr.flat.grad is None and not tr._lora:
+            if sync is not None and lone and tr.flat.grad is None and not tr._lora:
                 tr.backward_layers(saved, g, g16, gflat, on_ready=lambda lo, hi: sync.reduce_range(tr.flat, gflat, lo, hi))
                 tr.flat.grad = gflat
                 gflat = None
@@ -650,48 +649,17 @@ class MsaEncoder(BaseEncoder):
         self.transformer.train_dropout = None if on is None else bool(on)
 
     def hidden_and_pooled(self, tokens, want_hidden=True):
-        """(representation n_layers fp32 [B, R, L, d] -- [B, L, d] for row 0, None unless wanted --, pooled [B, d]): final LayerNorm fused with the pooling"""
+        """(representation n_layers, None unless wanted, pooled [B, d]): the final LayerNorm fused with the pooling.  The representation of a padded batch is
+        fp32 [B, R, L, d] ([B, L, d] for row 0); of a PackedMsa the stream [T_pad, d] (for row 0 the list of the N [L_b, d] blocks) -- msa.py's layouts"""
         tr = self.transformer
         tr.check_input(tokens)                          # every refusal before the device is touched
         mode = 0 if self.use_all_msa else getattr(self.pooling, "mode", 3)
         if mode not in (0, 1):
             raise NotImplementedError(f"MsaEncoder(use_all_msa=False): pooling_type {self.pooling_type!r} is not built for row 0 of the MSA; use 'mean' or 'cls' "
                                       "(use_all_msa=True ignores the pooling, as in the reference)")
-        if isinstance(tokens, PackedMsa):
-            return self._hidden_and_pooled_packed(tokens, mode, want_hidden)
         with torch.no_grad():
             x, _ = tr.run_layers(tokens, drop=bool(self.training and tr.dropout_enabled()))
-            B, R, L = tokens.shape
-            d, dev, pad = tr.d, tokens.device, tr.config.padding_idx
-            if self.use_all_msa:                         # one "sequence" of R * L tokens per MSA
-                ids, n = tokens.contiguous().view(B, R * L), R * L
-            else:
-                x, ids, n = x.view(B, R, L, d)[:, 0].contiguous(), tokens[:, 0].contiguous(), L
-            pooled, hidden = torch.empty(B, d, device=dev), (torch.empty(B, n, d, device=dev) if want_hidden else None)
-            hip.call("oneprot_lnpool_fwd", x, ids, pad, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None, None, None,
-                     None, hidden, B, n, d, tr.config.layer_norm_eps, mode)
-        return (hidden.view(B, R, L, d) if (self.use_all_msa and want_hidden) else hidden), pooled
-
-    def _hidden_and_pooled_packed(self, pk, mode, want_hidden):
-        """a PackedMsa: (representation n_layers as a stream fp32 [T_pad, d] -- `pk.unpack` gives the [R_b, L_b, d] blocks; for row 0 the list of the N
-        [L_b, d] row-0 representations --, pooled [N, d] in MSA order).  Pooling per segment of the stream (oneprot_lnpool_packed_fwd, which walks a
-        segment of any length): every MSA's R_b * L_b tokens with cu_tokens as the segment table, or its row 0 gathered into a small stream of its own."""
-        tr = self.transformer
-        with torch.no_grad():
-            x, _ = tr.run_layers(pk, drop=bool(self.training and tr.dropout_enabled()))
-            N, d, dev, pad, ids, cu, T = len(pk), tr.d, pk.device, tr.config.padding_idx, pk.ids, pk.cu_tokens, pk.T_pad
-            if not self.use_all_msa:
-                idx, cu, _ = pk.row0()
-                x, ids, T = x.index_select(0, idx), ids.index_select(0, idx), idx.numel()
-            pooled, hidden = torch.empty(N, d, device=dev), (torch.empty(T, d, device=dev) if want_hidden else None)
-            hip.call("oneprot_lnpool_packed_fwd", x, ids, cu, pad, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None,
-                     None, None, hidden, N, T, d, tr.config.layer_norm_eps, mode)
-            if want_hidden and not self.use_all_msa:
-                c = [0]
-                for _, l in pk.shapes:
-                    c.append(c[-1] + l)
-                hidden = [hidden[a:b] for a, b in zip(c[:-1], c[1:])]
-        return hidden, pooled
+            return tr.layout(tokens).pool(tr, x, self.use_all_msa, mode, want_hidden)
 
     def forward(self, tokens):
         return self.apply_head(self.hidden_and_pooled(tokens, want_hidden=False)[1])

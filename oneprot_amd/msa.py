@@ -31,12 +31,11 @@ dropout masks index the stream's own flat [T_pad, d] / [T_pad, f] element: the s
 refused as before.
 """
 import os
-import warnings
 
 import torch
 
 from . import hip
-from .esm import ArenaModule, ModelConfig
+from .arena import ArenaModule, ModelConfig
 from .packing import PackedMsa, PackedTokens
 
 MSA_DEFAULTS = dict(model_type="msa_transformer", num_layers=12, embed_dim=768, ffn_embed_dim=3072, attention_heads=12, max_positions=1024,
@@ -76,6 +75,111 @@ def plan_groups_ragged(shapes, H, budget=None):
         used += per
     groups.append((b0, len(shapes)))
     return groups
+
+
+class _MsaLayout:
+    """How the MSAs of a batch lie in memory, and every launch that depends on it -- the MSA tower's counterpart of layout.py: the key bias and the
+    embedding, the row attention's score maps and workspace (groups of whole MSAs under the score budget), the two attentions, the pooling end.
+    B MSAs on T rows, Tn of them tokens; R, L: the padded batch's, also for a ragged one (the row scale, the one-row shortcut, the column dropout's
+    stride).  drop = (p, seed, stream) selects an attention's dropout form, a false value the plain kernel.  Constructing a layout launches nothing."""
+
+    def embed(self, tr, x):
+        """the additive key-padding bias fp32 [T] (kept for the attentions) and x fp32 [T, d] = emb_layer_norm_before(token + position + MSA-row embedding)"""
+        cfg, pad = tr.config, tr.config.padding_idx
+        self.kb = torch.empty(self.T, device=x.device)
+        hip.call("oneprot_key_padding_bias", self.ids, self.kb, self.T, pad)
+        name, tables, geom = self._embed_form()
+        hip.call(name, self.ids, *tables, tr.view("embed_tokens.weight"), tr.view("embed_positions.weight"), tr.view("msa_position_embedding"),
+                 tr.view("emb_layer_norm_before.weight"), tr.view("emb_layer_norm_before.bias"), x, *geom, tr.d, cfg.vocab_size, cfg.max_positions + pad + 1,
+                 cfg.msa_rows, pad, cfg.layer_norm_eps)
+
+
+class _MsaPadded(_MsaLayout):
+    """tokens int64 [B, R, L]: T = B * R * L rows, MSA b at rows b * R * L onwards"""
+
+    def __init__(self, tr, tokens):
+        self.ids, (self.B, self.R, self.L), self.H, self.hd = tokens.contiguous(), tokens.shape, tr.H, tr.hd
+        self.T = self.Tn = self.B * self.R * self.L
+
+    def _embed_form(self):
+        return "oneprot_msa_embed_fwd", (), (self.B, self.R, self.L)
+
+    def alloc_scores(self):
+        B, R, L, H, dev = self.B, self.R, self.L, self.H, self.ids.device
+        self.groups = plan_groups(B, R, L, H)
+        gmax = max(b1 - b0 for b0, b1 in self.groups)
+        self.S = torch.empty(gmax, H, L, L, device=dev)
+        self.ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", gmax, R, L, H), dtype=torch.uint8, device=dev)     # probabilities + V transposed, per group
+
+    def row_attn(self, qkv, ctx, row_scale, drop):
+        R, L, H, hd, kb, S, ws = self.R, self.L, self.H, self.hd, self.kb, self.S, self.ws
+        for b0, b1 in self.groups:
+            t0, t1 = b0 * R * L, b1 * R * L
+            hip.call("oneprot_msa_row_scores", qkv[t0:t1], kb[t0:t1], S, b1 - b0, R, L, H, hd, row_scale)
+            # b0: the mask is that of the MSA's place in the batch, whatever the grouping
+            hip.call("oneprot_msa_row_context" + ("_dropout" if drop else ""), S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd,
+                     *((b0, *drop) if drop else ()))
+
+    def col_attn(self, qkv, ctx, drop):
+        hip.call("oneprot_msa_col_attn" + ("_dropout" if drop else ""), qkv, self.kb, ctx, self.B, self.R, self.L, self.H, self.hd, self.hd ** -0.5, *(drop or ()))
+
+    def pool(self, tr, x, all_rows, mode, want_hidden):
+        """(representation n_layers fp32 [B, R, L, d] -- [B, L, d] for row 0, None unless wanted --, pooled [B, d]): final LayerNorm fused with the pooling,
+        over every non-pad (r, l) of an MSA (`all_rows`) or over its row 0"""
+        B, R, L, d, dev = self.B, self.R, self.L, tr.d, x.device
+        if all_rows:                                    # one "sequence" of R * L tokens per MSA
+            ids, n = self.ids.view(B, R * L), R * L
+        else:
+            x, ids, n = x.view(B, R, L, d)[:, 0].contiguous(), self.ids[:, 0].contiguous(), L
+        pooled, hidden = torch.empty(B, d, device=dev), (torch.empty(B, n, d, device=dev) if want_hidden else None)
+        hip.call("oneprot_lnpool_fwd", x, ids, tr.config.padding_idx, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"), pooled, None,
+                 None, None, None, hidden, B, n, d, tr.config.layer_norm_eps, mode)
+        return (hidden.view(B, R, L, d) if (all_rows and want_hidden) else hidden), pooled
+
+
+class _MsaRagged(_MsaLayout):
+    """a PackedMsa: the stream's T_pad rows, MSA b a dense R_b x L_b block at cu_tokens[b]; the *_ragged entry points follow the blocks"""
+
+    def __init__(self, tr, pk):
+        self.p, self.ids, self.B, (self.R, self.L), self.H, self.hd = pk, pk.ids, len(pk), pk.padded_shape, tr.H, tr.hd
+        self.T, self.Tn = pk.T_pad, pk.n_tokens
+
+    def _embed_form(self):
+        self.whole = w = self.p.tables(self.H)[0]       # the whole stream as one call: embedding bounds and the column attention
+        return "oneprot_msa_embed_ragged_fwd", (self.p.cu_tokens, self.p.row_lens()), (self.B, self.T, w["max_R"], w["max_L"])
+
+    def alloc_scores(self):
+        H, dev = self.H, self.ids.device
+        self.groups = self.p.tables(H, plan_groups_ragged(self.p.shapes, H))
+        self.S = torch.empty(max(g["s_elems"] for g in self.groups), device=dev)
+        self.ws = torch.empty(max(hip.query("oneprot_msa_row_context_ragged_workspace", g["sum_l_lp"], g["sum_r_lp"], H) for g in self.groups), dtype=torch.uint8, device=dev)
+
+    def row_attn(self, qkv, ctx, row_scale, drop):
+        H, hd, kb, S, ws = self.H, self.hd, self.kb, self.S, self.ws
+        for g in self.groups:
+            hip.call("oneprot_msa_row_scores_ragged", qkv, kb, S, g["geo"], g["n"], g["max_L"], H, hd, row_scale)
+            hip.call("oneprot_msa_row_context_ragged" + ("_dropout" if drop else ""), S, qkv, kb, ctx, ws, ws.numel(), g["geo"], g["n"], g["max_R"], g["max_L"],
+                     g["sum_l_lp"], g["sum_r_lp"], H, hd, self.Tn, self.T, *((g["b_first"], *drop) if drop else ()))
+
+    def col_attn(self, qkv, ctx, drop):                 # one call over the stream; a block of one row inside a deeper batch is the kernel's
+        w = self.whole
+        hip.call("oneprot_msa_col_attn_ragged" + ("_dropout" if drop else ""), qkv, self.kb, ctx, w["geo"], self.B, w["max_R"], w["max_L"], self.H, self.hd,
+                 self.hd ** -0.5, self.Tn, self.T, *((self.L, *drop) if drop else ()))
+
+    def pool(self, tr, x, all_rows, mode, want_hidden):
+        """(representation n_layers as a stream fp32 [T_pad, d] -- `PackedMsa.unpack` gives the [R_b, L_b, d] blocks; for row 0 the list of the N [L_b, d]
+        row-0 representations; None unless wanted --, pooled [N, d] in MSA order).  Pooling per segment of the stream (oneprot_lnpool_packed_fwd, which walks
+        a segment of any length): every MSA's R_b * L_b tokens with cu_tokens as the segment table, or its row 0 gathered into a small stream of its own."""
+        pk, N, d, dev, ids, cu, T = self.p, self.B, tr.d, x.device, self.ids, self.p.cu_tokens, self.T
+        if not all_rows:
+            idx, cu, n0 = pk.row0()
+            x, ids, T = x.index_select(0, idx), ids.index_select(0, idx), idx.numel()
+        pooled, hidden = torch.empty(N, d, device=dev), (torch.empty(T, d, device=dev) if want_hidden else None)
+        hip.call("oneprot_lnpool_packed_fwd", x, ids, cu, tr.config.padding_idx, tr.view("emb_layer_norm_after.weight"), tr.view("emb_layer_norm_after.bias"),
+                 pooled, None, None, None, hidden, N, T, d, tr.config.layer_norm_eps, mode)
+        if want_hidden and not all_rows:
+            hidden = list(hidden[:n0].split([l for _, l in pk.shapes]))
+        return hidden, pooled
 
 
 def upgrade_fair_esm_state_dict(sd):
@@ -188,17 +292,16 @@ class MsaTransformer(ArenaModule):
         2 = column probabilities, 3 = column-block output, 4 = FFN activation, 5 = FFN output.  Hidden masks index the flat [T, d] / [T, f] element."""
         return self._rng_stream(self.RNG_DOMAIN_MSA, (call * (self.n_layers + 1) + layer + 1) * 8 + site)
 
+    _norm_weight_suffixes = ("layer_norm.weight", "emb_layer_norm_before.weight", "emb_layer_norm_after.weight")
+
     @torch.no_grad()
     def reset_parameters(self):
-        for name in self._spec:
-            v = self.view(name)
-            if name.endswith("layer_norm.weight") or name in ("emb_layer_norm_before.weight", "emb_layer_norm_after.weight"):
-                v.fill_(1.0)
-            elif name.endswith(".bias"):
-                v.zero_()
-            else:
-                v.normal_(0.0, 0.02)
+        super().reset_parameters()
         self.view("embed_tokens.weight")[self.config.padding_idx].zero_()
+
+    def layout(self, tokens):
+        """the layout of a padded [B, R, L] batch or of a PackedMsa"""
+        return (_MsaRagged if isinstance(tokens, PackedMsa) else _MsaPadded)(self, tokens)
 
     def check_input(self, tokens):
         """every refusal, before anything touches the device"""
@@ -238,30 +341,14 @@ class MsaTransformer(ArenaModule):
         if save:
             raise NotImplementedError("the MSA tower is frozen: there is no backward")
         self._refresh_bf16_mirror()
-        cfg = self.config
-        pk = tokens if isinstance(tokens, PackedMsa) else None
-        if pk is not None:
-            tokens, (R, L), B = pk.ids, pk.padded_shape, len(pk)
-            T, Tn = pk.T_pad, pk.n_tokens
-        else:
-            tokens = tokens.contiguous()
-            B, R, L = tokens.shape
-            T = B * R * L
-        d, f, H, hd, dev = self.d, self.f, self.H, self.hd, tokens.device
+        lay = self.layout(tokens)
+        T, R = lay.T, lay.R
+        d, f, hd, dev = self.d, self.f, self.hd, lay.ids.device
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)
-        eps, pad = cfg.layer_norm_eps, cfg.padding_idx
-        kb, x = f32(T), f32(T, d)
-        hip.call("oneprot_key_padding_bias", tokens, kb, T, pad)
-        if pk is not None:
-            whole = pk.tables(H)[0]                     # the whole stream as one call: embedding bounds and the column attention
-            hip.call("oneprot_msa_embed_ragged_fwd", tokens, pk.cu_tokens, pk.row_lens(), self.view("embed_tokens.weight"), self.view("embed_positions.weight"),
-                     self.view("msa_position_embedding"), self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, T,
-                     whole["max_R"], whole["max_L"], d, cfg.vocab_size, cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
-        else:
-            hip.call("oneprot_msa_embed_fwd", tokens, self.view("embed_tokens.weight"), self.view("embed_positions.weight"), self.view("msa_position_embedding"),
-                     self.view("emb_layer_norm_before.weight"), self.view("emb_layer_norm_before.bias"), x, B, R, L, d, cfg.vocab_size,
-                     cfg.max_positions + pad + 1, cfg.msa_rows, pad, eps)
+        eps = self.config.layer_norm_eps
+        x = f32(T, d)
+        lay.embed(self, x)
         if drop:
             call, seed = self._next_drop_call(), self._drop_seed
             p_h, p_a, p_f = self._drop_probs()
@@ -269,16 +356,7 @@ class MsaTransformer(ArenaModule):
                                                         # its operands __restrict__ and the header does not allow y = x for it, unlike the fp32 kernels)
             # MSATransformer.forward: emb_layer_norm_before -> dropout_module -> x * (1 - padding_mask); the kernel above has zeroed the padding already
             hip.call("oneprot_dropout_f32", x, x, T * d, p_h, seed, self._drop_stream(call, -1, 0))
-        if pk is not None:
-            groups = pk.tables(H, plan_groups_ragged(pk.shapes, H))
-            S = f32(max(g["s_elems"] for g in groups))
-            ws = torch.empty(max(hip.query("oneprot_msa_row_context_ragged_workspace", g["sum_l_lp"], g["sum_r_lp"], H) for g in groups), dtype=torch.uint8,
-                             device=dev)
-        else:
-            groups = plan_groups(B, R, L, H)
-            gmax = max(b1 - b0 for b0, b1 in groups)
-            S = f32(gmax, H, L, L)
-            ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", gmax, R, L, H), dtype=torch.uint8, device=dev)     # probabilities + V transposed, per group
+        lay.alloc_scores()
         h, qkv, ctx, u = b16(T, d), b16(T, 3 * d), b16(T, d), b16(T, f)
         row_scale = hd ** -0.5 / R ** 0.5               # R = the padded row count, as published
         for i in range(self.n_layers):
@@ -293,34 +371,10 @@ class MsaTransformer(ArenaModule):
                     o, n = self.span(p + "layer.q_proj.weight", p + "layer.v_proj.weight")
                     ob, nb = self.span(p + "layer.q_proj.bias", p + "layer.v_proj.bias")
                     hip.gemm_nt(h, self._bf16[o:o + n], T, 3 * d, d, hip.EPI_BF16, qkv, bias=self.flat.data[ob:ob + nb])
-                    if pk is not None and blk == "row_self_attention":
-                        for g in groups:
-                            hip.call("oneprot_msa_row_scores_ragged", qkv, kb, S, g["geo"], g["n"], g["max_L"], H, hd, row_scale)
-                            geom = (g["geo"], g["n"], g["max_R"], g["max_L"], g["sum_l_lp"], g["sum_r_lp"], H, hd, Tn, T)
-                            if drop:
-                                hip.call("oneprot_msa_row_context_ragged_dropout", S, qkv, kb, ctx, ws, ws.numel(), *geom, g["b_first"], p_a, seed,
-                                         self._drop_stream(call, i, 0))
-                            else:
-                                hip.call("oneprot_msa_row_context_ragged", S, qkv, kb, ctx, ws, ws.numel(), *geom)
-                    elif pk is not None:                # the column attention: one call over the stream; a block of one row inside a deeper batch is the kernel's
-                        geom = (whole["geo"], B, whole["max_R"], whole["max_L"], H, hd, hd ** -0.5, Tn, T)
-                        if drop:
-                            hip.call("oneprot_msa_col_attn_ragged_dropout", qkv, kb, ctx, *geom, L, p_a, seed, self._drop_stream(call, i, 2))
-                        else:
-                            hip.call("oneprot_msa_col_attn_ragged", qkv, kb, ctx, *geom)
-                    elif blk == "row_self_attention":
-                        for b0, b1 in groups:
-                            t0, t1 = b0 * R * L, b1 * R * L
-                            hip.call("oneprot_msa_row_scores", qkv[t0:t1], kb[t0:t1], S, b1 - b0, R, L, H, hd, row_scale)
-                            if drop:                    # b0: the mask is that of the MSA's place in the batch, whatever the grouping
-                                hip.call("oneprot_msa_row_context_dropout", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd, b0, p_a,
-                                         seed, self._drop_stream(call, i, 0))
-                            else:
-                                hip.call("oneprot_msa_row_context", S, qkv[t0:t1], kb[t0:t1], ctx[t0:t1], ws, ws.numel(), b1 - b0, R, L, H, hd)
-                    elif drop:
-                        hip.call("oneprot_msa_col_attn_dropout", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5, p_a, seed, self._drop_stream(call, i, 2))
+                    if blk == "row_self_attention":
+                        lay.row_attn(qkv, ctx, row_scale, drop and (p_a, seed, self._drop_stream(call, i, 0)))
                     else:
-                        hip.call("oneprot_msa_col_attn", qkv, kb, ctx, B, R, L, H, hd, hd ** -0.5)
+                        lay.col_attn(qkv, ctx, drop and (p_a, seed, self._drop_stream(call, i, 2)))
                 if self.capture is not None:
                     self.capture.append((blk[:3], i, ctx.clone()))
                 if self.stages is not None:             # the attention kernels leave qkv as they found it
@@ -363,22 +417,15 @@ class MsaTransformer(ArenaModule):
         """`model_name_or_path`: a raw fair-esm checkpoint file, {"args" | "cfg": ..., "model": state dict} (what the reference hands to
         esm.pretrained.load_model_and_alphabet_local, msa_encoder.py:18).  PARITY UNPINNED: the key upgrade and the architecture fields follow the published
         loader, not a run of it."""
-        path = str(model_name_or_path)
-        if not os.path.isfile(path):
-            if os.environ.get("ONEPROT_ALLOW_RANDOM_INIT", "0") != "1":
-                raise OSError(f"no weights (a fair-esm .pt file) found for {model_name_or_path}; "
-                              "set ONEPROT_ALLOW_RANDOM_INIT=1 to build a randomly initialised model of that architecture")
-            warnings.warn(f"{model_name_or_path}: no weight file, using random initialisation")
-            return cls(ModelConfig(**MSA_DEFAULTS))
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-        cfg = config_from_args(ck.get("cfg") if ck.get("cfg") is not None else ck.get("args"))
-        sd = upgrade_fair_esm_state_dict(ck["model"])
-        for k in ("embed_tokens.weight", "msa_position_embedding"):
-            if k in sd:
-                setattr(cfg, "vocab_size" if k == "embed_tokens.weight" else "msa_rows", sd[k].shape[0 if k == "embed_tokens.weight" else 1])
-        model = cls(cfg)
-        missing, unexpected = model.load_state_dict(sd, strict=False)
-        missing = [m for m in missing if not (m.startswith(("lm_head.", "contact_head.", "extra.")))]
+        path, cfg, sd = str(model_name_or_path), ModelConfig(**MSA_DEFAULTS), None
+        if os.path.isfile(path):
+            ck = torch.load(path, map_location="cpu", weights_only=False)
+            cfg = config_from_args(ck.get("cfg") if ck.get("cfg") is not None else ck.get("args"))
+            sd = upgrade_fair_esm_state_dict(ck["model"])
+            for k in ("embed_tokens.weight", "msa_position_embedding"):
+                if k in sd:
+                    setattr(cfg, "vocab_size" if k == "embed_tokens.weight" else "msa_rows", sd[k].shape[0 if k == "embed_tokens.weight" else 1])
+        model, missing, unexpected = cls._from_checkpoint(sd, model_name_or_path, "a fair-esm .pt file", ("lm_head.", "contact_head.", "extra."), cfg)
         unexpected = [u for u in unexpected if not u.endswith("_float_tensor")]
         if missing or unexpected:
             raise OSError(f"checkpoint {model_name_or_path}: missing {missing[:5]}, unexpected {unexpected[:5]}")

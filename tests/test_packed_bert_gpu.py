@@ -285,7 +285,7 @@ def test_packed_bert_embedding_forward_backward(tmp_path, random_init):
     for _ in range(2):
         gflat = torch.zeros(tr._total, device=DEV)
         with torch.no_grad():
-            tr._embedding_backward(bert._layout(tr, p), g.to(DEV), gflat)
+            tr._embedding_backward(bert.layout.of(tr, p), g.to(DEV), gflat)
         grads.append(gflat)
     torch.cuda.synchronize()
     assert torch.equal(grads[0], grads[1])
