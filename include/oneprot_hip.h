@@ -468,6 +468,62 @@ int oneprot_msa_tokenize(const void* msa_bytes, const int64_t* table, const int*
                          int64_t* seq_tokens, const int64_t* table_host, int64_t n_bytes, int n, int k_max, int R_max, int Lt_max, int Ls_max,
                          int max_length, int64_t T_pad, int cls_id, int pad_id, int eos_id, void* stream);
 
+/* ---------------- ProNet tower (ref src/models/components/struct_graph_encoder.py:5-42 plugs in dig.threedgraph.method.ProNet; the arithmetic is the
+ * published model's, Wang et al. 2023, restated: DESIGN.md section 7, tests/pronet_ref.py is the oracle) ----------------------------------------------
+ * N nodes of n_graphs graphs in one batch, a graph's nodes contiguous: graph_ptr int32 [n_graphs + 1], batch int32 [N].  Edges are stored by target in a
+ * table ONEPROT_PRONET_SLOTS wide: nbr int32 [N, 32] (sources ascending, -1 behind the first deg[i]), and "slot" i * 32 + e names edge e of target i in
+ * every per-edge array.  N <= 2^26.  All of it fp32, no atomics: every sum runs in a fixed order and two runs give the same bits. */
+#define ONEPROT_PRONET_SLOTS 32
+/* Replaces torch_cluster.radius_graph(pos, r=cutoff, batch, max_num_neighbors) in ProNet.forward: sources j != i of i's graph with |ca_j - ca_i|^2 <=
+   cutoff^2 (fp32: products and sums rounded one by one, no FMA), the max_num_neighbors <= 32 LOWEST indices when more are in range (torch_cluster's
+   GPU rule).  Any graph size. */
+int oneprot_radius_graph(const float* ca, const int* graph_ptr, const int* batch, int* nbr, int* deg, int N, int n_graphs, float cutoff, int max_num_neighbors,
+                         void* stream);
+/* The same edges grouped by source (what autograd's scatter-add backward of `x_j = x[edge_index[0]]` walks with float atomics): src_off int32 [N + 1],
+   src_list int32 [32 N] of slots, for every source its edges with the target ascending.  count_ws int32 [N].  Nothing is read back. */
+int oneprot_graph_by_source(const int* graph_ptr, const int* batch, const int* nbr, const int* deg, int* count_ws, int* src_off, int* src_list, int N,
+                            int n_graphs, void* stream);
+/* Replaces ProNet.forward's per-edge geometry (dist, theta, phi from the CA triplets with neighbours (i -+ 1) mod N over the whole batch; the three Euler
+   angles between the backbone frames of i and j) and its three embeddings (emb: dist / theta / phi -> feature0 [4 nr]; the torsion embedding on the
+   Euler angles -> feature1 [6 nr]; the sinusoidal j - i embedding -> feature2 [np]), num_spherical = 2, no envelope.  consts fp32 [4 nr + np / 2]:
+   the Bessel zeros z_{l,n} (l major), the normalisers sqrt(2) / |j_{l+1}(z_{l,n})|, the np / 2 frequencies.  f0 / f1 / f2 are [32 N, width]; unfilled
+   slots are written as 0.  noise != 0: each Euler angle gains clip(sigma * normal, +-clip), the normals being Box-Muller pairs (uniforms ((w >> 9) + 1/2) 2^-23: r = sqrt(-2 ln u1), r cos 2 pi u2 and r sin 2 pi u2) of
+   Philox4x32-10(counter = slot, stream_id; key = seed), words (0, 1) -> angles 0 and 1, words (2, 3) -> angle 2.  nr <= 8, np even <= 48. */
+int oneprot_pronet_edge_features(const float* ca, const float* cn, const float* cc, const int* nbr, const int* deg, const float* consts, float* f0, float* f1,
+                                 float* f2, int N, int num_radial, int num_pos_emb, float cutoff, int noise, float sigma, float clip, uint64_t seed,
+                                 uint64_t stream_id, void* stream);
+/* Replaces DIG's EdgeGraphConv (propagate with message = edge_weight * x_j, aggr add) together with the TwoLinear that makes edge_weight:
+   m[i, :] = sum_e (W2 W1 feat[i * 32 + e, :]) * a[nbr[i, e], :].  WfT fp32 [F, h] is the folded operand (W2 W1)^T; neither w_e nor the messages are
+   written.  h a multiple of 64 up to 256, F <= 48. */
+int oneprot_edge_conv_fwd(const float* feat, const float* WfT, const float* a, const int* nbr, const int* deg, float* m, int N, int h, int F, void* stream);
+/* Its data gradient (autograd's index_add of dm[i] * w_e into source j): da[j, :] = sum over the edges out of j, targets ascending, w_e recomputed. */
+int oneprot_edge_conv_bwd_x(const float* feat, const float* WfT, const float* dm, const int* src_off, const int* src_list, float* da, int N, int h, int F,
+                            void* stream);
+/* The gradient of the folded operand (autograd's two TwoLinear weight gradients over [E, .] operands): dWfT[f, c] = sum_e dm[i, c] a[j, c] feat[slot, f];
+   per-work-group partials over fixed target ranges, then one ordered sum.  workspace: oneprot_edge_conv_bwd_w_workspace bytes (0 for a bad shape). */
+size_t oneprot_edge_conv_bwd_w_workspace(int N, int h, int F);
+int oneprot_edge_conv_bwd_w(const float* feat, const float* a, const float* dm, const int* nbr, const int* deg, float* dWfT, void* workspace,
+                            size_t workspace_bytes, int N, int h, int F, void* stream);
+/* Replaces ProNet.forward's `self.embedding(torch.cat([F.one_hot(z, 26), bb_embs], dim=1))`: a gathered weight column, a 6-wide product and the bias.
+   W fp32 [h, 32], z int64 [N], bb fp32 [N, 6]; feat_out (optional) fp32 [N, 32] is the concatenated input, the operand of the weight-gradient GEMM. */
+int oneprot_pronet_embed_fwd(const int64_t* z, const float* bb, const float* W, const float* b, float* x0, float* feat_out, int N, int h, void* stream);
+/* The node-side row ops around oneprot_sgemm (torch's `act(lin(x))`, swish = x * sigmoid(x), F.relu): z[M, n] += bias in place (bias optional), then
+   y[r * ldy + c] = act(z[r, c]) + resid[r, c] (y, resid optional; ldy >= n writes into a column block of a wider matrix, which is torch.cat).
+   act 0 identity, 1 swish, 2 relu.  The backward: dz[r, c] = dy[r * ldy + c] * act'(z[r, c]). */
+int oneprot_pronet_bias_act(float* z, const float* bias, const float* resid, float* y, int64_t M, int n, int ldy, int act, void* stream);
+int oneprot_pronet_act_bwd(const float* dy, const float* z, float* dz, int64_t M, int n, int ldy, int act, void* stream);
+/* out[c] = sum_r x[r, c] of an fp32 [M, n] matrix (autograd's bias gradient `grad.sum(0)` with M = every node of the batch): blocked summation in a
+   fixed order, no chain longer than 8, in parallel over row chunks -- oneprot_rowsum_f32 is one serial chain per column, made for a handful of rows.
+   workspace: oneprot_colsum_f32_workspace(M, n) bytes (0 for a bad shape). */
+size_t oneprot_colsum_f32_workspace(int64_t M, int n);
+int oneprot_colsum_f32(const float* x, float* out, void* workspace, size_t workspace_bytes, int64_t M, int n, void* stream);
+/* Replaces `x + torch.clip(torch.empty_like(x).normal_(0, sigma), -clip, clip)` (ProNet's data_augment_eachlayer): element e takes normal e & 3 of
+   Philox4x32-10(counter = e >> 2, stream_id; key = seed), Box-Muller as above.  n a multiple of 4; y may alias x.  Its backward is the identity. */
+int oneprot_clipped_normal_add_f32(const float* x, float* y, int64_t n, float sigma, float clip, uint64_t seed, uint64_t stream_id, void* stream);
+/* Replaces torch_scatter's `scatter(x, batch, dim=0)` (sum readout) and its backward: y[g] = sum of the rows of graph g in index order; dx[i] = dy[batch[i]]. */
+int oneprot_segment_sum_f32(const float* x, const int* graph_ptr, float* y, int n_graphs, int d, void* stream);
+int oneprot_segment_sum_bwd_f32(const float* dy, const int* batch, float* dx, int N, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

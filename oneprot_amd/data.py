@@ -12,6 +12,9 @@ checkpoint wire format (section 8f #3).
   `packed_text=True`, which packs it with BERT's pad id 0.  Modality "msa" (ref msa_dataset.py's batches): tokens [B, msa_depth, Lm] over the 33-symbol
   alphabet, cls 0 in column 0, pad 1; ragged MSAs are shorter AND shallower (trailing rows fully padded); the MSA side stays padded unless `packed_msa=True`, which yields it as an
   oneprot_amd.packing.PackedMsa (each MSA at its own depth and length; off by default, like `packed_text`, and independent of `packed`).
+  Modality "pocket" / "struct_graph" (ref struct_graph_dataset.py's batches): the modality side is an oneprot_amd.graph_data.GraphBatch of `batch_size`
+  synthetic proteins of `mod_len` residues (ragged: between a quarter of it and all of it) -- a random-walk backbone with 3.8 A CA steps, N and C at
+  1.46 A and 1.52 A from CA, backbone features through calc_bb_embs -- for the ProNet tower of oneprot_amd/pronet.py.
 * `save_checkpoint` / `load_weights_only` -- Lightning-style {"state_dict": {...}} files with the reference's key names
   (`network.<modality>.transformer....`), loaded exactly as ref src/train.py:73-82 does (optional 'model.' prefix, strict=True, weights only).
 """
@@ -90,6 +93,14 @@ class SyntheticPairs:
         gen = torch.Generator().manual_seed(self.seed)
         for _ in range(self.n):
             seq = self._frame(gen, self.B, self.Ls, 4, 23, 0, 2, 1, self.ragged)
+            if self.modality in ("pocket", "struct_graph"):
+                from .graph_data import GraphBatch, synthetic_protein
+                lens = torch.randint(max(self.Lm // 4, 2), self.Lm + 1, (self.B,), generator=gen) if self.ragged else torch.full((self.B,), self.Lm)
+                mod = GraphBatch.from_data_list([synthetic_protein(int(n), gen) for n in lens])
+                if self.packed:
+                    seq = PackedTokens.from_padded(seq, pad_id=1)
+                yield seq.to(self.device), mod.to(self.device), self.modality, None
+                continue
             if self.modality == "msa":
                 mod = self._msa_frame(gen, self.B, self.msa_depth, self.Lm, self.ragged)
                 if self.packed:

@@ -142,6 +142,14 @@ else:
     _Base = _PlainBase
 
 
+def _rng_owner(enc):
+    """the tower of an encoder that owns counter-based dropout / noise streams: `transformer` (ESM, BERT, MSA), or the graph tower of StructEncoder"""
+    tr = getattr(enc, "transformer", None)
+    if tr is None and hasattr(getattr(enc, "encoder", None), "rng_state"):
+        tr = enc.encoder
+    return tr
+
+
 class OneProtLitModule(_Base):
     def __init__(self, components: Dict[str, Any], optimizer: Any, train_on_all_modalities_after_step: int = 0, scheduler: Any = None,
                  use_seqsim: bool = False, loss_fn: str = 'CLIP', use_l1_regularization: bool = False, local_loss: bool = True,
@@ -158,7 +166,7 @@ class OneProtLitModule(_Base):
         # tower under two names draw different masks) rather than to the construction order the tower numbered itself with
         import zlib
         for name, enc in self.network.items():
-            tr = getattr(enc, "transformer", None)
+            tr = _rng_owner(enc)
             if hasattr(tr, "_rng_uid"):
                 tr._rng_uid = zlib.crc32(name.encode()) & 0xFFFF
         self.train_on_all_modalities_after_step = train_on_all_modalities_after_step
@@ -357,18 +365,16 @@ class OneProtLitModule(_Base):
     # -- and live outside the state dict, whose key set is the reference's on-disk contract: they travel in a checkpoint entry of their own, so that
     # a resumed run continues the mask sequence instead of replaying it from call 0.
     def on_save_checkpoint(self, checkpoint):
-        checkpoint["oneprot_amd_dropout_rng"] = {m: enc.transformer.rng_state() for m, enc in self.network.items()
-                                                 if hasattr(getattr(enc, "transformer", None), "rng_state")}
+        checkpoint["oneprot_amd_dropout_rng"] = {m: _rng_owner(enc).rng_state() for m, enc in self.network.items() if hasattr(_rng_owner(enc), "rng_state")}
 
     def on_load_checkpoint(self, checkpoint):
         saved = checkpoint.get("oneprot_amd_dropout_rng") or {}
         for m, state in saved.items():
-            tr = getattr(self.network[m], "transformer", None) if m in self.network else None
+            tr = _rng_owner(self.network[m]) if m in self.network else None
             if hasattr(tr, "set_rng_state"):
                 tr.set_rng_state(state)
         if saved:      # a tower with dropout streams that the checkpoint knows nothing about would silently restart its mask sequence
-            missing = [m for m, enc in self.network.items() if m not in saved and getattr(enc, "transformer", None) is not None
-                       and hasattr(enc.transformer, "rng_state") and enc.transformer.rng_state()]
+            missing = [m for m, enc in self.network.items() if m not in saved and hasattr(_rng_owner(enc), "rng_state") and _rng_owner(enc).rng_state()]
             if missing:
                 import warnings
                 warnings.warn(f"checkpoint carries no dropout stream state for {missing}: their mask sequences restart from call 0")

@@ -1,0 +1,142 @@
+"""ProNet without a GPU: the restatement's self-checks (tests/pronet_ref.py), the constructor's refusals, the published state-dict key set, the
+configs, and the condition every GPU graph fixture must satisfy."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oneprot_amd import pronet as P
+from tests import pronet_ref as R
+from tests.pronet_fixtures import CUTOFF, MARGIN, MIXED, conv_case, mixed_batch, pair_margin, small_batch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_bessel_zeros_and_the_hosts_constants():
+    from scipy.special import spherical_jn
+    z = R.bessel_zeros(8)
+    for l in (0, 1):
+        assert np.abs(spherical_jn(l, z[l])).max() < 1e-12
+        assert (np.diff(z[l]) > 3.0).all() and z[l][0] > 3.0                       # the FIRST positive zeros, none skipped
+    zeros, norms = P.bessel_constants(8)                                           # the product's own root finder and normalisers
+    assert np.abs(np.array(zeros) - z).max() < 1e-12
+    assert np.abs(np.array(norms) - R.bessel_norms(z)).max() < 1e-10
+    c = P.feature_constants(6, 16)
+    assert c.dtype == torch.float32 and c.shape == (4 * 6 + 8,) and float(c[24]) == 1.0
+
+
+def test_radial_functions_are_orthonormal():
+    """integral over [0, 1] of rbf[l, n](d) rbf[l, m](d) d^2 = delta_nm, Gauss-Legendre with 200 nodes"""
+    x, w = np.polynomial.legendre.leggauss(200)
+    d, w = torch.from_numpy(0.5 * (x + 1.0)), torch.from_numpy(0.5 * w)
+    rb = R.rbf(d, 6)                                                               # [200, 2, 6]
+    for l in (0, 1):
+        gram = torch.einsum("q,qn,qm->nm", w * d ** 2, rb[:, l], rb[:, l])
+        assert float((gram - torch.eye(6, dtype=torch.float64)).abs().max()) < 1e-6
+
+
+def test_gradcheck_of_one_block():
+    b = small_batch()
+    assert b.num_nodes == 12
+    h, mid, pre = 8, 4, "interaction_blocks.0."                                      # the restatement alone: any width, the published names
+    gen = torch.Generator().manual_seed(0)
+    shapes = {f"{pre}lin_feature{c}.lin1.weight": (mid, F) for c, F in enumerate((24, 36, 16))}
+    shapes.update({f"{pre}lin_feature{c}.lin2.weight": (h, mid) for c in range(3)})
+    shapes.update({f"{pre}conv{c}.lin_r.weight": (h, h) for c in range(3)})
+    for name in [f"conv{c}.lin_l" for c in range(3)] + [f"lin{c}" for c in range(3)] + ["lin_1", "lin_2", "final", "lins_cat.1", "lins_cat.2", "lins.0", "lins.1"]:
+        shapes.update({f"{pre}{name}.weight": (h, h), f"{pre}{name}.bias": (h,)})
+    shapes.update({f"{pre}lins_cat.0.weight": (h, 3 * h), f"{pre}lins_cat.0.bias": (h,)})
+    sd = {k: torch.randn(*v, generator=gen, dtype=torch.float64) * 0.5 for k, v in shapes.items()}
+    names = list(sd)
+    nbr, deg = R.radius_graph(b.coords_ca.numpy(), b.ptr.numpy(), CUTOFF, 32)
+    feats = R.edge_features(b.coords_ca, b.coords_n, b.coords_c, nbr, deg)
+    slot, i, j = R.edge_index(nbr, deg)
+    x = torch.randn(12, h, generator=gen, dtype=torch.float64, requires_grad=True)
+    params = [sd[k].clone().requires_grad_() for k in names]
+
+    def f(x, *ps):
+        return R.block({**sd, **dict(zip(names, ps))}, "interaction_blocks.0.", x, feats, slot, i, j)
+    assert torch.autograd.gradcheck(f, (x, *params), eps=1e-6, atol=1e-6, rtol=1e-4)
+
+
+@pytest.mark.parametrize("kw, what", [
+    (dict(), "level"), (dict(level="aminoacid"), "level"), (dict(level="allatom"), "level"),
+    (dict(level="backbone", num_spherical=3), "num_spherical"), (dict(level="backbone", max_num_neighbors=33), "max_num_neighbors"),
+    (dict(level="backbone", hidden_channels=96), "hidden_channels"), (dict(level="backbone", hidden_channels=320), "hidden_channels"),
+    (dict(level="backbone", mid_emb=129), "mid_emb"), (dict(level="backbone", num_radial=9), "num_radial"), (dict(level="backbone", num_pos_emb=15), "num_pos_emb"),
+])
+def test_constructor_refusals(kw, what):
+    with pytest.raises(NotImplementedError, match=what):
+        P.ProNet(**kw)
+
+
+def test_state_dict_keys_are_the_published_names():
+    tower = P.ProNet(level="backbone", num_blocks=2, hidden_channels=64, out_channels=5, out_layers=3, int_emb_layers=2)
+    want = {"embedding.weight", "embedding.bias", "lin_out.weight", "lin_out.bias"}
+    want |= {f"lins_out.{k}.{p}" for k in range(2) for p in ("weight", "bias")}
+    for b in range(2):
+        pre = f"interaction_blocks.{b}."
+        for c in range(3):
+            want |= {f"{pre}conv{c}.lin_l.weight", f"{pre}conv{c}.lin_l.bias", f"{pre}conv{c}.lin_r.weight", f"{pre}lin_feature{c}.lin1.weight",
+                     f"{pre}lin_feature{c}.lin2.weight", f"{pre}lin{c}.weight", f"{pre}lin{c}.bias"}
+        for name in ["lin_1", "lin_2", "final"] + [f"lins_cat.{k}" for k in range(2)] + [f"lins.{k}" for k in range(1)]:
+            want |= {f"{pre}{name}.weight", f"{pre}{name}.bias"}
+    sd = tower.state_dict()
+    assert set(sd) == want
+    assert sd["embedding.weight"].shape == (64, 32) and sd["interaction_blocks.0.lins_cat.0.weight"].shape == (64, 192)
+    assert sd["interaction_blocks.1.lin_feature1.lin1.weight"].shape == (64, 36) and sd["interaction_blocks.1.lin_feature2.lin2.weight"].shape == (64, 64)
+    assert sd["lin_out.weight"].shape == (5, 64) and all(v.dtype == torch.float32 for v in sd.values())
+    assert all(type(p) is torch.nn.Parameter for p in tower.parameters())
+
+
+def test_rng_state_round_trip_and_stream_domains():
+    a, b = P.ProNet(level="backbone"), P.ProNet(level="backbone")
+    assert a._rng_uid != b._rng_uid
+    sites = {t.stream_of(call, s) for t in (a, b) for call in range(3) for s in range(2 * 4 + 2 + 1)}
+    assert len(sites) == 2 * 3 * 11 and all(s >> 60 == P.RNG_DOMAIN_PRONET for s in sites)
+    st = a.rng_state()
+    a._drop_calls += 5
+    b.set_rng_state(a.rng_state())
+    assert b.rng_state() == a.rng_state() != st
+
+
+def test_graph_configs_compose_and_instantiate_without_a_device():
+    from oneprot_amd.config import compose, instantiate
+    c = compose(os.path.join(ROOT, "configs"), "train", overrides={"model": "oneprot_graph"})
+    comps = c["model"]["components"]
+    assert list(comps) == ["sequence", "struct_graph", "pocket", "text"]                 # the reference's default composition
+    for name in ("pocket", "struct_graph"):
+        assert comps[name]["encoder"]["_target_"] == "oneprot_amd.pronet.ProNet"
+        assert comps[name]["encoder"]["out_channels"] == comps[name]["output_dim"] == comps["sequence"]["output_dim"]
+        enc = instantiate(comps[name])
+        tower = enc.encoder
+        assert type(tower) is P.ProNet and (tower.level, tower.dropout, tower.euler_noise, tower.data_augment_eachlayer) == ("backbone", 0.25, True, True)
+        assert tower.out_channels == comps[name]["output_dim"] and all(p.device.type == "cpu" for p in enc.parameters())
+        dm = compose(os.path.join(ROOT, "configs"), f"data/modalities/{name}", resolve=False)["data"]["modalities"][name]
+        assert dm["dataset"]["pocket"] == (name == "pocket") and dm["batch_size"]["train"] == 16
+        from src.data.datasets.struct_graph_dataset import StructDataset
+        ds = StructDataset(split="val", **dm["dataset"])                                 # the reference's constructor arguments; a missing csv is reported, not raised
+        assert len(ds) == 1000 and ds.pocket == (name == "pocket")
+    unchanged = compose(os.path.join(ROOT, "configs"), "train")["model"]["components"]
+    assert list(unchanged) == ["sequence", "struct_token"]
+
+
+def test_fixture_condition():
+    """every graph fixture used on the GPU: | |ca_j - ca_i| - cutoff | >= 1e-4 A for all same-graph pairs, coordinates within +-64 A"""
+    for batch in (mixed_batch(), small_batch()):
+        ptr = batch.ptr.tolist()
+        assert float(batch.coords_ca.abs().max()) <= 64.0
+        for a, b in zip(ptr[:-1], ptr[1:]):
+            assert pair_margin(batch.coords_ca[a:b].numpy()) >= MARGIN
+    b = mixed_batch()
+    assert [n for _, n in MIXED] == np.diff(b.ptr.numpy()).tolist()
+    nbr, deg = R.radius_graph(b.coords_ca.numpy(), b.ptr.numpy(), CUTOFF, 32)
+    assert deg.min() == 0 and deg.max() == 32 and 0 < deg[int(b.ptr[6]):].min() < 32       # under the cap, at it, and beyond it (the 34-node ball)
+    ball = b.coords_ca[int(b.ptr[3]):int(b.ptr[4])].double()
+    assert float(torch.cdist(ball, ball).max()) < CUTOFF - MARGIN                            # 34 in range of each other: the cap is exceeded
+    line = b.coords_ca[int(b.ptr[5]):int(b.ptr[6])]
+    assert float(torch.cross(line[1] - line[0], line[2] - line[0], dim=-1).abs().max()) == 0.0     # exactly collinear
+    nbr_c, deg_c, *_ = conv_case()
+    off, _ = R.by_source(nbr_c, deg_c)
+    assert set(deg_c.tolist()) == {0, 1, 31, 32} and np.diff(off)[0] > 32 and np.diff(off)[-1] == 0

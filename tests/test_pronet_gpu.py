@@ -1,0 +1,147 @@
+"""The ProNet tower (oneprot_amd/pronet.py) on the HIP kernels against the fp64 restatement under autograd (tests/pronet_ref.py): output and every
+parameter gradient at h = 128, 2 blocks, on the mixed batch of tests/pronet_fixtures.py (graphs of 2, 1, 33, 34, 100, 5 and 300 nodes).
+
+The bound is measured, not chosen: the restatement is also run in fp32 torch (every contraction of the HIP path is fp32, so no autocast) and its
+relative L2 error against fp64 is taken per tensor; the HIP path is allowed 4 x that, a different summation order being worth a small factor and no
+more.  Measured on the MI355X (output and 80 gradients; fp32 restatement on the CPU):
+  eval   fp32 torch 3.9e-8 .. 4.7e-7 (mean 2.4e-7, output 3.8e-7)   HIP 3.7e-8 .. 5.3e-7 (mean 3.2e-7, output 5.0e-7)   worst HIP / fp32 ratio 1.85
+  train  fp32 torch 3.9e-8 .. 3.3e-7                                HIP 3.7e-8 .. 4.4e-7                                worst ratio 1.92
+so the bound in force is 4 x (3.9e-8 .. 4.7e-7) per tensor, i.e. at most 1.9e-6.  Every figure is printed before the assertion (-s)."""
+import functools
+import os
+
+import pytest
+import torch
+
+from oneprot_amd import pronet as P
+from tests import pronet_ref as R
+from tests import pronet_rng_ref as RNG
+from tests.pronet_fixtures import CUTOFF, mixed_batch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+CFG = dict(num_blocks=2, num_radial=6, num_pos_emb=16, cutoff=CUTOFF, max_num_neighbors=32, int_emb_layers=3, out_layers=2)
+FACTOR = 4.0
+
+
+def make_tower(**kw):
+    torch.manual_seed(21)
+    return P.ProNet(level="backbone", num_blocks=2, hidden_channels=128, out_channels=8, **kw)
+
+
+def rel_l2(a, ref):
+    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
+    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
+
+
+def reference(sd, batch, dtype, cot, aug=None):
+    """(output, {name: gradient}) of the restatement in `dtype`, the loss being sum(out * cot)"""
+    p = {k: v.detach().to(dtype).clone().requires_grad_() for k, v in sd.items()}
+    out = R.forward(p, batch, dtype=dtype, aug=aug, **CFG)
+    (out * cot.to(dtype)).sum().backward()
+    return out.detach(), {k: v.grad for k, v in p.items()}
+
+
+def run_hip(tower, batch, cot):
+    tower.zero_grad(set_to_none=True)
+    out = tower(batch)
+    (out * cot.to(DEV)).sum().backward()
+    return out.detach(), {k: v.grad.clone() for k, v in tower.named_parameters()}
+
+
+def check(tower, sd, aug, cot, label):
+    batch = mixed_batch()
+    out64, g64 = reference(sd, batch, torch.float64, cot, aug)
+    out32, g32 = reference(sd, batch, torch.float32, cot, aug)
+    out, g = run_hip(tower, batch.to(DEV), cot)
+    assert out.shape == (batch.num_graphs, 8) and out.dtype == torch.float32
+    rows = [("output", rel_l2(out32, out64), rel_l2(out, out64))] + [(k, rel_l2(g32[k], g64[k]), rel_l2(g[k], g64[k])) for k in g64]
+    for name, e32, ehip in rows:
+        print(f"{label} {name:60s} fp32-torch {e32:.3e}  hip {ehip:.3e}  ratio {ehip / max(e32, 1e-30):.2f}")
+    assert set(g) == set(g64)
+    bad = [(n, e32, eh) for n, e32, eh in rows if not eh <= FACTOR * e32]
+    assert not bad, f"{label}: outside {FACTOR} x the fp32 restatement's own error: {bad[:5]} ({len(bad)} of {len(rows)})"
+    return out, g
+
+
+@pytest.fixture(scope="module")
+def cot():
+    return torch.randn(7, 8, generator=torch.Generator().manual_seed(8))
+
+
+def test_tower_eval_output_and_gradients_vs_fp64(cot):
+    tower = make_tower().to(DEV).eval()
+    sd = {k: v.cpu() for k, v in tower.state_dict().items()}
+    out, g = check(tower, sd, None, cot, "eval")
+    out2, g2 = run_hip(tower, mixed_batch().to(DEV), cot)                    # same state twice: the same bits
+    assert torch.equal(out, out2) and all(torch.equal(g[k], g2[k]) for k in g)
+    with torch.no_grad():                                                    # no tape without grad mode, same forward
+        assert torch.equal(tower(mixed_batch().to(DEV)), out)
+    loss = tower(mixed_batch().to(DEV)).sum()
+    loss.backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="second backward"):               # the tape is played once: loud, not a silent None
+        loss.backward()
+
+
+def _aug(tower, batch, call):
+    """every mask and normal of forward call `call`, rebuilt on the host"""
+    N, h, G, nb = batch.num_nodes, tower.hidden_channels, batch.num_graphs, tower.num_blocks
+    seed = tower._drop_seed
+    return {"euler": RNG.euler_noise(N * 32, seed, tower.stream_of(call, 0)),
+            "x_noise": [RNG.node_noise((N, h), seed, tower.stream_of(call, 1 + 2 * b)) for b in range(nb)],
+            "keep_H": [RNG.keep_mask((N, 3 * h), tower.dropout, seed, tower.stream_of(call, 2 + 2 * b)) for b in range(nb)],
+            "keep_out": [RNG.keep_mask((G, h), tower.dropout, seed, tower.stream_of(call, 1 + 2 * nb + k)) for k in range(tower.out_layers - 1)]}
+
+
+def test_tower_train_mode_with_rebuilt_masks_and_normals(cot):
+    tower = make_tower(dropout=0.25, euler_noise=True, data_augment_eachlayer=True).to(DEV).train()
+    sd = {k: v.cpu() for k, v in tower.state_dict().items()}
+    state = tower.rng_state()
+    assert state["_drop_calls"] == 0
+    aug = _aug(tower, mixed_batch(), 0)
+    assert 0.70 < float(aug["keep_H"][0][0].float().mean()) < 0.80
+    out, g = check(tower, sd, aug, cot, "train")
+    assert tower.rng_state()["_drop_calls"] == 1
+    out_next, _ = run_hip(tower, mixed_batch().to(DEV), cot)                 # the next call draws anew
+    assert not torch.equal(out_next, out)
+    tower.set_rng_state(state)                                               # the saved position replays call 0 bit for bit
+    out2, g2 = run_hip(tower, mixed_batch().to(DEV), cot)
+    assert torch.equal(out, out2) and all(torch.equal(g[k], g2[k]) for k in g)
+    tower.eval()                                                             # eval: no draw, the position stays
+    before = tower.rng_state()
+    tower(mixed_batch().to(DEV))
+    assert tower.rng_state() == before
+
+
+def test_through_the_module_as_pocket(tmp_path):
+    os.environ.update(RANK="0", WORLD_SIZE="1", ONEPROT_ALLOW_RANDOM_INIT="1")
+    from oneprot_amd.data import load_weights_only, save_checkpoint
+    from oneprot_amd.optim import FusedAdam
+    from src.models.components.sequence_encoder import SequenceEncoder
+    from src.models.components.struct_graph_encoder import StructEncoder
+    from src.models.oneprot_module import OneProtLitModule
+
+    def build():
+        torch.manual_seed(9)
+        seq = SequenceEncoder("facebook/esm2_t6_8M_UR50D", output_dim=64, pooling_type="mean", proj_type="linear", use_lora=False, frozen=True)
+        pocket = StructEncoder(P.ProNet(level="backbone", out_channels=64, dropout=0.25, euler_noise=True, data_augment_eachlayer=True), output_dim=64,
+                               proj_type="linear", use_logit_scale=True)
+        return OneProtLitModule(components={"sequence": seq, "pocket": pocket}, optimizer=functools.partial(FusedAdam, lr=1e-3), loss_fn="CLIP",
+                                use_l1_regularization=True).to(DEV)
+    module = build()
+    gb = mixed_batch()
+    gen = torch.Generator().manual_seed(4)
+    ids = torch.randint(4, 24, (gb.num_graphs, 32), generator=gen)
+    ids[:, 0], ids[:, -1] = 0, 2
+    batch = {"pocket": (ids.to(DEV), gb.to(DEV), "pocket", None)}
+    losses = [float(module.training_step(batch, i).detach()) for i in range(8)]
+    assert all(torch.isfinite(torch.tensor(losses))) and losses[-1] < losses[0], losses
+    path = str(tmp_path / "pocket.ckpt")
+    save_checkpoint(module, path)
+    other = build()
+    res = load_weights_only(other, path)
+    assert not res.missing_keys and not res.unexpected_keys
+    a, b = module.state_dict(), other.state_dict()
+    assert set(a) == set(b) and all(torch.equal(a[k].cpu(), b[k].cpu()) for k in a)
+    assert any(k.startswith("network.pocket.encoder.interaction_blocks.0.conv0.lin_l.") for k in a)
+    assert other.network["pocket"].encoder.rng_state() == module.network["pocket"].encoder.rng_state()      # the draw position travels with the checkpoint
