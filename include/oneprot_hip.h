@@ -524,6 +524,44 @@ int oneprot_clipped_normal_add_f32(const float* x, float* y, int64_t n, float si
 int oneprot_segment_sum_f32(const float* x, const int* graph_ptr, float* y, int n_graphs, int d, void* stream);
 int oneprot_segment_sum_bwd_f32(const float* dy, const int* batch, float* dx, int N, int d, void* stream);
 
+/* ---------------- downstream metrics (ref src/utils/downstream.py:12-59 count_f1_max; ref src/saprot_fit_cls.py:41-65 and src/saprot_fit_mlp.py:298-330
+ * score with sklearn's roc_auc_score / accuracy_score / f1_score / mean_squared_error / r2_score and scipy's spearmanr) -------------------------------------
+ * A stable sort, midranks and ordered scans, and F1-max on top of them.  1 <= n <= 2^31 - 1 everywhere.  No work-group waits on another; a radix pass is
+ * three launches (histogram per tile of ONEPROT_SORT_TILE keys, scan of the [256, tiles] table, ranked scatter).  Two runs give the same bits: the order
+ * inside a tile comes from wave ballots and prefix counts, and every floating-point sum runs through one fixed tree whose shape depends on n alone.
+ * Nothing is read back.  Workspaces are 8-byte aligned; a *_workspace() query returns 0 for invalid arguments. */
+#define ONEPROT_SORT_TILE 2048
+#define ONEPROT_SCAN_TILE 2048
+/* Replaces `pred.flatten().argsort(descending=...)` (ref downstream.py:35; torch's argsort is unstable): perm int32 [n], sorted_keys (optional) fp32 [n].
+   LSD radix, four 8-bit passes over the order-preserving bit map of the keys; -0.0 is made +0.0 first, so the zeros are equal keys; +-inf sort as values;
+   NaN is outside the contract.  Equal keys keep ASCENDING index in both directions (descending sorts the complemented key). */
+size_t oneprot_sort_workspace(int64_t n);
+int oneprot_sort_f32(const float* keys, int64_t n, int descending, int* perm, float* sorted_keys, void* workspace, size_t workspace_bytes, void* stream);
+/* Stable ascending sort of non-negative int32 keys below 2^key_bits (1 <= key_bits <= 31; ceil(key_bits / 8) passes) with int32 values; values NULL means
+   0 .. n-1 (an argsort); keys_out optional.  The outputs must not be the inputs.  workspace: oneprot_sort_workspace(n). */
+int oneprot_sort_i32(const int* keys, const int* values, int64_t n, int key_bits, int* keys_out, int* values_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Replaces scipy.stats.rankdata(x, "average") inside spearmanr and roc_auc_score's tie handling: rank2[i] = first + last + 2 of the run of equal keys that
+   holds x[i] in the ascending order (0-based positions) = twice the average 1-based rank, an exact integer (read it unsigned beyond n = 2^30). */
+size_t oneprot_midranks_workspace(int64_t n);
+int oneprot_midranks_f32(const float* x, int64_t n, int* rank2, void* workspace, size_t workspace_bytes, void* stream);
+/* Replaces `x.cumsum(0)` (ref downstream.py:31-32, 52-57; torch's GPU cumsum fixes no order): y[i] = x[s] + ... + x[i], s the last multiple of seg_len at or
+   below i (seg_len 0: s = 0).  is_f64 0: int32 streams, 1: fp64 streams; y may be x. */
+size_t oneprot_scan_workspace(int64_t n);
+int oneprot_inclusive_scan(const void* x, void* y, int64_t n, int64_t seg_len, int is_f64, void* workspace, size_t workspace_bytes, void* stream);
+/* The sums behind accuracy_score / mean_squared_error / r2_score / the Pearson step of spearmanr, in fp64 over two fp32 (is_i32 0) or int32 (1) streams, with
+   a' = a - shift_a and b' = b - shift_b formed in fp64: moments_bytes = 8 doubles {n, sum a', sum b', sum a'^2, sum b'^2, sum a'b', sum (a'-b')^2,
+   #(a == b)}.  A shift only conditions the sums; the caller undoes it algebraically, so it need not be exact. */
+size_t oneprot_moments_workspace(int64_t n);
+int oneprot_moments(const void* a, const void* b, int64_t n, int is_i32, float shift_a, float shift_b, void* moments_bytes, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* Replaces count_f1_max (ref downstream.py:12-59) for pred fp32 [B, N] and target [B, N] in {0, 1} (int32, or fp32 with target_is_f32 = 1), B * N < 2^31:
+   all scores in descending order, equal scores in ascending flat index; after each element k of row i, cnt_i += 1, tp_i += target; P_k = mean over the rows
+   with cnt > 0 of tp_i / cnt_i, R_k = mean over all B rows of tp_i / (T_i + 1e-10), F_k = 2 P_k R_k / (P_k + R_k + 1e-10).  f1_bytes = 2 doubles
+   {max_k F_k, the score at the first k that reaches it}.  Counts are integers, the quotients and running sums fp64. */
+size_t oneprot_f1max_workspace(int B, int N);
+int oneprot_f1max(const float* pred, const void* target, int target_is_f32, int B, int N, void* f1_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

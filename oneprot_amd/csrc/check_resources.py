@@ -21,6 +21,7 @@ RULES = [
     (r"^void k_sim_", 0),                       # retrieval: similarity tile + rank count / top-k selection / diagonal
     (r"^(void )?k_msa_", 0),                           # MSA tower: embedding, tied row scores / context, column attention
     (r"^(void )?k_pronet_", 0),                        # ProNet tower: graph, edge features, fused edge convolution (48 weights or partials per thread in registers)
+    (r"^(void )?k_metrics_", 0),                       # downstream metrics: radix sort passes, ordered scans and sums, F1-max
 ]
 
 

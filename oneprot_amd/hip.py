@@ -6,7 +6,8 @@ raises.  torch is used only as the owner of device memory and streams (tensor.da
 The header is the single source of the ABI: the ctypes signatures (_SIGS) and the expected element type of every pointer argument (_PTR_DTYPES) are
 parsed from it at import, so a new entry point is declared there, defined in csrc/, and needs nothing here unless one of its void* is not bf16
 (_BYTE_PTRS / _FLAG_TYPED_PTRS).  call(name, *positional) launches any entry point; gemm_nt / gemm_tn / layernorm_fwd / layernorm_bwd are keyword
-launchers of the four widest ones and end in the same call().
+launchers of the four widest ones and end in the same call().  sort_f32 / sort_i32 / midranks_f32 / inclusive_scan / moments / f1max are the launchers of the
+downstream-metric entry points (csrc/metrics.hip): they size and allocate the workspace, and hand back device tensors (fp64 results as views of byte buffers).
 """
 import ctypes
 import os
@@ -39,9 +40,10 @@ _RETURNS = {"int": c_int, "size_t": c_size_t, "int64_t": c_int64, "void": None}
 # Element type of a pointer argument: f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a flag argument / epilogue id.
 # A typed pointer says it itself and a void* is bf16 storage (the header's convention).  The void* that are not bf16 are named here, and nowhere else:
 _PTR_LETTER = {"float": "f", "int64_t": "l", "int": "i", "void": "h"}
-_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes"}                          # by parameter name, in every entry point
+_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes", "moments_bytes", "f1_bytes"}      # by parameter name, in every entry point (fp64 results travel as bytes)
 _FLAG_TYPED_PTRS = {("oneprot_gemm_bf16_nt", "out0"), ("oneprot_gemm_bf16_nt", "out1"), ("oneprot_gemm_bf16_nt", "aux"),
-                    ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x")}
+                    ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x"),
+                    ("oneprot_inclusive_scan", "x"), ("oneprot_inclusive_scan", "y"), ("oneprot_moments", "a"), ("oneprot_moments", "b"), ("oneprot_f1max", "target")}
 
 
 def _parse_header(text, where=HEADER_PATH):
@@ -93,6 +95,7 @@ def _load_header():
 # before the launch.
 _SIGS, _PTR_DTYPES, _consts = _load_header()
 MSA_MAX_LEN, MSA_MAX_ROWS = _consts["MSA_MAX_LEN"], _consts["MSA_MAX_ROWS"]
+SORT_TILE, SCAN_TILE = _consts["SORT_TILE"], _consts["SCAN_TILE"]      # keys per work-group of a radix pass / elements per chunk of the scan tree (csrc/metrics.hip)
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 
 _lib = None
@@ -216,6 +219,77 @@ def layernorm_fwd(x, gamma, beta, T, d, eps, *, y16=None, y32=None, mean=None, r
 def layernorm_bwd(dy, dy_mode, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, T, d, *, wrow=None, L=0, x_is_bf16=0, add_to=None, dx16=None, accumulate=0):
     """dy_mode 0: dy bf16 [T,d]; 1: fp32 [T,d]; 2: dy[t] = dy[t // L] * wrow[t].  dx = (add_to or 0) + LN'(dy), dx16 its optional bf16 copy."""
     call("oneprot_layernorm_bwd", dy, dy_mode, wrow, L, x, x_is_bf16, gamma, mean, rstd, add_to, dx, dx16, dgamma, dbeta, ws, T, d, accumulate)
+
+
+def _workspace(query_name, like, *shape):
+    nbytes = query(query_name, *shape)
+    if nbytes == 0:
+        raise HipKernelError(f"{query_name}{shape} returned 0: invalid size")
+    return torch.empty(nbytes, dtype=torch.uint8, device=like.device)
+
+
+# The downstream-metric entry points (csrc/metrics.hip).  Each allocates the workspace its query asks for on the tensor's device and returns device tensors;
+# fp64 results come back as float64 views of the byte buffers the entry points write.
+def sort_f32(keys, *, descending=False, want_keys=False):
+    """(perm int32 [n], sorted keys fp32 [n] or None): the stable argsort of a flat fp32 device tensor; equal keys in ascending index in both directions"""
+    n = keys.numel()
+    perm = torch.empty(n, dtype=torch.int32, device=keys.device)
+    out = torch.empty(n, dtype=torch.float32, device=keys.device) if want_keys else None
+    ws = _workspace("oneprot_sort_workspace", keys, n)
+    call("oneprot_sort_f32", keys, n, int(bool(descending)), perm, out, ws, ws.numel())
+    return perm, out
+
+
+def sort_i32(keys, key_bits, *, values=None, want_keys=True):
+    """(sorted keys int32 [n] or None, values int32 [n]): the stable sort of int32 keys in [0, 2^key_bits); values None sorts 0 .. n-1 along (an argsort)"""
+    n = keys.numel()
+    vout = torch.empty(n, dtype=torch.int32, device=keys.device)
+    kout = torch.empty(n, dtype=torch.int32, device=keys.device) if want_keys else None
+    ws = _workspace("oneprot_sort_workspace", keys, n)
+    call("oneprot_sort_i32", keys, values, n, int(key_bits), kout, vout, ws, ws.numel())
+    return kout, vout
+
+
+def midranks_f32(x):
+    """rank2 int32 [n]: twice the average 1-based rank of every element of a flat fp32 device tensor"""
+    n = x.numel()
+    rank2 = torch.empty(n, dtype=torch.int32, device=x.device)
+    ws = _workspace("oneprot_midranks_workspace", x, n)
+    call("oneprot_midranks_f32", x, n, rank2, ws, ws.numel())
+    return rank2
+
+
+def inclusive_scan(x, *, seg_len=0):
+    """the ordered inclusive scan of a flat int32 or float64 device tensor, restarting at every multiple of seg_len (0: one flat scan)"""
+    if x.dtype not in (torch.int32, torch.float64):
+        raise HipKernelError(f"oneprot_inclusive_scan: dtype {x.dtype}; the entry point takes int32 or float64")
+    n = x.numel()
+    y = torch.empty_like(x)
+    ws = _workspace("oneprot_scan_workspace", x, n)
+    call("oneprot_inclusive_scan", x, y, n, int(seg_len), int(x.dtype == torch.float64), ws, ws.numel())
+    return y
+
+
+def moments(a, b, *, shift_a=0.0, shift_b=0.0):
+    """float64 [8] on the device: n, sum a', sum b', sum a'^2, sum b'^2, sum a'b', sum (a'-b')^2, #(a == b) of two fp32 or two int32 streams, a' = a - shift_a"""
+    if a.dtype != b.dtype or a.dtype not in (torch.int32, torch.float32) or a.numel() != b.numel():
+        raise HipKernelError(f"oneprot_moments: streams of {a.dtype} [{a.numel()}] and {b.dtype} [{b.numel()}]; two fp32 or two int32 streams of one length are taken")
+    n = a.numel()
+    out = torch.empty(64, dtype=torch.uint8, device=a.device)
+    ws = _workspace("oneprot_moments_workspace", a, n)
+    call("oneprot_moments", a, b, n, int(a.dtype == torch.int32), float(shift_a), float(shift_b), out, ws, ws.numel())
+    return out.view(torch.float64)
+
+
+def f1max(pred, target):
+    """float64 [2] on the device: (F1-max, the score at which it is reached) of pred fp32 [B, N] and target int32 or fp32 [B, N]"""
+    if target.dtype not in (torch.int32, torch.float32) or target.shape != pred.shape or pred.dim() != 2:
+        raise HipKernelError(f"oneprot_f1max: pred {tuple(pred.shape)}, target {target.dtype} {tuple(target.shape)}; fp32 [B, N] and int32 or fp32 [B, N] are taken")
+    B, N = pred.shape
+    out = torch.empty(16, dtype=torch.uint8, device=pred.device)
+    ws = _workspace("oneprot_f1max_workspace", pred, B, N)
+    call("oneprot_f1max", pred, target, int(target.dtype == torch.float32), B, N, out, ws, ws.numel())
+    return out.view(torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
