@@ -562,6 +562,49 @@ int oneprot_moments(const void* a, const void* b, int64_t n, int is_i32, float s
 size_t oneprot_f1max_workspace(int B, int N);
 int oneprot_f1max(const float* pred, const void* target, int target_is_f32, int B, int N, void* f1_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------- downstream MLP probe (ref src/saprot_fit_mlp.py: the MLP of :63-115, the losses of :163-169, AdamW of :205-207) ------------------------------
+ * "Few rows" fp32 kernels (csrc/probe.hip): a batch is 32 or 64 rows, so a work-group owns every row of a column tile and finishes the layer in its epilogue;
+ * a training step of an MLP with H hidden layers is at most 5 H + 8 launches (5 H + 10 with the residual projection) and nothing is read back.  All of it fp32
+ * fmaf chains, no float atomics, every sum in a fixed order: two runs give the same bits.  norm: 0 none, 1 BatchNorm1d train mode, 2 BatchNorm1d eval mode;
+ * act: 0 identity, 1 ReLU, 2 erf-GELU, 3 LeakyReLU(0.01).  Dropout is the element rule of oneprot_dropout_f32 over the flat [M, n] index for (seed,
+ * stream_id): the fused epilogues and that kernel draw the same mask, and the backward regenerates it.  idx (optional) int32 [M]: row m of the operand is row
+ * idx[m] of a resident [N, k] matrix, so a shuffled batch is never materialised. */
+#define ONEPROT_PROBE_MAX_BATCH 256      /* rows of a BatchNorm (train mode) batch: one work-group holds a column's whole batch */
+/* Replaces nn.Linear -> [nn.BatchNorm1d] -> activation -> [nn.Dropout] (ref saprot_fit_mlp.py:74-92,107-108) and the residual sum (:110-113):
+   z[M, n] = gather(x, idx)[M, k] w[n, k]^T + b (written when z is given: the backward needs the pre-norm values), y = dropout(act(norm(z))) (+ resid[M, n], or
+   rows resid_idx[m] of resid when resid_idx is given) when y is given.  Any M, n, k >= 1; norm 1 needs 2 <= M <= ONEPROT_PROBE_MAX_BATCH, computes the two-pass mean
+   and biased variance (eps 1e-5), writes mean / rstd [n] and updates running_mean / running_var (momentum 0.1, unbiased variance) as nn.BatchNorm1d does;
+   norm 2 reads running_mean / running_var. */
+int oneprot_probe_linear_fwd(const float* x, const int* idx, const float* w, const float* b, float* z, float* y, const float* resid, const int* resid_idx,
+                             const float* gamma, const float* beta, float* mean, float* rstd, float* running_mean, float* running_var, int M, int n, int k,
+                             int norm, int act, float p, uint64_t seed, uint64_t stream_id, void* stream);
+/* Replaces nn.LayerNorm -> activation -> [nn.Dropout] (ref saprot_fit_mlp.py:79-90 with use_layer_norm): y = dropout(act(LN(z))) (+ resid, rows
+   resid_idx[m] when given) over the rows of z[M, n], eps 1e-5; mean / rstd [M] (optional) for the backward. */
+int oneprot_probe_rownorm_act_fwd(const float* z, const float* gamma, const float* beta, float* y, const float* resid, const int* resid_idx, float* mean,
+                                  float* rstd, int M, int n, int act, float p, uint64_t seed, uint64_t stream_id, void* stream);
+/* autograd's backward of the two above: dz[M, n] from dy, with the mask regenerated, act' applied and the norm's backward; dgamma / dbeta [n] (optional) are the
+   column sums of u xhat and u, u = dL/d norm(z).  norm_act_bwd: mean / rstd are the forward's [n] for norm 1, running_mean / running_VAR for norm 2. */
+int oneprot_probe_norm_act_bwd(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd, float* dz,
+                               float* dgamma, float* dbeta, int M, int n, int norm, int act, float p, uint64_t seed, uint64_t stream_id, void* stream);
+int oneprot_probe_rownorm_act_bwd(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd, float* dz,
+                                  float* dgamma, float* dbeta, int M, int n, int act, float p, uint64_t seed, uint64_t stream_id, void* stream);
+/* autograd's backward of nn.Linear (ref saprot_fit_mlp.py:75,95,99): dw[n, k] = dz[M, n]^T gather(x, idx)[M, k] and db[n] (optional) = column sums of dz,
+   written (not accumulated) wherever dw / db point -- the flat gradient arena; da[M, k] = dz[M, n] w[n, k]. */
+int oneprot_probe_linear_bwd_w(const float* dz, const float* x, const int* idx, float* dw, float* db, int M, int n, int k, void* stream);
+int oneprot_probe_linear_bwd_x(const float* dz, const float* w, float* da, int M, int n, int k, void* stream);
+/* Replaces the loss of ref saprot_fit_mlp.py:163-169,184,197 and its backward.  logits [M, C]; kind 0 F.binary_cross_entropy_with_logits (mean over M C, the
+   stable form max(x, 0) - x y + log1p(exp(-|x|))), 1 F.mse_loss (mean), both with target fp32 [., C]; 2 F.cross_entropy with labels int64 [.] (mean over M, row
+   log-sum-exp; a label outside [0, C) turns the loss NaN).  Row m's target is row idx[m] when idx is given.  dlogits (optional) carries the mean's scaling.
+   loss_bytes: one double, loss_sum += weight x mean loss, summed in fp64 through per-work-group partials and one ordered finish: a validation pass adds its
+   slabs up (weight = rows) without a readback.  workspace: oneprot_probe_loss_workspace() bytes. */
+size_t oneprot_probe_loss_workspace(void);
+int oneprot_probe_loss_fwd_bwd(const float* logits, const float* target, const int64_t* labels, const int* idx, float* dlogits, void* loss_bytes,
+                               void* workspace, int M, int C, int kind, float weight, void* stream);
+/* torch.optim.AdamW on a flat arena (ref saprot_fit_mlp.py:205-207): p <- p (1 - lr weight_decay), then the Adam update.  Any n; step >= 1.  The betas are
+   handed over as 1 - beta (0.1, 0.001), which fp32 holds to 5e-8 where 1 - (float)0.999 is off by 1.3e-5.  (oneprot_adam_step's decay is the L2 form.) */
+int oneprot_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float one_minus_beta1, float one_minus_beta2, float eps,
+                       float weight_decay, int step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

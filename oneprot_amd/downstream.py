@@ -16,6 +16,7 @@ current device: a deliberate difference from retrieval.py, which refuses host te
 arrays.  Scores are computed on their fp32 values.  A missing library raises hip.HipLibraryMissing; there is no host fallback.  Shape mismatches, empty
 inputs, more than two dimensions, more than 2^31 - 1 elements and (for host data) targets outside {0, 1} raise ValueError before the device is touched."""
 import math
+import os
 
 import numpy as np
 import torch
@@ -205,4 +206,24 @@ def evaluate_predictions(task_name, y_pred, y_true, partition):
     else:
         known = BINARY_TASKS + MULTILABEL_TASKS + REGRESSION_TASKS + MULTICLASS_TASKS
         raise ValueError(f"evaluate_predictions: unknown task {task_name!r}; the reference's tasks are {', '.join(known)}")
+    return out
+
+
+def load_data(cfg):
+    """ref src/utils/downstream.py:121-147: for every partition of cfg["evaluate_on"] the file
+    <emb_dir>/<model_type>/<task_name>/<partition>/<task_name>_<partition>_embeddings_labels.pt with `embeddings` and `labels_fitness`, as host numpy arrays under
+    "<partition>_emb" / "<partition>_target"; a finite cfg["threshold"] binarises the EMBEDDINGS (> threshold -> 1.0, else 0.0), as the reference does.  A
+    missing file raises FileNotFoundError (the reference goes on with the previous partition's arrays, or a NameError for the first)."""
+    out = {}
+    task, model_type = cfg["task_name"], cfg["model_type"]
+    for partition in cfg["evaluate_on"]:
+        path = os.path.join(cfg["emb_dir"], f"{model_type}/{task}/{partition}/{task}_{partition}_embeddings_labels.pt")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"load_data: {path} not found")
+        both = torch.load(path, map_location="cpu", weights_only=True)
+        emb, target = both["embeddings"], both["labels_fitness"]
+        if not math.isinf(float(cfg["threshold"])):
+            emb = torch.where(emb > float(cfg["threshold"]), torch.tensor(1.0), torch.tensor(0.0))
+        out[f"{partition}_emb"] = emb.cpu().numpy()
+        out[f"{partition}_target"] = target.cpu().numpy()
     return out

@@ -8,6 +8,8 @@ parsed from it at import, so a new entry point is declared there, defined in csr
 (_BYTE_PTRS / _FLAG_TYPED_PTRS).  call(name, *positional) launches any entry point; gemm_nt / gemm_tn / layernorm_fwd / layernorm_bwd are keyword
 launchers of the four widest ones and end in the same call().  sort_f32 / sort_i32 / midranks_f32 / inclusive_scan / moments / f1max are the launchers of the
 downstream-metric entry points (csrc/metrics.hip): they size and allocate the workspace, and hand back device tensors (fp64 results as views of byte buffers).
+probe_linear_fwd / probe_rownorm_act_fwd / probe_norm_act_bwd / probe_rownorm_act_bwd / probe_loss are the keyword launchers of the MLP probe's wide entry points
+(csrc/probe.hip).
 """
 import ctypes
 import os
@@ -40,7 +42,7 @@ _RETURNS = {"int": c_int, "size_t": c_size_t, "int64_t": c_int64, "void": None}
 # Element type of a pointer argument: f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a flag argument / epilogue id.
 # A typed pointer says it itself and a void* is bf16 storage (the header's convention).  The void* that are not bf16 are named here, and nowhere else:
 _PTR_LETTER = {"float": "f", "int64_t": "l", "int": "i", "void": "h"}
-_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes", "moments_bytes", "f1_bytes"}      # by parameter name, in every entry point (fp64 results travel as bytes)
+_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes", "moments_bytes", "f1_bytes", "loss_bytes"}      # by parameter name, in every entry point (fp64 results travel as bytes)
 _FLAG_TYPED_PTRS = {("oneprot_gemm_bf16_nt", "out0"), ("oneprot_gemm_bf16_nt", "out1"), ("oneprot_gemm_bf16_nt", "aux"),
                     ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x"),
                     ("oneprot_inclusive_scan", "x"), ("oneprot_inclusive_scan", "y"), ("oneprot_moments", "a"), ("oneprot_moments", "b"), ("oneprot_f1max", "target")}
@@ -96,6 +98,7 @@ def _load_header():
 _SIGS, _PTR_DTYPES, _consts = _load_header()
 MSA_MAX_LEN, MSA_MAX_ROWS = _consts["MSA_MAX_LEN"], _consts["MSA_MAX_ROWS"]
 SORT_TILE, SCAN_TILE = _consts["SORT_TILE"], _consts["SCAN_TILE"]      # keys per work-group of a radix pass / elements per chunk of the scan tree (csrc/metrics.hip)
+PROBE_MAX_BATCH = _consts["PROBE_MAX_BATCH"]                            # rows of a BatchNorm (train mode) batch of the MLP probe (csrc/probe.hip)
 _DT = {"f": torch.float32, "h": torch.bfloat16, "l": torch.int64, "i": torch.int32, "b": torch.uint8}
 
 _lib = None
@@ -290,6 +293,47 @@ def f1max(pred, target):
     ws = _workspace("oneprot_f1max_workspace", pred, B, N)
     call("oneprot_f1max", pred, target, int(target.dtype == torch.float32), B, N, out, ws, ws.numel())
     return out.view(torch.float64)
+
+
+# The MLP probe (csrc/probe.hip).  norm / act ids as include/oneprot_hip.h numbers them; rng = (p, seed, stream_id) of the dropout, None for no dropout.
+PROBE_NORM_NONE, PROBE_NORM_BN_TRAIN, PROBE_NORM_BN_EVAL = range(3)
+PROBE_ACT = {"identity": 0, "relu": 1, "gelu": 2, "leaky_relu": 3}
+PROBE_LOSS_BCE, PROBE_LOSS_MSE, PROBE_LOSS_CE = range(3)
+
+
+def _rng3(rng):
+    p, seed, stream_id = rng if rng is not None else (0.0, 0, 0)
+    return float(p), int(seed), int(stream_id)
+
+
+def probe_linear_fwd(x, w, b, M, n, k, *, idx=None, z=None, y=None, resid=None, resid_idx=None, norm=0, act=0, gamma=None, beta=None, mean=None, rstd=None,
+                     running_mean=None, running_var=None, rng=None):
+    """z = gather(x, idx) w^T + b (pre-norm, optional), y = dropout(act(norm(z))) (+ resid) (optional)"""
+    call("oneprot_probe_linear_fwd", x, idx, w, b, z, y, resid, resid_idx, gamma, beta, mean, rstd, running_mean, running_var, M, n, k, int(norm), int(act),
+         *_rng3(rng))
+
+
+def probe_rownorm_act_fwd(z, gamma, beta, y, M, n, *, act=0, resid=None, resid_idx=None, mean=None, rstd=None, rng=None):
+    """y = dropout(act(LayerNorm(z))) (+ resid)"""
+    call("oneprot_probe_rownorm_act_fwd", z, gamma, beta, y, resid, resid_idx, mean, rstd, M, n, int(act), *_rng3(rng))
+
+
+def probe_norm_act_bwd(dy, z, dz, M, n, *, norm=0, act=0, gamma=None, beta=None, mean=None, rstd=None, dgamma=None, dbeta=None, rng=None):
+    """dz of y = dropout(act(norm(z))); norm 2 takes the running mean and the running variance as mean / rstd"""
+    call("oneprot_probe_norm_act_bwd", dy, z, gamma, beta, mean, rstd, dz, dgamma, dbeta, M, n, int(norm), int(act), *_rng3(rng))
+
+
+def probe_rownorm_act_bwd(dy, z, gamma, beta, mean, rstd, dz, M, n, *, act=0, dgamma=None, dbeta=None, rng=None):
+    call("oneprot_probe_rownorm_act_bwd", dy, z, gamma, beta, mean, rstd, dz, dgamma, dbeta, M, n, int(act), *_rng3(rng))
+
+
+def probe_loss(logits, M, C, kind, loss_sum, ws, *, target=None, labels=None, idx=None, dlogits=None, weight=1.0):
+    """loss_sum (a float64 [1] device tensor) += weight x mean loss; dlogits (optional) = its gradient.  ws from probe_loss_workspace()."""
+    call("oneprot_probe_loss_fwd_bwd", logits, target, labels, idx, dlogits, loss_sum.view(torch.uint8), ws, M, C, int(kind), float(weight))
+
+
+def probe_loss_workspace(device):
+    return torch.empty(query("oneprot_probe_loss_workspace"), dtype=torch.uint8, device=device)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -58,6 +58,36 @@ class FusedAdam(torch.optim.Optimizer):
         return loss
 
 
+class FusedAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW's hyper-parameters and arithmetic (decoupled decay p <- p (1 - lr wd), then the Adam update; ref src/saprot_fit_mlp.py:205-207), one
+    `oneprot_adamw_step` launch per parameter tensor of any size.  The MLP probe's parameters are views of one flat tensor (probe.MLP.arena()), so its step is
+    ONE launch.  `lr` is read from the group at every step, so a scheduler only has to write it there."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise hip.HipKernelError("FusedAdamW needs parameters on the GPU (no CPU fallback)")
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["step"] += 1
+                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                hip.call("oneprot_adamw_step", p.data, g, st["exp_avg"], st["exp_avg_sq"], p.numel(), group["lr"], 1.0 - b1, 1.0 - b2, group["eps"], group["weight_decay"], st["step"])
+                _bump_version(p)
+        return loss
+
+
 @torch.no_grad()
 def clip_grad_norm_(parameters, max_norm, optimizer=None):
     """Global L2 norm over all .grad tensors (torch.nn.utils.clip_grad_norm_ semantics: coef = min(1, max/(norm+1e-6))).
