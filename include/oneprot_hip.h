@@ -517,6 +517,12 @@ int oneprot_pronet_act_bwd(const float* dy, const float* z, float* dz, int64_t M
    workspace: oneprot_colsum_f32_workspace(M, n) bytes (0 for a bad shape). */
 size_t oneprot_colsum_f32_workspace(int64_t M, int n);
 int oneprot_colsum_f32(const float* x, float* out, void* workspace, size_t workspace_bytes, int64_t M, int n, void* stream);
+/* dW[n, k] = sum_r dz[r, n] x[r, k] of fp32 dz [M, n] and x [M, k] (autograd's weight gradient `dz.t() @ x` with M = every node of the batch), blocked like
+   the column sum: chains of at most 128 rows (M / 256 beyond 32 768 rows) in parallel, then eight accumulators and a tree over the row blocks -- where
+   oneprot_sgemm(transA = 1, b_is_kn = 1) runs one chain of M terms.  M <= 2^26, n and k <= 4096.  workspace: oneprot_wgrad_f32_workspace(M, n, k) bytes
+   (0 for a bad shape). */
+size_t oneprot_wgrad_f32_workspace(int64_t M, int n, int k);
+int oneprot_wgrad_f32(const float* dz, const float* x, float* dW, void* workspace, size_t workspace_bytes, int64_t M, int n, int k, void* stream);
 /* Replaces `x + torch.clip(torch.empty_like(x).normal_(0, sigma), -clip, clip)` (ProNet's data_augment_eachlayer): element e takes normal e & 3 of
    Philox4x32-10(counter = e >> 2, stream_id; key = seed), Box-Muller as above.  n a multiple of 4; y may alias x.  Its backward is the identity. */
 int oneprot_clipped_normal_add_f32(const float* x, float* y, int64_t n, float sigma, float clip, uint64_t seed, uint64_t stream_id, void* stream);

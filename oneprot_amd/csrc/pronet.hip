@@ -474,3 +474,68 @@ extern "C" int oneprot_colsum_f32(const float* x, float* out, void* workspace, s
   hipLaunchKernelGGL(k_pronet_colsum_final, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, out, nb, n);
   return launch_status();
 }
+
+// ---- weight gradients of the node linears ---------------------------------------------------------------------------------------------------------------
+// dW[n, k] = sum_r dz[r, n] x[r, k] (autograd's `dz.t() @ x`), the contraction running over M = every node of the batch.  oneprot_sgemm makes that ONE
+// fmaf chain of M terms per element in (n / 64) (k / 64) work-groups: at M = 8193 its rounding is 6 to 36 times that of a blocked fp32 sum, and four
+// work-groups walk 8193 rows each.  Here a work-group owns a 64 x 64 tile of dW and `per` rows (128, or M / 256 for more than 32 768 rows), four
+// outputs a side per thread as in sgemm.hip, and writes slab part[b]; the slabs are summed by k_pronet_colsum_final (eight accumulators and a tree).
+// Rows behind the slab are staged as zeros: fmaf(0, 0, acc) is exact.  A fixed order throughout: two runs give the same bits.
+#define PN_WG_BK 32
+__global__ void __launch_bounds__(256) k_pronet_wgrad(const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ part, int M, int n, int k,
+                                                      int per) {
+  __shared__ float sA[PN_WG_BK][64 + 4];
+  __shared__ float sB[PN_WG_BK][64 + 4];
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64, tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int r0 = blockIdx.z * per, r1 = min(M, r0 + per);
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  for (int rb = r0; rb < r1; rb += PN_WG_BK) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < PN_WG_BK * 64 / 256; ++it) {
+      const int idx = tid + it * 256, kk = idx >> 6, cc = idx & 63, r = rb + kk;
+      sA[kk][cc] = (r < r1 && m0 + cc < n) ? dz[(size_t)r * n + m0 + cc] : 0.f;
+      sB[kk][cc] = (r < r1 && n0 + cc < k) ? x[(size_t)r * k + n0 + cc] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int kk = 0; kk < PN_WG_BK; ++kk) {
+      float a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = sA[kk][ty * 4 + i]; b[i] = sB[kk][tx * 4 + i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int gm = m0 + ty * 4 + i;
+    if (gm >= n) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gn = n0 + tx * 4 + j;
+      if (gn < k) part[((size_t)blockIdx.z * n + gm) * k + gn] = acc[i][j];
+    }
+  }
+}
+static inline bool pn_wgrad_shape_ok(int64_t M, int n, int k) { return M > 0 && M <= ((int64_t)1 << 26) && n > 0 && n <= 4096 && k > 0 && k <= 4096; }
+static inline int pn_wgrad_rows(int64_t M) { const int q = (int)(((M + 255) / 256 + 63) / 64 * 64); return q > 128 ? q : 128; }
+extern "C" size_t oneprot_wgrad_f32_workspace(int64_t M, int n, int k) {
+  if (!pn_wgrad_shape_ok(M, n, k)) return 0;
+  const int per = pn_wgrad_rows(M);
+  return (size_t)((M + per - 1) / per) * n * k * sizeof(float);
+}
+extern "C" int oneprot_wgrad_f32(const float* dz, const float* x, float* dW, void* workspace, size_t workspace_bytes, int64_t M, int n, int k, void* stream) {
+  const size_t need = oneprot_wgrad_f32_workspace(M, n, k);
+  if (!dz || !x || !dW || !workspace || !need || workspace_bytes < need || ((uintptr_t)workspace & 3)) return OP_EINVAL;
+  const int per = pn_wgrad_rows(M), nb = (int)((M + per - 1) / per);
+  hipLaunchKernelGGL(k_pronet_wgrad, dim3((k + 63) / 64, (n + 63) / 64, nb), dim3(256), 0, (hipStream_t)stream, dz, x, (float*)workspace, (int)M, n, k, per);
+  hipLaunchKernelGGL(k_pronet_colsum_final, dim3((n * k + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dW, nb, n * k);
+  return launch_status();
+}

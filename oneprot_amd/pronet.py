@@ -9,7 +9,7 @@ via Complete 3D Graph Networks", ICLR 2023) restated, and tests/pronet_ref.py --
 `ProNet(...)(batch) -> fp32 [num_graphs, out_channels]`; `batch` is an oneprot_amd.graph_data.GraphBatch or anything with the attribute names of the PyG
 Batch the reference builds (x, coords_ca, coords_n, coords_c, bb_embs, batch, num_graphs).  It is a torch.nn.Module with plain fp32 parameters under
 the published module names; the arithmetic of a call is ONE torch.autograd.Function whose forward records a tape of kernel launches and whose backward
-replays it in reverse: node linears on oneprot_sgemm, everything per edge in the fused convolution kernels, which never write the [E, h] edge weights
+replays it in reverse: node linears on oneprot_sgemm (their weight gradients, which contract over the nodes, on oneprot_wgrad_f32), everything per edge in the fused convolution kernels, which never write the [E, h] edge weights
 or messages.  No float atomics and no host read-back: a step is a pure function of (inputs, parameters, RNG position).
 
 Train-mode noise and dropout (module in train mode only) draw from the library's Philox streams under RNG domain 4; `rng_state()` / `set_rng_state()`
@@ -146,6 +146,13 @@ def _sgemm(A, B, C, M, N, K, transA, b_is_kn, accumulate=0):
     hip.call("oneprot_sgemm", A, B, C, M, N, K, transA, b_is_kn, 1.0, accumulate)
 
 
+def _wgrad(dz, x, dW):
+    """dW = dz^T x over every row of the batch, blocked over the rows: one sgemm chain of N terms rounds 6 to 36 times worse at N = 8193"""
+    M, n, k = dz.shape[0], dz.shape[1], x.shape[1]
+    ws = torch.empty(hip.query("oneprot_wgrad_f32_workspace", M, n, k), dtype=torch.uint8, device=dz.device)
+    hip.call("oneprot_wgrad_f32", dz, x, dW, ws, ws.numel(), M, n, k)
+
+
 def _linear(tape, pairs, bias, act, resid=None, into=None, needs_dx=True):
     """y = act(sum_k x_k W_k^T + bias) (+ resid).  pairs: [(x [M, K], W parameter [n, K])]; into = (buffer [M, ld], column offset): y is that column
     block (torch.cat by placement).  Returns y, or the buffer."""
@@ -179,7 +186,7 @@ def _linear(tape, pairs, bias, act, resid=None, into=None, needs_dx=True):
             for x, W in pairs:
                 K = x.shape[1]
                 dW = torch.empty_like(W)
-                _sgemm(dz, x, dW, n, K, M, 1, 1)                              # dW = dz^T x
+                _wgrad(dz, x, dW)                                             # dW = dz^T x
                 tape.pgrads[W] = dW
                 if needs_dx:
                     dx = torch.empty_like(x)
@@ -350,7 +357,7 @@ class ProNet(nn.Module):
             def embed_bwd():
                 g = tape.grads.pop(id(x0))
                 dW, db = torch.empty_like(emb.weight), torch.empty_like(emb.bias)
-                _sgemm(g, feat32, dW, h, 32, N, 1, 1)
+                _wgrad(g, feat32, dW)
                 _colsum(g, db)
                 tape.pgrads[emb.weight], tape.pgrads[emb.bias] = dW, db
             tape.ops.append(embed_bwd)

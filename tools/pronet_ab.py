@@ -27,7 +27,7 @@ from tests import pronet_ref as R                                               
 
 DEV = "cuda:0"
 ENTRY_POINTS = ["oneprot_radius_graph", "oneprot_graph_by_source", "oneprot_pronet_edge_features", "oneprot_edge_conv_fwd", "oneprot_edge_conv_bwd_x",
-                "oneprot_edge_conv_bwd_w", "oneprot_sgemm", "oneprot_pronet_bias_act", "oneprot_pronet_act_bwd", "oneprot_colsum_f32",
+                "oneprot_edge_conv_bwd_w", "oneprot_sgemm", "oneprot_wgrad_f32", "oneprot_pronet_bias_act", "oneprot_pronet_act_bwd", "oneprot_colsum_f32",
                 "oneprot_dropout_add_f32", "oneprot_pronet_embed_fwd", "oneprot_segment_sum_f32", "oneprot_segment_sum_bwd_f32"]
 
 
