@@ -611,6 +611,51 @@ int oneprot_probe_loss_fwd_bwd(const float* logits, const float* target, const i
 int oneprot_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float one_minus_beta1, float one_minus_beta2, float eps,
                        float weight_decay, int step, void* stream);
 
+/* ---------------- gradient-boosted tree probes (ref src/saprot_fit_cls.py:32-38 and src/saprot_fit_reg.py:26-32: xgboost.XGBClassifier / XGBRegressor .fit /
+ * .predict; ref configs/downstream_model/xgboost_cls.yaml, xgboost_reg.yaml: tree_method gpu_hist) ---------------------------------------------------------
+ * The `hist` tree builder on fixed-point histograms (csrc/gbt.hip).  X fp32 [N, F], 1 <= N <= 2^24, 1 <= F <= 65535, 2 <= max_bin <= 256, finite.  Gradients
+ * are quantised to integers q = rint(x 2^(20 - e)) before any sum (e = 0, except for the g of reg:squarederror: the smallest e with max |g| < 2^e over the kept
+ * rows, at least -100, 0 when every g is 0), histograms are int32 in LDS and int64 in global memory: integer sums, the same bits in every run and for every
+ * work decomposition.  No float atomics, no work-group waits on another, nothing is read back.  Trees are heap-numbered (root 0, children 2 n + 1, 2 n + 2)
+ * arrays of tree_nodes = 2^(max_depth + 1) - 1 entries per (round, output): tree_feat (-1: leaf), tree_bin (cut index), tree_thr (cut value), tree_leaf
+ * ((float)(learning_rate w)).  Byte masks row_keep [N], feat_keep [F] are 0 / 1; bins is uint8 [N, F].  The float parameters are used as doubles. */
+/* cuts [F, max_bin - 1] (unused slots +inf) and ncuts [F] from grouped [F, N], every feature's column ascending: the distinct values among
+   v[floor(k N / max_bin)], k = 1 .. max_bin - 1, with -0.0 read as +0.0.  bins[i, f] = the number of cuts <= X[i, f], so bin <= j iff x < cut[j]. */
+int oneprot_gbt_cuts(const float* grouped, int64_t N, int F, int max_bin, float* cuts, int* ncuts, void* stream);
+int oneprot_gbt_bin(const float* X, const float* cuts, const int* ncuts, void* bins, int64_t N, int F, int max_bin, void* stream);
+/* One round's masks (xgboost's subsample / colsample_bytree).  The uniform of element e is the 16-bit slice of oneprot_dropout_f32's element rule, over 65536.
+   Row i is kept iff uniform(seed, row_stream, i) < subsample (subsample >= 1 keeps all, drawing nothing); the n_keep features with the smallest
+   uniform(seed, feat_stream, f) are kept, equal uniforms to the lower index (n_keep = F keeps all, drawing nothing).  feat_uniform: int32 [F] scratch. */
+int oneprot_gbt_sample(void* row_keep, void* feat_keep, int* feat_uniform, int64_t N, int F, float subsample, int n_keep, uint64_t seed, uint64_t row_stream,
+                       uint64_t feat_stream, void* stream);
+/* gq / hq int32 [K, N] and expo int32 [K] from margin fp32 [N, K], in fp32.  objective 0 binary:logistic (target fp32 [N, K]: p = 1 / (1 + exp(-m)), g = p - y,
+   h = p (1 - p)), 1 reg:squarederror (K = 1, target fp32 [N]: g = m - y, h = 1), 2 multi:softmax (labels int32 [N]: p the row softmax, g_k = p_k - [y = k],
+   h_k = 2 p_k (1 - p_k)).  Rows with row_keep 0 get q = 0.  gmax_bits: one int32 of scratch (the order-free maximum of |g| as float bits). */
+int oneprot_gbt_grad(const float* margin, const float* target, const int* labels, const void* row_keep, int* gq, int* hq, int* expo, int* gmax_bits, int64_t N,
+                     int K, int objective, void* stream);
+/* hist int64 [kc, 2^level, F, max_bin, 2] (g, h), overwritten: the sums of gq / hq [kc, N] over the rows whose pos [kc, N] is node 2^level - 1 + n.
+   0 <= level <= 5.  oneprot_gbt_hist_bytes: the bytes of ONE output's histogram at this level (0 for invalid arguments). */
+size_t oneprot_gbt_hist_bytes(int F, int max_bin, int level);
+int oneprot_gbt_hist(const void* bins, const int* gq, const int* hq, const int* pos, int64_t* hist, int64_t N, int F, int max_bin, int level, int kc, void* stream);
+/* Per (output, node of the level): candidates (kept feature f, cut j < ncuts[f]), left = bins <= j; valid iff HL_int > 0, HR_int > 0, HL >= min_child_weight
+   and HR >= min_child_weight; T(G) = sign(G) max(|G| - reg_alpha, 0), score = T(G)^2 / (H + reg_lambda), gain = (score(L) + score(R)) - score(node) in fp64;
+   best = largest gain, then lowest f, then lowest j; the node splits iff a valid candidate exists and gain > max(gamma, 0).  Writes the node's entries and its
+   children's leaf values (0 under a node that does not split) into the tree arrays [kc, tree_nodes]; w = -T(G) / (H + reg_lambda), 0 when H + reg_lambda <= 0.
+   gain_bytes (optional): doubles [kc, tree_nodes], the best valid gain of the node, -inf without one.  Two launches: a wave per (output, node, feature) leaves
+   the feature's best cut in the workspace (oneprot_gbt_split_workspace bytes, 8-byte aligned), a work-group per (output, node) takes the ordered arg-max. */
+size_t oneprot_gbt_split_workspace(int F, int level, int kc);
+int oneprot_gbt_split(const int64_t* hist, const float* cuts, const int* ncuts, const void* feat_keep, const int* expo, int* tree_feat, int* tree_bin, float* tree_thr,
+                      float* tree_leaf, void* gain_bytes, void* workspace, size_t workspace_bytes, int F, int max_bin, int level, int kc, int tree_nodes,
+                      float min_child_weight, float gamma, float reg_alpha, float reg_lambda, float learning_rate, void* stream);
+/* pos [kc, N]: a row in a node of this level that split moves to child 2 p + 1 (bin <= tree_bin) or 2 p + 2; every other row stays */
+int oneprot_gbt_partition(const void* bins, const int* tree_feat, const int* tree_bin, int* pos, int64_t N, int F, int level, int kc, int tree_nodes, void* stream);
+/* margin[i, k0 + kk] += tree_leaf[kk, pos[kk, i]] for the kc outputs of a chunk: every row, kept or dropped (margin fp32 [N, K]) */
+int oneprot_gbt_update(float* margin, const int* pos, const float* tree_leaf, int64_t N, int K, int k0, int kc, int tree_nodes, void* stream);
+/* Replaces model.predict's margin: margin[i, k] = init_margin + the leaves of trees (t, k), t = 0 .. n_trees - 1 in order, one fp32 chain; raw X against
+   tree_thr, x < threshold goes left.  Tree arrays [n_trees, K, tree_nodes]. */
+int oneprot_gbt_predict(const float* X, const int* tree_feat, const float* tree_thr, const float* tree_leaf, float* margin, int64_t N, int F, int K, int n_trees,
+                        int tree_nodes, float init_margin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

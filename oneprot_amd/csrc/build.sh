@@ -4,7 +4,7 @@
 # instantiation carries scratch (a register spill), so that a spill regression cannot reach a bench run unnoticed.
 set -e
 cd "$(dirname "$0")"
-SRCS="rowops.hip gemm_nt.hip gemm_nt8.hip gemm_nt_ln.hip gemm_tn.hip sgemm.hip attention.hip featops.hip retrieval.hip msa.hip msa_select.hip pronet.hip metrics.hip probe.hip"
+SRCS="rowops.hip gemm_nt.hip gemm_nt8.hip gemm_nt_ln.hip gemm_tn.hip sgemm.hip attention.hip featops.hip retrieval.hip msa.hip msa_select.hip pronet.hip metrics.hip probe.hip gbt.hip"
 OBJS=""
 PIDS=""
 ASM=""       # units whose .s is already being written: the loop after this one must not start a second writer of the same .s.tmp

@@ -22,6 +22,7 @@ RULES = [
     (r"^(void )?k_msa_", 0),                           # MSA tower: embedding, tied row scores / context, column attention
     (r"^(void )?k_pronet_", 0),                        # ProNet tower: graph, edge features, fused edge convolution (48 weights or partials per thread in registers)
     (r"^(void )?k_metrics_", 0),                       # downstream metrics: radix sort passes, ordered scans and sums, F1-max
+    (r"^(void )?k_gbt_", 0),                           # gradient-boosted trees: cuts, bins, gradients, histograms, split search, partition, predict
 ]
 
 
