@@ -185,3 +185,83 @@ def test_header_declares_every_symbol_gbt_calls():
     assert hip._PTR_DTYPES["oneprot_gbt_grad"] == "ffibiiii"
     for section in ("saprot_fit_cls.py:32-38", "saprot_fit_reg.py:26-32", "xgboost_cls.yaml", "xgboost_reg.yaml"):
         assert section in header
+
+
+# ================================================================================================================== the fixtures and references of tests/test_gbt_edges_gpu.py
+@pytest.mark.parametrize("name", sorted(C.BIG_FIXTURES))
+def test_big_fixture_gaps(name):
+    """the 4500-row fixtures (three row chunks of the histogram kernel) under test_fixture_gaps' condition: every split decided by a relative gain gap of at
+    least 1e-4, every round splitting its root; and the largest margin stays below 2, which the GPU test's bound of one ulp in [1, 2) per round rests on"""
+    m = C.big_reference(name)
+    print(f"{name}: gap {m['gap']:.3e} (recorded {C.BIG_GAPS[name]:.3e}), max |margin| {np.abs(m['margin']).max():.3f}")
+    assert m["gap"] >= 1e-4
+    assert abs(m["gap"] - C.BIG_GAPS[name]) <= 0.01 * C.BIG_GAPS[name]
+    assert all(tr["feat"][0] >= 0 for rnd in m["trees"] for tr in rnd)
+    assert len(m["trees"]) == C.BIG_ROUNDS and len(m["trees"][0]) == {"softmax": 3, "multilabel": 5}.get(name, 1)
+    assert m["bins"].shape == (C.BIG_N, C.BIG_F) and C.BIG_N > 2 * 2047 and float(np.abs(m["margin"]).max()) < 2.0
+
+
+@pytest.mark.parametrize("name", sorted(C.FIXTURES))
+def test_vectorised_walk_equals_the_restatement_on_held_out_rows(name):
+    """tests/gbt_cases.py walk (level-synchronous, the reference of the GPU prediction tests) against gbt_ref.predict_margin (a loop per row) on 200 rows the
+    300-row fit has not seen: rows that sit on a cut, rows scaled by 3; bit for bit"""
+    ref, objective = C.reference(name), C.FIXTURES[name][0]
+    X = np.concatenate([C.heldout(name)[:100], C.heldout(name)[200:300]])
+    feat, thr, leaf = C.pack_trees(ref)
+    want = R.predict_margin(ref, X, objective)
+    got = C.walk(X, feat, thr, leaf, R.initial_margin(objective, 0.5))
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))
+    cuts = ref["cuts"]
+    assert sum(bool((X[i, f] == cuts[f]).any()) for i in range(20) for f in range(C.F)) >= 20       # the rows on a cut are there
+    assert np.abs(X[100:]).max() > np.abs(X[:100]).max()
+
+
+@pytest.mark.parametrize("index", range(len(C.PREDICT_CASES)))
+def test_predict_inputs_tell_the_wrong_walks_apart(index):
+    """on the X of every synthetic prediction case, a walk with <= in place of < and a walk that reads below a stopped node give other margins than the right
+    walk -- wherever the case has the rows to show it (a single row is not asked to show both)"""
+    depth, K, T, n_trees, F, n, init = C.PREDICT_CASES[index]
+    d = C.predict_case(index)
+    assert d["want"].shape == (n, K) and d["feat"].shape == (T, K, (2 << depth) - 1)
+    inner = (1 << depth) - 1
+    assert (d["feat"][0, 0, :inner] >= 0).all() and (d["feat"][..., inner:] == -1).all() and (d["leaf"] != 0).all() and (d["feat_full"] >= 0).all()
+    if n_trees == 0:
+        assert (d["want"] == np.float32(init)).all()
+        return
+    X = d["X"]
+    live = d["feat"][:n_trees] >= 0
+    assert np.isin(X, d["thr"][:n_trees][live]).any()
+    if n >= 255:
+        assert np.isposinf(X).any() and np.isneginf(X).any() and (X[np.signbit(X)] == 0).any() and np.abs(X).max() >= 3 * np.abs(d["thr"]).max()
+        le = C.walk(X, d["feat"], d["thr"], d["leaf"], init, n_trees, le=True)
+        assert (le != d["want"]).any()
+        if n_trees * K > 1:
+            through = C.walk(X, d["feat_full"], d["thr"], d["leaf"], init, n_trees)
+            assert (through != d["want"]).any()
+
+
+def test_predict_cases_cover_what_they_claim():
+    depth, K, T, n_trees, F, n, _ = (set(v) for v in zip(*C.PREDICT_CASES))
+    assert depth == {1, 3, 6} and K == {1, 3, 5} and {1, 7} <= T and 0 in n_trees and F == {1, 8, 1280} and n == {1, 255, 256, 257, 70001}
+    assert any(c[3] not in (0, c[2]) for c in C.PREDICT_CASES) and any(c[6] != 0.0 for c in C.PREDICT_CASES)
+
+
+@pytest.mark.parametrize("objective,K", C.GRAD_CASES)
+def test_gradient_bound_admits_the_fp32_restatement(objective, K):
+    """the bound of the GPU gradient test, 0.5 + 2^20 x 4 x E32 quanta around the fp64 value, holds for the restatement's own fp32 evaluation on every case, so
+    it can never fail a correct fp32 evaluation; and it stays a few quanta wide while a wrong formula is thousands of quanta away"""
+    worst = 0.0
+    for label, m, y, keep in C.grad_cases(objective, K):
+        g64, h64, e32, bound = C.grad_reference(m, y, objective)
+        g, h = R.gradients(m, y, objective)
+        for k in range(K):
+            gq, hq = R.quantise(g[:, k], h[:, k], keep, 0)
+            assert np.abs(gq[keep] - 2.0 ** R.FRAC * g64[keep, k]).max(initial=0.0) <= bound, label
+            assert np.abs(hq[keep] - 2.0 ** R.FRAC * h64[keep, k]).max(initial=0.0) <= bound, label
+            assert not gq[~keep].any() and not hq[~keep].any()
+        worst = max(worst, bound)
+        if objective == R.SOFTMAX and m.shape[0] >= 255 and "normal" in label:
+            assert np.abs(2.0 ** R.FRAC * h64 / 2.0).max() > 1000 * bound                     # what a missing factor 2 in h would be off by
+            assert {0, K - 1} <= set(y.tolist())
+    print(f"{objective} K {K}: widest bound {worst:.3f} quanta")
+    assert worst < 4.0
