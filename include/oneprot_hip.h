@@ -230,8 +230,11 @@ int oneprot_scale_by_device_scalar(float* x, int64_t n, const float* s, void* st
 /* bias[i] = ids[i]==pad ? -FLT_MAX : 0  (additive key-padding mask, hf masking_utils.create_bidirectional_mask) */
 int oneprot_key_padding_bias(const int64_t* ids, float* bias, int64_t n, int pad_id, void* stream);
 
-/* y = dropout(x) on a bf16 operand of n elements (n % 8 == 0), keep probability 1 - p, kept values scaled by the inverse keep probability; the mask
-   is a pure function of (seed, stream_id, element index) -- Philox4x32-10 -- and is never stored.  Replaces the `lora_dropout` module peft 0.5.0
+/* THE ELEMENT RULE of every Philox draw below (csrc/philox.h; host side and stream-id layout: oneprot_amd/rng.py): element e reads the 16-bit slice e & 7 --
+   the low (even) or high (odd) half of word (e & 7) >> 1 -- of Philox4x32-10(counter = (e >> 3, stream_id), key = seed).  A dropout keeps e iff that slice
+   >= thr = (unsigned)(p * 65536 + 0.5) in fp32 and scales kept values by 65536 / (65536 - thr); p < 0, NaN, p >= 1 and thr = 65536 are refused with OP_EINVAL.
+   y = dropout(x) on a bf16 operand of n elements (n % 8 == 0) under that rule; the mask
+   is a pure function of (seed, stream_id, element index) and is never stored.  Replaces the `lora_dropout` module peft 0.5.0
    applies to the adapter branch's input (ref src/models/components/sequence_encoder.py:61-74, text_encoder.py:39-52: LoraConfig(lora_dropout=...)).
    The generator is not torch's: same distribution, different stream. */
 int oneprot_dropout_bf16(const void* x, void* y, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream);
@@ -572,8 +575,8 @@ int oneprot_f1max(const float* pred, const void* target, int target_is_f32, int 
  * "Few rows" fp32 kernels (csrc/probe.hip): a batch is 32 or 64 rows, so a work-group owns every row of a column tile and finishes the layer in its epilogue;
  * a training step of an MLP with H hidden layers is at most 5 H + 8 launches (5 H + 10 with the residual projection) and nothing is read back.  All of it fp32
  * fmaf chains, no float atomics, every sum in a fixed order: two runs give the same bits.  norm: 0 none, 1 BatchNorm1d train mode, 2 BatchNorm1d eval mode;
- * act: 0 identity, 1 ReLU, 2 erf-GELU, 3 LeakyReLU(0.01).  Dropout is the element rule of oneprot_dropout_f32 over the flat [M, n] index for (seed,
- * stream_id): the fused epilogues and that kernel draw the same mask, and the backward regenerates it.  idx (optional) int32 [M]: row m of the operand is row
+ * act: 0 identity, 1 ReLU, 2 erf-GELU, 3 LeakyReLU(0.01).  Dropout is the element rule (at oneprot_dropout_bf16) over the flat [M, n] index for (seed,
+ * stream_id): the fused epilogues and oneprot_dropout_f32 draw the same mask, and the backward regenerates it.  idx (optional) int32 [M]: row m of the operand is row
  * idx[m] of a resident [N, k] matrix, so a shuffled batch is never materialised. */
 #define ONEPROT_PROBE_MAX_BATCH 256      /* rows of a BatchNorm (train mode) batch: one work-group holds a column's whole batch */
 /* Replaces nn.Linear -> [nn.BatchNorm1d] -> activation -> [nn.Dropout] (ref saprot_fit_mlp.py:74-92,107-108) and the residual sum (:110-113):
@@ -623,7 +626,7 @@ int oneprot_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, 
    v[floor(k N / max_bin)], k = 1 .. max_bin - 1, with -0.0 read as +0.0.  bins[i, f] = the number of cuts <= X[i, f], so bin <= j iff x < cut[j]. */
 int oneprot_gbt_cuts(const float* grouped, int64_t N, int F, int max_bin, float* cuts, int* ncuts, void* stream);
 int oneprot_gbt_bin(const float* X, const float* cuts, const int* ncuts, void* bins, int64_t N, int F, int max_bin, void* stream);
-/* One round's masks (xgboost's subsample / colsample_bytree).  The uniform of element e is the 16-bit slice of oneprot_dropout_f32's element rule, over 65536.
+/* One round's masks (xgboost's subsample / colsample_bytree).  The uniform of element e is its 16-bit slice under the element rule (at oneprot_dropout_bf16), over 65536.
    Row i is kept iff uniform(seed, row_stream, i) < subsample (subsample >= 1 keeps all, drawing nothing); the n_keep features with the smallest
    uniform(seed, feat_stream, f) are kept, equal uniforms to the lower index (n_keep = F keeps all, drawing nothing).  feat_uniform: int32 [F] scratch. */
 int oneprot_gbt_sample(void* row_keep, void* feat_keep, int* feat_uniform, int64_t N, int F, float subsample, int n_keep, uint64_t seed, uint64_t row_stream,

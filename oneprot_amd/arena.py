@@ -1,6 +1,6 @@
 """The parameter arena every tower is built on: all parameters of an encoder in ONE fp32 tensor (`flat`, the only nn.Parameter) in the
 order the kernels consume them, named tensors as views into it; a bf16 mirror (GEMM operands) plus transposed bf16 weight copies for the dgrad GEMMs, refreshed
-when the arena's version counter changes (an optimizer step, a checkpoint load); the counter-based dropout streams.  Adapters are lora.py's (`LoraArena`)."""
+when the arena's version counter changes (an optimizer step, a checkpoint load); the counter-based dropout streams are rng.py's.  Adapters are lora.py's (`LoraArena`)."""
 import json
 import os
 import warnings
@@ -9,7 +9,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, rng
 
 
 class ModelConfig:
@@ -52,39 +52,18 @@ class _Out:
         return (self.last_hidden_state, self.pooler_output)[i]
 
 
-class ArenaModule(nn.Module):
+class ArenaModule(rng.StreamOwner, nn.Module):
     """Parameters of a whole encoder in one fp32 arena (`flat`) with named views, a bf16 mirror for the MFMA GEMMs, and
     state-dict hooks that expose / accept the HF key names."""
 
-    # Counter-based dropout streams (Philox key = seed, counter high words = stream id): every consumer gets a domain of its own so that no two
-    # of them can draw the same mask -- bits 60..63 the purpose (1: BERT hidden / attention dropout, 2: LoRA dropout, 3: the MSA tower's train-mode dropouts), bits 44..59 the tower
-    # (construction order within the process until OneProtLitModule re-numbers it by modality name; saved / restored with the stream state), bits 0..43 the consumer's own (call, layer, site) numbering.
-    RNG_DOMAIN_BERT, RNG_DOMAIN_LORA, RNG_DOMAIN_MSA = 1, 2, 3
-    _next_rng_uid = 0
+    RNG_DOMAIN_BERT, RNG_DOMAIN_LORA, RNG_DOMAIN_MSA = rng.DOMAINS["bert"], rng.DOMAINS["lora"], rng.DOMAINS["msa"]
     _lora = None              # no adapter (lora.LoraArena.enable_lora sets one); read on any tower by encoders.py and module.py
 
     def _init_arena(self):
         self._spec = OrderedDict()
         self._cursor = 0
         self._extra = OrderedDict()
-        self._rng_uid = ArenaModule._next_rng_uid & 0xFFFF
-        ArenaModule._next_rng_uid += 1
-
-    def _rng_stream(self, domain, local):
-        return (int(domain) << 60) | (self._rng_uid << 44) | (int(local) & ((1 << 44) - 1))
-
-    def rng_state(self):
-        """Seeds and call counters of the dropout streams (plain ints): what a checkpoint has to carry for a resumed run to continue the mask
-        sequence instead of replaying it from call 0 (OneProtLitModule.on_save_checkpoint / on_load_checkpoint)."""
-        st = {k: int(getattr(self, k)) for k in ("_lora_seed", "_lora_calls", "_drop_seed", "_drop_calls") if getattr(self, k, None) is not None}
-        if st:
-            st["_rng_uid"] = int(self._rng_uid)              # the tower id inside the stream ids: a resumed process continues THESE streams
-        return st
-
-    def set_rng_state(self, state):
-        for k in ("_lora_seed", "_lora_calls", "_drop_seed", "_drop_calls", "_rng_uid"):
-            if k in state:
-                setattr(self, k, int(state[k]))
+        self._init_streams()
 
     def _finish_arena(self):
         self._total = self._cursor

@@ -150,12 +150,7 @@ class BertTransformer(LoraArena):
         cfg = self.config
         if not (on and self.training):
             return False
-        if not (float(cfg.hidden_dropout_prob) > 0 or float(cfg.attention_probs_dropout_prob) > 0):
-            return False
-        if getattr(self, "_drop_seed", None) is None:
-            self._drop_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
-            self._drop_calls = 0
-        return True
+        return float(cfg.hidden_dropout_prob) > 0 or float(cfg.attention_probs_dropout_prob) > 0
 
     def _drop_stream(self, call_id, layer, site):
         """stream id of a dropout site: layer -1 = embeddings; site 0 = attention probabilities, 1 = attention output dense, 2 = FFN output dense"""
@@ -184,8 +179,7 @@ class BertTransformer(LoraArena):
         lay.embed(self, x, h)
         drop = self._train_dropout()
         if drop:      # hf's train-mode dropouts: embeddings, attention probabilities, the two dense outputs of every layer
-            drop_call = self._drop_calls
-            self._drop_calls += 1
+            drop_call = self._next_call()
             p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
             y_drop = f32(T, d)
             hip.call("oneprot_dropout_f32", x, x, T * d, p_h, self._drop_seed, self._drop_stream(drop_call, -1, 0))

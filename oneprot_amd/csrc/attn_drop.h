@@ -4,7 +4,7 @@
 // >= thr16 = round(p * 65536), kept probabilities scaled by 65536 / (65536 - thr16).  p < 2^-17 gives thr16 = 0: no dropout at all.
 // tests/philox_ref.py restates the rule on the host and tests/test_attention_dropout_gpu.py pins it: change no constant here.
 #pragma once
-#include "common.h"
+#include "philox.h"      // dropout_thr_scale: p -> (thr16, scale) as for the Philox masks
 
 struct AttnDrop { unsigned thr16, s0, s1; float scale; };
 __device__ __forceinline__ bool attn_keep(unsigned qi, unsigned ki, unsigned bh, const AttnDrop& dr) {
@@ -13,10 +13,7 @@ __device__ __forceinline__ bool attn_keep(unsigned qi, unsigned ki, unsigned bh,
   return (x >> 16) >= dr.thr16;
 }
 static int attn_drop_make(float p, uint64_t seed, uint64_t stream_id, AttnDrop& dr) {
-  if (!(p >= 0.f) || !(p < 1.f)) return OP_EINVAL;
-  dr.thr16 = (unsigned)(p * 65536.f + 0.5f);
-  if (dr.thr16 >= 65536u) return OP_EINVAL;
-  dr.scale = 65536.f / (float)(65536u - dr.thr16);
+  if (!dropout_thr_scale(p, dr.thr16, dr.scale)) return OP_EINVAL;
   const uint64_t m = (seed ^ (stream_id * 0x9E3779B97F4A7C15ull)) * 0xD6E8FEB86659FD93ull;
   dr.s0 = (unsigned)m; dr.s1 = (unsigned)(m >> 32) ^ (unsigned)(stream_id * 0x2545F491u);
   return OP_OK;

@@ -5,12 +5,15 @@
 set -e
 cd "$(dirname "$0")"
 SRCS="rowops.hip gemm_nt.hip gemm_nt8.hip gemm_nt_ln.hip gemm_tn.hip sgemm.hip attention.hip featops.hip retrieval.hip msa.hip msa_select.hip pronet.hip metrics.hip probe.hip gbt.hip"
+HDRS="$(ls *.h) ../../include/oneprot_hip.h"      # every unit depends on every header: no list to keep by hand
 OBJS=""
 PIDS=""
 ASM=""       # units whose .s is already being written: the loop after this one must not start a second writer of the same .s.tmp
 for s in $SRCS; do
   o="${s%.hip}.o"
-  if [ ! -f "$o" ] || [ ! -f "$o.remarks" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ attn_drop.h -nt "$o" ] || [ gemm_epi.h -nt "$o" ] || [ gemm_epi8.h -nt "$o" ] || [ sched_ws.h -nt "$o" ] || [ ../../include/oneprot_hip.h -nt "$o" ]; then
+  stale=""
+  for h in "$s" $HDRS; do if [ "$h" -nt "$o" ]; then stale=1; fi; done
+  if [ ! -f "$o" ] || [ ! -f "$o.remarks" ] || [ -n "$stale" ]; then
     ( if hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-value -Rpass-analysis=kernel-resource-usage -c "$s" -o "$o.tmp" 2> "$o.remarks.tmp"; then
         mv "$o.tmp" "$o"; mv "$o.remarks.tmp" "$o.remarks"
       else

@@ -71,8 +71,7 @@ __device__ __forceinline__ void gelu_fwd_and_grad(float x, float& g, float& dg) 
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words.  The dropout masks of this library are pure functions of
-// (seed, stream id, element index) through this generator and are never stored (featops.hip: oneprot_dropout_*; attention.hip: the BERT tower's
-// attention-probability dropout).
+// (seed, stream id, element index) through this generator and are never stored.  Called through philox.h only, which states the element rule.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {

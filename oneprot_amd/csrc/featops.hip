@@ -2,7 +2,7 @@
 //   GELU (proj head), L2-normalise (+logit scale), softmax cross-entropy of the contrastive logits (fwd+bwd fused),
 //   L1 feature penalty, global grad-norm (two-stage deterministic reduction), clip coefficient, fused Adam.
 // All HBM-bound or latency-bound; reductions are deterministic (no float atomics).
-#include "common.h"
+#include "philox.h"
 #include "sched_ws.h"
 #include "../../include/oneprot_hip.h"
 #include <float.h>
@@ -243,16 +243,15 @@ extern "C" int oneprot_key_padding_bias(const int64_t* ids, float* bias, int64_t
 
 // ---------------------------------------------------------------------------------------------------------
 // Dropout of a bf16 operand (peft 0.5.0 lora.Linear: the adapter branch sees dropout(x); ref sequence_encoder.py:61-74, lora_dropout).  The mask is
-// never stored: element e keeps iff the 16-bit slice e & 7 of Philox4x32-10(counter = (e >> 3, stream), key = seed) is >= thr = round(p * 65536),
-// so the backward kernel regenerates the forward's mask from (seed, stream).  Kept values are scaled by 65536 / (65536 - thr), the inverse of
-// the keep probability actually used.  torch's own Philox stream is not reproduced (a different generator of the same distribution).
+// never stored: it is the element rule of philox.h over the flat index, so the backward kernel regenerates the forward's mask from (seed, stream).
+// torch's own Philox stream is not reproduced (a different generator of the same distribution).
 // MODE 0: y = dropout(x);  MODE 1: y += dropout'(x) = mask * scale * x  (y, x bf16; the adapter branch's input gradient added to the direct one)
 template <int MODE>
 __global__ void __launch_bounds__(256) k_dropout_bf16(const u32x4* __restrict__ x, u32x4* __restrict__ y, size_t n8, unsigned thr, float scale, unsigned long long seed,
                                                      unsigned long long stream_id) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-    unsigned rnd[4];
-    philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
+    bool keep[8];
+    philox_keep8(i, thr, seed, stream_id, keep);
     const u32x4 v = x[i];
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
     unsigned o[4];
@@ -261,8 +260,8 @@ __global__ void __launch_bounds__(256) k_dropout_bf16(const u32x4* __restrict__ 
     const unsigned a[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float lo = ((rnd[j] & 0xffffu) >= thr) ? bflo(w[j]) * scale : 0.f;
-      float hi = ((rnd[j] >> 16) >= thr) ? bfhi(w[j]) * scale : 0.f;
+      float lo = keep[2 * j] ? bflo(w[j]) * scale : 0.f;
+      float hi = keep[2 * j + 1] ? bfhi(w[j]) * scale : 0.f;
       if (MODE == 1) { lo += bflo(a[j]); hi += bfhi(a[j]); }
       o[j] = pack2bf(lo, hi);
     }
@@ -274,16 +273,16 @@ __global__ void __launch_bounds__(256) k_dropout_bf16(const u32x4* __restrict__ 
 __global__ void __launch_bounds__(256) k_dropout_bwd_add_f32(const u32x4* __restrict__ dy, float4* __restrict__ dx, size_t n8, unsigned thr, float scale,
                                                              unsigned long long seed, unsigned long long stream_id) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-    unsigned rnd[4];
-    philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
+    bool keep[8];
+    philox_keep8(i, thr, seed, stream_id, keep);
     const u32x4 v = dy[i];
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
     float4 a = dx[2 * i], b = dx[2 * i + 1];
     float* o[8] = {&a.x, &a.y, &a.z, &a.w, &b.x, &b.y, &b.z, &b.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if ((rnd[j] & 0xffffu) >= thr) *o[2 * j] += bflo(w[j]) * scale;
-      if ((rnd[j] >> 16) >= thr) *o[2 * j + 1] += bfhi(w[j]) * scale;
+      if (keep[2 * j]) *o[2 * j] += bflo(w[j]) * scale;
+      if (keep[2 * j + 1]) *o[2 * j + 1] += bfhi(w[j]) * scale;
     }
     dx[2 * i] = a; dx[2 * i + 1] = b;
   }
@@ -293,15 +292,12 @@ __global__ void __launch_bounds__(256) k_dropout_bwd_add_f32(const u32x4* __rest
 __global__ void __launch_bounds__(256) k_dropout_f32(const float4* __restrict__ x, const float4* __restrict__ resid, float4* __restrict__ y, size_t n8, unsigned thr, float scale,
                                                      unsigned long long seed, unsigned long long stream_id) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-    unsigned rnd[4];
-    philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
+    bool keep[8];
+    philox_keep8(i, thr, seed, stream_id, keep);
     float4 a = x[2 * i], b = x[2 * i + 1];
     float* o[8] = {&a.x, &a.y, &a.z, &a.w, &b.x, &b.y, &b.z, &b.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      *o[2 * j] = ((rnd[j] & 0xffffu) >= thr) ? *o[2 * j] * scale : 0.f;
-      *o[2 * j + 1] = ((rnd[j] >> 16) >= thr) ? *o[2 * j + 1] * scale : 0.f;
-    }
+    for (int j = 0; j < 8; ++j) *o[j] = keep[j] ? *o[j] * scale : 0.f;
     if (resid) {
       const float4 ra = resid[2 * i], rb = resid[2 * i + 1];
       a.x += ra.x; a.y += ra.y; a.z += ra.z; a.w += ra.w; b.x += rb.x; b.y += rb.y; b.z += rb.z; b.w += rb.w;
@@ -310,11 +306,10 @@ __global__ void __launch_bounds__(256) k_dropout_f32(const float4* __restrict__ 
   }
 }
 static int launch_dropout(int mode, const void* x, void* y, int64_t n, float p, uint64_t seed, uint64_t stream_id, void* stream, const void* resid = nullptr) {
-  if (!x || !y || n <= 0 || (n & 7) || !(p >= 0.f) || !(p < 1.f)) return OP_EINVAL;
+  unsigned thr;
+  float scale;
+  if (!x || !y || n <= 0 || (n & 7) || !dropout_thr_scale(p, thr, scale)) return OP_EINVAL;
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)resid) & 15) return OP_EINVAL;
-  const unsigned thr = (unsigned)(p * 65536.f + 0.5f);
-  if (thr >= 65536u) return OP_EINVAL;
-  const float scale = 65536.f / (float)(65536u - thr);
   const size_t n8 = (size_t)n >> 3;
   if (mode == 3) hipLaunchKernelGGL(k_dropout_f32, dim3(ew_grid(n8)), dim3(256), 0, (hipStream_t)stream, (const float4*)x, (const float4*)resid, (float4*)y, n8, thr, scale, (unsigned long long)seed, (unsigned long long)stream_id);
   else if (mode == 2) hipLaunchKernelGGL(k_dropout_bwd_add_f32, dim3(ew_grid(n8)), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x, (float4*)y, n8, thr, scale, (unsigned long long)seed, (unsigned long long)stream_id);
@@ -360,17 +355,14 @@ __global__ void __launch_bounds__(256) k_dropout_add_ln_fwd(const float* __restr
       const int c = lane + 64 * i;
       if (c < nv8) {
         const size_t e8 = row8 + c;
-        unsigned rnd[4];
-        philox4x32_10((unsigned)e8, (unsigned)(e8 >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
+        bool keep[8];
+        philox_keep8(e8, thr, seed, stream_id, keep);
         const float4 a = reinterpret_cast<const float4*>(x)[2 * e8], b = reinterpret_cast<const float4*>(x)[2 * e8 + 1];
         const float4 ra = reinterpret_cast<const float4*>(resid)[2 * e8], rb = reinterpret_cast<const float4*>(resid)[2 * e8 + 1];
         const float xin[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         const float rin[8] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[i][2 * j] = (((rnd[j] & 0xffffu) >= thr) ? xin[2 * j] * scale : 0.f) + rin[2 * j];
-          v[i][2 * j + 1] = (((rnd[j] >> 16) >= thr) ? xin[2 * j + 1] * scale : 0.f) + rin[2 * j + 1];
-        }
+        for (int j = 0; j < 8; ++j) v[i][j] = (keep[j] ? xin[j] * scale : 0.f) + rin[j];
         if (s_out) {
           reinterpret_cast<float4*>(s_out)[2 * e8] = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
           reinterpret_cast<float4*>(s_out)[2 * e8 + 1] = make_float4(v[i][4], v[i][5], v[i][6], v[i][7]);
@@ -416,11 +408,10 @@ __global__ void __launch_bounds__(256) k_dropout_add_ln_fwd(const float* __restr
 }
 extern "C" int oneprot_dropout_add_layernorm_fwd(const float* x, const float* resid, float* s_out, const float* gamma, const float* beta, void* y_bf16, float* y_f32,
                                                  float* mean, float* rstd, int64_t T, int d, float eps, float p, uint64_t seed, uint64_t stream_id, void* stream) {
-  if (!x || !resid || !gamma || !beta || (!y_bf16 && !y_f32) || T <= 0 || d <= 0 || (d & 7) || d > 4 * 512 || !(p >= 0.f) || !(p < 1.f)) return OP_EINVAL;
+  unsigned thr;
+  float scale;
+  if (!x || !resid || !gamma || !beta || (!y_bf16 && !y_f32) || T <= 0 || d <= 0 || (d & 7) || d > 4 * 512 || !dropout_thr_scale(p, thr, scale)) return OP_EINVAL;
   if (((uintptr_t)x | (uintptr_t)resid | (uintptr_t)s_out | (uintptr_t)y_bf16 | (uintptr_t)y_f32 | (uintptr_t)gamma | (uintptr_t)beta) & 15) return OP_EINVAL;
-  const unsigned thr = (unsigned)(p * 65536.f + 0.5f);
-  if (thr >= 65536u) return OP_EINVAL;
-  const float scale = 65536.f / (float)(65536u - thr);
   const int nv = (d / 8 + 63) / 64;
   const int blocks = (int)((T + 3) / 4 < 4096 ? (T + 3) / 4 : 4096);
 #define DLN(N) hipLaunchKernelGGL((k_dropout_add_ln_fwd<N>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, resid, s_out, gamma, beta, (bf16_t*)y_bf16, y_f32, mean, rstd, (int)T, d, eps, thr, scale, (unsigned long long)seed, (unsigned long long)stream_id)

@@ -12,7 +12,7 @@
 // LDS tile of the histogram kernel: 64 (node, feature) slots x max_bin bins x {g, h} x int32 = 128 KB at max_bin 256, of the CU's 160 KB: one work-group of
 // sixteen waves per CU.  Level d has 2^d nodes, so a tile holds 64 >> d features of every node of the level; a wave's 64 lanes read 64 >> d consecutive
 // feature bytes of 2^d rows, and their LDS adds land in different features' (or nodes') bins.
-#include "common.h"
+#include "philox.h"
 #include "../../include/oneprot_hip.h"
 
 #define GBT_FRAC 20
@@ -23,15 +23,6 @@ typedef unsigned long long ull_t;
 typedef long long ll_t;
 enum { GO_LOGISTIC = 0, GO_SQUARED = 1, GO_SOFTMAX = 2 };
 
-// the 16-bit slice of element e in Philox4x32-10(counter = (e >> 3, stream), key = seed): k_dropout_f32's element rule (featops.hip)
-__device__ __forceinline__ unsigned gbt_slice16(size_t e, ull_t seed, ull_t stream_id) {
-  unsigned rnd[4];
-  const size_t i = e >> 3;
-  philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
-  const unsigned j = (unsigned)e & 7u, q = j >> 1;
-  const unsigned w = q == 0 ? rnd[0] : q == 1 ? rnd[1] : q == 2 ? rnd[2] : rnd[3];
-  return (j & 1u) ? (w >> 16) : (w & 0xffffu);
-}
 static inline unsigned gbt_grid(int64_t n) { return (unsigned)((n + 255) / 256 < 1048576 ? (n + 255) / 256 : 1048576); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -69,14 +60,14 @@ __global__ void __launch_bounds__(256) k_gbt_bin(const float* __restrict__ X, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// sampling: row i is kept iff its uniform slice / 65536 < rate; the features with the n_keep smallest uniforms are kept, equal uniforms to the lower index
+// sampling: the uniform of element e is its 16-bit slice under philox.h.  Row i is kept iff its uniform slice / 65536 < rate; the features with the n_keep smallest uniforms are kept, equal uniforms to the lower index
 __global__ void __launch_bounds__(256) k_gbt_row_keep(unsigned char* __restrict__ keep, int64_t N, float rate, ull_t seed, ull_t stream_id) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
-    keep[i] = rate >= 1.0f ? 1 : ((float)gbt_slice16((size_t)i, seed, stream_id) < rate * 65536.0f ? 1 : 0);
+    keep[i] = rate >= 1.0f ? 1 : ((float)philox_slice16((size_t)i, seed, stream_id) < rate * 65536.0f ? 1 : 0);
 }
 __global__ void __launch_bounds__(256) k_gbt_feat_uniform(int* __restrict__ u, int F, ull_t seed, ull_t stream_id) {
   const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f < F) u[f] = (int)gbt_slice16((size_t)f, seed, stream_id);
+  if (f < F) u[f] = (int)philox_slice16((size_t)f, seed, stream_id);
 }
 __global__ void __launch_bounds__(256) k_gbt_feat_keep(const int* __restrict__ u, unsigned char* __restrict__ keep, int F, int n_keep) {
   const int f = blockIdx.x * 256 + threadIdx.x;

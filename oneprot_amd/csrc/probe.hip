@@ -2,9 +2,9 @@
 // BatchNorm), the layers are 1280 x 512 x 256 x <= 1943 wide, and a training step is ~40 MFLOP: what it costs is the number of launches, not arithmetic.  So a
 // work-group of the forward owns ALL rows of a column tile and finishes bias, BatchNorm statistics, activation, dropout and the residual sum in its epilogue, and
 // the backward of norm + activation + dropout is one launch that owns whole columns as well.  Everything is fp32 fmaf chains in a fixed order (the logits feed a
-// threshold search), no float atomics, and two runs give the same bits.  The dropout mask is the element rule of oneprot_dropout_f32 (featops.hip) over the flat
-// [M, n] index, regenerated in the backward and never stored.
-#include "common.h"
+// threshold search), no float atomics, and two runs give the same bits.  The dropout mask is the element rule of philox.h over the flat [M, n] index,
+// regenerated in the backward and never stored.
+#include "philox.h"
 #include "../../include/oneprot_hip.h"
 
 enum { PN_NONE = 0, PN_BN_TRAIN = 1, PN_BN_EVAL = 2, PN_LN = 3 };
@@ -25,25 +25,10 @@ __device__ __forceinline__ float probe_act_grad(float a, int act) {
   if (act == PA_LEAKY) return a > 0.f ? 1.f : 0.01f;
   return 1.f;
 }
-// element e of the flat [M, n] index keeps iff the 16-bit slice e & 7 of Philox4x32-10(counter = (e >> 3, stream), key = seed) is >= thr: k_dropout_f32's rule
-__device__ __forceinline__ bool probe_keep(size_t e, unsigned thr, ull_t seed, ull_t stream_id) {
-  unsigned rnd[4];
-  const size_t i = e >> 3;
-  philox4x32_10((unsigned)i, (unsigned)(i >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), rnd);
-  const unsigned j = (unsigned)e & 7u, q = j >> 1;
-  const unsigned w = q == 0 ? rnd[0] : q == 1 ? rnd[1] : q == 2 ? rnd[2] : rnd[3];
-  return ((j & 1u) ? (w >> 16) : (w & 0xffffu)) >= thr;
-}
+// element e of the flat [M, n] index under the element rule of philox.h
 __device__ __forceinline__ float probe_drop(float y, size_t e, unsigned thr, float scale, ull_t seed, ull_t stream_id) {
   if (thr == 0u) return y;                                                                   // p = 0: scale is 1 and every element is kept
-  return probe_keep(e, thr, seed, stream_id) ? y * scale : 0.f;
-}
-static bool drop_args(float p, unsigned& thr, float& scale) {                                // as launch_dropout (featops.hip)
-  if (!(p >= 0.f) || !(p < 1.f)) return false;
-  thr = (unsigned)(p * 65536.f + 0.5f);
-  if (thr >= 65536u) return false;
-  scale = 65536.f / (float)(65536u - thr);
-  return true;
+  return philox_slice16(e, seed, stream_id) >= thr ? y * scale : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -187,7 +172,7 @@ extern "C" int oneprot_probe_linear_fwd(const float* x, const int* idx, const fl
                                         const float* gamma, const float* beta, float* mean, float* rstd, float* running_mean, float* running_var, int M, int n, int k,
                                         int norm, int act, float p, uint64_t seed, uint64_t stream_id, void* stream) {
   unsigned thr; float scale;
-  if (!x || !w || (!z && !y) || M < 1 || n < 1 || k < 1 || norm < PN_NONE || norm > PN_BN_EVAL || act < PA_ID || act > PA_LEAKY || !drop_args(p, thr, scale)) return OP_EINVAL;
+  if (!x || !w || (!z && !y) || M < 1 || n < 1 || k < 1 || norm < PN_NONE || norm > PN_BN_EVAL || act < PA_ID || act > PA_LEAKY || !dropout_thr_scale(p, thr, scale)) return OP_EINVAL;
   if (norm != PN_NONE && (!y || !gamma || !beta)) return OP_EINVAL;
   if (norm == PN_BN_TRAIN && (M < 2 || M > ONEPROT_PROBE_MAX_BATCH)) return OP_EINVAL;      // nn.BatchNorm1d: "Expected more than 1 value per channel"
   if (norm == PN_BN_EVAL && (!running_mean || !running_var)) return OP_EINVAL;
@@ -230,7 +215,7 @@ __global__ void __launch_bounds__(256) k_probe_rownorm_fwd(const float* __restri
 extern "C" int oneprot_probe_rownorm_act_fwd(const float* z, const float* gamma, const float* beta, float* y, const float* resid, const int* resid_idx, float* mean,
                                              float* rstd, int M, int n, int act, float p, uint64_t seed, uint64_t stream_id, void* stream) {
   unsigned thr; float scale;
-  if (!z || !gamma || !beta || !y || M < 1 || n < 1 || act < PA_ID || act > PA_LEAKY || !drop_args(p, thr, scale)) return OP_EINVAL;
+  if (!z || !gamma || !beta || !y || M < 1 || n < 1 || act < PA_ID || act > PA_LEAKY || !dropout_thr_scale(p, thr, scale)) return OP_EINVAL;
   hipLaunchKernelGGL(k_probe_rownorm_fwd, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, z, gamma, beta, y, resid, resid_idx, mean, rstd, M, n, act, thr, scale,
                      (ull_t)seed, (ull_t)stream_id);
   return launch_status();
@@ -324,7 +309,7 @@ __global__ void __launch_bounds__(256) k_probe_rownorm_act_bwd(ProbeBwdArgs A, i
 extern "C" int oneprot_probe_norm_act_bwd(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd, float* dz,
                                           float* dgamma, float* dbeta, int M, int n, int norm, int act, float p, uint64_t seed, uint64_t stream_id, void* stream) {
   ProbeBwdArgs A{dy, z, gamma, beta, mean, rstd, dz, dgamma, dbeta, M, n, norm, act, 0u, 1.f, (ull_t)seed, (ull_t)stream_id};
-  if (!dy || !z || !dz || M < 1 || n < 1 || norm < PN_NONE || norm > PN_BN_EVAL || act < PA_ID || act > PA_LEAKY || !drop_args(p, A.thr, A.scale)) return OP_EINVAL;
+  if (!dy || !z || !dz || M < 1 || n < 1 || norm < PN_NONE || norm > PN_BN_EVAL || act < PA_ID || act > PA_LEAKY || !dropout_thr_scale(p, A.thr, A.scale)) return OP_EINVAL;
   if (norm != PN_NONE && (!gamma || !beta || !mean || !rstd)) return OP_EINVAL;
   if (norm == PN_BN_TRAIN && M < 2) return OP_EINVAL;
   hipLaunchKernelGGL(k_probe_norm_act_bwd, dim3((n + 15) / 16), dim3(256), 0, (hipStream_t)stream, A);
@@ -334,7 +319,7 @@ extern "C" int oneprot_probe_norm_act_bwd(const float* dy, const float* z, const
 extern "C" int oneprot_probe_rownorm_act_bwd(const float* dy, const float* z, const float* gamma, const float* beta, const float* mean, const float* rstd, float* dz,
                                              float* dgamma, float* dbeta, int M, int n, int act, float p, uint64_t seed, uint64_t stream_id, void* stream) {
   ProbeBwdArgs A{dy, z, gamma, beta, mean, rstd, dz, dgamma, dbeta, M, n, PN_LN, act, 0u, 1.f, (ull_t)seed, (ull_t)stream_id};
-  if (!dy || !z || !gamma || !beta || !mean || !rstd || !dz || M < 1 || n < 1 || act < PA_ID || act > PA_LEAKY || !drop_args(p, A.thr, A.scale)) return OP_EINVAL;
+  if (!dy || !z || !gamma || !beta || !mean || !rstd || !dz || M < 1 || n < 1 || act < PA_ID || act > PA_LEAKY || !dropout_thr_scale(p, A.thr, A.scale)) return OP_EINVAL;
   const int col_blocks = (dgamma || dbeta) ? (n + 15) / 16 : 0;
   hipLaunchKernelGGL(k_probe_rownorm_act_bwd, dim3(col_blocks + (M + 3) / 4), dim3(256), 0, (hipStream_t)stream, A, col_blocks);
   return launch_status();

@@ -7,7 +7,7 @@
 // [N + 1] and src_list int32 [32 N] of slots, targets ascending -- so that da[j] is one ordered sum and no float atomic is needed.
 // w_e = W2 W1 f_e is never written: the convolution kernels hold row c of the folded operand (WfT [F, h], column c) in registers, one thread per
 // channel, and form w_e[c] from the edge's feature row in LDS.
-#include "common.h"
+#include "philox.h"
 #include "../../include/oneprot_hip.h"
 
 #define PN_SLOTS ONEPROT_PRONET_SLOTS
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(256) k_pronet_edge_features(const float* __res
   ang[2] = atan2f(pn_dot(pn_cross(nn, x2), z2) / l2, pn_dot(nn, x2));
   if (noise) {
     unsigned w[4];
-    philox4x32_10((unsigned)s, (unsigned)(s >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+    philox_block((uint64_t)s, seed, stream_id, w);
     float n[4];
     pn_box_muller(w[0], w[1], n[0], n[1]);
     pn_box_muller(w[2], w[3], n[2], n[3]);
@@ -395,7 +395,7 @@ __global__ void __launch_bounds__(256) k_pronet_noise_add(const float* __restric
   const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
   if (q >= n4) return;
   unsigned w[4];
-  philox4x32_10((unsigned)q, (unsigned)(q >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+  philox_block((uint64_t)q, seed, stream_id, w);
   float n[4];
   pn_box_muller(w[0], w[1], n[0], n[1]);
   pn_box_muller(w[2], w[3], n[2], n[3]);

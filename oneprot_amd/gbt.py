@@ -17,9 +17,9 @@ import os
 import numpy as np
 import torch
 
-from . import downstream, hip
+from . import downstream, hip, rng
 
-RNG_DOMAIN_GBT = 6             # arena.py numbers 1-3, pronet.py 4, probe.py 5
+RNG_DOMAIN_GBT = rng.DOMAINS["gbt"]
 FRAC = 20                      # fraction bits of the fixed-point gradients (csrc/gbt.hip GBT_FRAC)
 MAX_DEPTH = 6
 OBJECTIVES = {"binary:logistic": 0, "reg:squarederror": 1, "multi:softmax": 2}
@@ -46,7 +46,7 @@ def plan_chunks(K, F, max_bin, max_depth, budget=None):
 
 def stream_of(local):
     """the Philox stream of draw number `local` of a fit: rows of round t draw from stream t, features from stream n_estimators + t"""
-    return (RNG_DOMAIN_GBT << 60) | (int(local) & ((1 << 60) - 1))
+    return rng.stream_id(RNG_DOMAIN_GBT, None, local)
 
 
 def _to_device(x, dtype, what):

@@ -40,8 +40,7 @@ class LoraArena(ArenaModule):
         self._key_prefix = "base_model.model."                          # the keys of a PeftModel
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"lora_dropout must be in [0, 1), got {dropout}")
-        self._lora_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF      # masks follow torch.manual_seed; every call / layer draws its own stream
-        self._lora_calls = 0
+        self._seed_streams("_lora")
         for p in self.parameters():
             p.requires_grad = False
         self.lora_A.requires_grad = True
@@ -175,10 +174,7 @@ class LoraArena(ArenaModule):
 
     def _lora_next_call(self):
         """a run_layers call in the two-branch form draws its id (its own masks; the backward regenerates them from (seed, call, layer)), else None"""
-        if not self._lora_two_branch():
-            return None
-        self._lora_calls += 1
-        return self._lora_calls - 1
+        return self._next_call("_lora") if self._lora_two_branch() else None
 
     def _qkv_forward(self, i, h, w_qkv, b_qkv, T, n_out, rope, q_scale, q, k, v, lora_call):
         """Layer i's fused QKV GEMM with the rotary / head-major epilogue: h [T, d] x w_qkv^T, or (lora_call not None) peft's two branches in one launch,

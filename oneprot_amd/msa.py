@@ -280,12 +280,7 @@ class MsaTransformer(ArenaModule):
         return tuple(float(getattr(cfg, k, MSA_DEFAULTS[k])) for k in ("dropout", "attention_dropout", "activation_dropout"))
 
     def _next_drop_call(self):
-        if getattr(self, "_drop_seed", None) is None:
-            self._drop_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF      # masks follow torch.manual_seed, as in bert.py
-            self._drop_calls = 0
-        call = self._drop_calls
-        self._drop_calls += 1
-        return call
+        return self._next_call()
 
     def _drop_stream(self, call, layer, site):
         """stream id of a dropout site.  layer -1, site 0: the embedding dropout; within a layer 0 = row probabilities, 1 = row-block output,

@@ -16,10 +16,10 @@ import torch
 import torch.nn as nn
 
 from . import downstream, hip
-from .arena import ArenaModule
 from .optim import FusedAdamW
+from .rng import DOMAINS, StreamOwner
 
-RNG_DOMAIN_PROBE = 5           # arena.py numbers 1-3, pronet.py 4
+RNG_DOMAIN_PROBE = DOMAINS["probe"]
 ACTIVATIONS = {"relu": nn.ReLU, "gelu": nn.GELU, "leaky_relu": nn.LeakyReLU}
 EVAL_SLAB = 4096               # rows of one eval-mode forward (validation loss, predict)
 
@@ -70,7 +70,7 @@ class _MLPFn(torch.autograd.Function):
         return (None, None, None) + tuple(model._gview[id(p)].clone() if p.requires_grad else None for p in ctx.params)
 
 
-class MLP(nn.Module):
+class MLP(StreamOwner, nn.Module):
     """ref saprot_fit_mlp.py:63-115, same constructor, forward and state-dict names.  An activation outside {relu, gelu, leaky_relu} raises ValueError (the
     reference silently builds no activation).  With both norm flags BatchNorm wins, as in the reference."""
 
@@ -104,9 +104,7 @@ class MLP(nn.Module):
         self.hidden_layers = nn.ModuleList(layers)
         self.output_layer = nn.Linear(in_features, self.output_dim)
         self.residual_projection = nn.Linear(self.input_dim, hidden_dims[-1]) if self.use_residual and self.input_dim != hidden_dims[-1] else None
-        self._rng_uid = ArenaModule._next_rng_uid & 0xFFFF                     # one numbering of the towers of a process (arena.py)
-        ArenaModule._next_rng_uid += 1
-        self._drop_seed, self._drop_calls = 0x5EED0000 + self._rng_uid, 0
+        self._init_streams(fixed_seed=True)
         self._flatten()
 
     # ---- the arena: every parameter a view of one flat tensor, every gradient the kernels write a view of a second one.  The bookkeeping (_plan, _flat, _gflat,
@@ -180,16 +178,7 @@ class MLP(nn.Module):
     # ---- RNG position of the dropout masks
     def stream_of(self, call, layer):
         """the Philox stream of hidden layer `layer`'s dropout in train-mode forward number `call`"""
-        local = call * max(len(self._plan), 1) + layer
-        return (RNG_DOMAIN_PROBE << 60) | (self._rng_uid << 44) | (int(local) & ((1 << 44) - 1))
-
-    def rng_state(self):
-        return {"_drop_seed": int(self._drop_seed), "_drop_calls": int(self._drop_calls), "_rng_uid": int(self._rng_uid)}
-
-    def set_rng_state(self, state):
-        for k in ("_drop_seed", "_drop_calls", "_rng_uid"):
-            if k in state:
-                setattr(self, k, int(state[k]))
+        return self._rng_stream(RNG_DOMAIN_PROBE, call * max(len(self._plan), 1) + layer)
 
     # ---- forward
     def forward(self, x):
@@ -212,10 +201,7 @@ class MLP(nn.Module):
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size [{M}, {plan[0][0].out_features}]")
             if M > hip.PROBE_MAX_BATCH:
                 raise ValueError(f"MLP: a BatchNorm batch of {M} rows; the train-mode kernel holds at most {hip.PROBE_MAX_BATCH}")
-        call = None
-        if training and self.dropout_rate > 0 and H:
-            call = self._drop_calls
-            self._drop_calls += 1
+        call = self._next_call() if training and self.dropout_rate > 0 and H else None
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
         act = hip.PROBE_ACT[self.activation]
         resid, resid_gathered = None, False

@@ -12,7 +12,7 @@ the published module names; the arithmetic of a call is ONE torch.autograd.Funct
 replays it in reverse: node linears on oneprot_sgemm (their weight gradients, which contract over the nodes, on oneprot_wgrad_f32), everything per edge in the fused convolution kernels, which never write the [E, h] edge weights
 or messages.  No float atomics and no host read-back: a step is a pure function of (inputs, parameters, RNG position).
 
-Train-mode noise and dropout (module in train mode only) draw from the library's Philox streams under RNG domain 4; `rng_state()` / `set_rng_state()`
+Train-mode noise and dropout (module in train mode only) draw from the library's Philox streams under rng.py's domain "pronet"; `rng_state()` / `set_rng_state()`
 carry the position.  Same distribution as torch's, another draw."""
 import math
 
@@ -20,11 +20,11 @@ import torch
 from torch import nn
 
 from . import hip
-from .arena import ArenaModule
+from .rng import DOMAINS, StreamOwner
 
 SLOTS = hip._consts["PRONET_SLOTS"]
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
-RNG_DOMAIN_PRONET = 4
+RNG_DOMAIN_PRONET = DOMAINS["pronet"]
 NOISE_SIGMA, NOISE_CLIP = 0.025, 0.1
 
 
@@ -263,7 +263,7 @@ class _ProNetFn(torch.autograd.Function):
         return (None, None, None, None) + grads
 
 
-class ProNet(nn.Module):
+class ProNet(StreamOwner, nn.Module):
     def __init__(self, level="aminoacid", num_blocks=4, hidden_channels=128, out_channels=1, mid_emb=64, num_radial=6, num_spherical=2, cutoff=10.0,
                  max_num_neighbors=32, int_emb_layers=3, out_layers=2, num_pos_emb=16, dropout=0, data_augment_eachlayer=False, euler_noise=False):
         super().__init__()
@@ -297,26 +297,13 @@ class ProNet(nn.Module):
         self.lins_out = nn.ModuleList([nn.Linear(h, h) for _ in range(out_layers - 1)])
         self.lin_out = nn.Linear(h, out_channels)
         self.register_buffer("feature_consts", feature_constants(num_radial, num_pos_emb), persistent=False)
-        self._rng_uid = ArenaModule._next_rng_uid & 0xFFFF                     # one numbering of the towers of a process (arena.py)
-        ArenaModule._next_rng_uid += 1
-        self._drop_seed, self._drop_calls = 0x5EED0000 + self._rng_uid, 0
+        self._init_streams(fixed_seed=True)
 
     # ---- RNG position ----
-    def _rng_stream(self, local):
-        return (RNG_DOMAIN_PRONET << 60) | (self._rng_uid << 44) | (int(local) & ((1 << 44) - 1))
-
     def stream_of(self, call, site):
         """the Philox stream of draw `site` of forward call `call`: site 0 the Euler noise, 1 + 2 b the node noise of block b, 2 + 2 b its dropout,
         1 + 2 num_blocks + k the dropout of readout layer k"""
-        return self._rng_stream(call * (2 * self.num_blocks + self.out_layers + 1) + site)
-
-    def rng_state(self):
-        return {"_drop_seed": int(self._drop_seed), "_drop_calls": int(self._drop_calls), "_rng_uid": int(self._rng_uid)}
-
-    def set_rng_state(self, state):
-        for k in ("_drop_seed", "_drop_calls", "_rng_uid"):
-            if k in state:
-                setattr(self, k, int(state[k]))
+        return self._rng_stream(RNG_DOMAIN_PRONET, call * (2 * self.num_blocks + self.out_layers + 1) + site)
 
     # ---- forward ----
     @staticmethod
@@ -332,8 +319,7 @@ class ProNet(nn.Module):
         self.check_input(batch)
         rng = None
         if self.training and (self.dropout > 0 or self.data_augment_eachlayer or self.euler_noise):
-            rng = (self._drop_seed, self._drop_calls)
-            self._drop_calls += 1
+            rng = (self._drop_seed, self._next_call())
         params = tuple(self.parameters())
         record = torch.is_grad_enabled() and any(p.requires_grad for p in params)       # grad mode is off inside Function.forward: decided here
         return _ProNetFn.apply(self, batch, rng, record, *params)
