@@ -6,7 +6,9 @@ cases with their fp64 values), each checked without a GPU in tests/test_gbt_cpu.
 import functools
 
 import numpy as np
+import torch
 
+from oneprot_amd import gbt, hip
 from tests import gbt_ref as R
 from tests import philox_ref as PR
 
@@ -240,3 +242,80 @@ def grad_reference(m, y, objective):
     g64, h64 = gradients64(m, y, objective)
     e32 = max(float(np.abs(g32 - g64).max()), float(np.abs(h32 - h64).max()), 2.0 ** -24)
     return g64, h64, e32, 0.5 + 2.0 ** R.FRAC * GRAD_FACTOR * e32
+
+
+# ================================================================================================================== launches and gates the GPU files share
+DEV = "cuda:0"
+# largest |device margin - restatement margin| over the rounds of every end-to-end fixture, measured on an MI355X (printed by the tests with -s); the
+# regression fixture has no exp in its chain and every operation of it is a single IEEE fp32 operation on both sides: it is exact
+MEASURED = {"logistic": 1.192e-7, "squared": 0.0, "softmax": 2.384e-7, "multilabel": 2.384e-7, "sampled": 3.576e-7}       # 1, 0, 2, 2 and 3 x 2^-23
+FACTOR = 16.0
+
+
+def dev(a, dtype=None):
+    t = torch.as_tensor(np.ascontiguousarray(a))
+    return t.to(DEV, dtype).contiguous() if dtype is not None else t.to(DEV).contiguous()
+
+
+def cuts_of(cuts, ncuts):
+    cuts, ncuts = cuts.cpu().numpy(), ncuts.cpu().numpy()
+    return [cuts[f, :ncuts[f]] for f in range(len(ncuts))]
+
+
+def run_grad(m, y, objective, keep=None):
+    N, K = m.shape
+    md = dev(m, torch.float32)
+    keep = np.ones(N, dtype=np.uint8) if keep is None else keep.astype(np.uint8)
+    gq, hq = (torch.empty(K, N, dtype=torch.int32, device=DEV) for _ in range(2))
+    expo, gmax = torch.empty(K, dtype=torch.int32, device=DEV), torch.empty(1, dtype=torch.int32, device=DEV)
+    if objective == R.SOFTMAX:
+        hip.call("oneprot_gbt_grad", md, None, dev(y, torch.int32), dev(keep), gq, hq, expo, gmax, N, K, 2)
+    else:
+        hip.call("oneprot_gbt_grad", md, dev(y.reshape(N, K), torch.float32), None, dev(keep), gq, hq, expo, gmax, N, K, gbt.OBJECTIVES[objective])
+    return gq, hq, expo
+
+
+def hist_reference(bins, gq, hq, pos, level, B):
+    """int64 [K, L, F, B, 2]: every (row, feature) adds its row's integers at (node, feature, bin) -- one np.add.at per output and component"""
+    K, (N, F) = gq.shape[0], bins.shape
+    L, base = 1 << level, (1 << level) - 1
+    out = np.zeros((K, L, F, B, 2), dtype=np.int64)
+    for k in range(K):
+        rows = np.nonzero((pos[k] >= base) & (pos[k] < base + L))[0]
+        flat = ((pos[k][rows, None].astype(np.int64) - base) * F + np.arange(F)[None, :]) * B + bins[rows].astype(np.int64)
+        for c, q in enumerate((gq[k], hq[k])):
+            acc = np.zeros(L * F * B, dtype=np.int64)
+            np.add.at(acc, flat.reshape(-1), np.repeat(q[rows], F))
+            out[k, ..., c] = acc.reshape(L, F, B)
+    return out
+
+
+def run_hist(bins, gq, hq, pos, level, B):
+    K, N = gq.shape
+    F = bins.shape[1]
+    hist = torch.full((K, 1 << level, F, B, 2), -7, dtype=torch.int64, device=DEV)       # overwritten, not accumulated
+    assert hip.query("oneprot_gbt_hist_bytes", F, B, level) * K == hist.numel() * 8
+    hip.call("oneprot_gbt_hist", bins, gq, hq, pos, hist, N, F, B, level, K)
+    return hist
+
+
+def fit_device(name, **over):
+    X, y = data(name)
+    objective = FIXTURES[name][0]
+    kw = dict(PARAMS, objective=objective)
+    if name == "sampled":
+        kw.update(subsample=SAMPLE_RATE, colsample_bytree=SAMPLE_RATE, random_state=SAMPLE_SEED)
+    kw.update(over)
+    cls = gbt.XGBRegressor if objective == R.SQUARED else gbt.XGBClassifier
+    return cls(**kw).fit(X, y), X, y
+
+
+def assert_same_trees(model, ref, label):
+    s = {k: v.cpu().numpy() for k, v in model.state_dict().items()}
+    for t, rnd in enumerate(ref["trees"]):
+        for k, tr in enumerate(rnd):
+            assert np.array_equal(s["tree_feat"][t, k], tr["feat"]), (label, t, k, s["tree_feat"][t, k], tr["feat"])
+            split = tr["feat"] >= 0
+            assert np.array_equal(s["tree_bin"][t, k][split], tr["bin"][split]) and np.array_equal(s["tree_thr"][t, k][split], tr["thr"][split]), (label, t, k)
+    got = cuts_of(model._state["cuts"], model._state["ncuts"])
+    assert all(np.array_equal(a, b) for a, b in zip(got, ref["cuts"]))

@@ -69,17 +69,15 @@ pytestmark = pytest.mark.gpu
 from oneprot_amd import hip  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
 from tests import philox_ref as PR  # noqa: E402
-from tests import test_attention_production_gpu as AP  # noqa: E402
-from tests.test_production_sizes_gpu import SEED_HI, STREAM_HI  # noqa: E402
+from tests.attn_cases import CTX_GATE, CTX_GATE_X, LSE_GATE, LSE_GATE_X, extreme_rows, fwd_inputs, run_fwd  # noqa: E402    (2^-7, 1e-2), (2^-6, 1.5e-2) x scale; (1e-4, 5e-3), (2e-4, 2e-2)
+from tests.attn_ref import bhld, bwd_ref, bwd_ref_reading_ctx, fwd_ref, rot_half  # noqa: E402
+from tests.cases import DEV, SEED_HI, STREAM_HI, bf, gen, randn, ws  # noqa: E402
+from tests.gate import close  # noqa: E402
 
-DEV = AP.DEV
 F64 = torch.float64
-LN2 = math.log(2.0)
 NEG_MIN = torch.finfo(torch.float32).min
 NAN = float("nan")
 
-CTX_GATE, LSE_GATE = AP.CTX_GATE, AP.LSE_GATE                        # (2^-7, 1e-2) x scale, (1e-4, 5e-3)
-CTX_GATE_X, LSE_GATE_X = AP.CTX_GATE_X, AP.LSE_GATE_X                # (2^-6, 1.5e-2) x scale, (2e-4, 2e-2)
 EDGE_LENGTHS = [1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 777]
 
 
@@ -96,11 +94,6 @@ def drop_bias(B, L):
         if L >= 5:
             bias[b, L - L // 5:] = float("-inf") if (L + b) % 2 == 0 else NEG_MIN          # b = 1: -inf for odd L
     return bias.to(DEV)
-
-
-def bhld(x, B, H, L, hd):
-    """ctx / dctx [B * L, H * hd] as [B, H, L, hd]"""
-    return x.view(B, L, H, hd).permute(0, 2, 1, 3)
 
 
 def export_keep(B, H, L, p, seed=SEED_HI, stream=STREAM_HI):
@@ -122,7 +115,7 @@ def run_fwd_split(q, k, v, bias):
     """oneprot_attn_fwd on k_attn_fwd<HD, false>: the body the dropout forward shares"""
     hip.query("oneprot_attn_force_fwd_path", 0)
     try:
-        return AP.run_fwd(q, k, v, bias)
+        return run_fwd(q, k, v, bias)
     finally:
         hip.query("oneprot_attn_force_fwd_path", -1)
 
@@ -131,7 +124,7 @@ def run_bwd_drop(q, k, v, bias, ctx, dctx, lse, p, q_scale, cosd=None, sind=None
     """dq, dk, dv as [3, B, H, L, hd] (views of the bf16 dqkv the call wrote over NaN)"""
     B, H, L, hd = q.shape
     dqkv = torch.full((B * L, 3 * H * hd), NAN, dtype=torch.bfloat16, device=DEV)
-    w = AP._ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
+    w = ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
     hip.call("oneprot_attn_bwd_dropout", q, k, v, bias, ctx, dctx, lse, cosd, sind, q_scale, dqkv, w, B, H, L, hd, p, seed, stream)
     return dqkv.view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
 
@@ -139,60 +132,13 @@ def run_bwd_drop(q, k, v, bias, ctx, dctx, lse, p, q_scale, cosd=None, sind=None
 def run_bwd_split(q, k, v, bias, ctx, dctx, lse, q_scale):
     B, H, L, hd = q.shape
     dqkv = torch.full((B * L, 3 * H * hd), NAN, dtype=torch.bfloat16, device=DEV)
-    w = AP._ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
+    w = ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
     hip.query("oneprot_attn_force_bwd_path", 0)
     try:
         hip.call("oneprot_attn_bwd", q, k, v, bias, ctx, dctx, lse, None, None, q_scale, dqkv, w, B, H, L, hd)
     finally:
         hip.query("oneprot_attn_force_bwd_path", -1)
     return dqkv.view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
-
-
-# ====================================================================================================== fp64 references
-def fwd_ref(q, k, v, bias, keep, scale):
-    """fp64 (keep * softmax(q k^T ln 2 + bias) * scale) v as [B, H, L, hd], and the undropped lse [B, H, L]; q is in log2 units"""
-    s = (q.to(F64) @ k.to(F64).transpose(-1, -2)) * LN2
-    if bias is not None:
-        s = s + bias.to(F64)[:, None, None, :]
-    lse = torch.logsumexp(s, -1)
-    p = torch.exp(s - lse[..., None])
-    return (p * keep * scale) @ v.to(F64), lse
-
-
-def bwd_ref(q, k, v, bias, dctx, keep, scale, q_scale, cos=None, sin=None):
-    """fp64 autograd through (rotary +) scale + softmax + mask: the gradients w.r.t. the un-rotated, un-scaled projections, i.e. w.r.t. the stored q
-    divided by log2 e and q_scale (bwd_ref of tests/test_attention_production_gpu.py with the mask).  cos / sin fp64 [L, hd] or None.  [B, H, L, hd] each."""
-    B, H, L, hd = q.shape
-    qr, kr = q.to(F64) / hip.LOG2E, k.to(F64)
-    if cos is not None:
-        qr, kr = qr * cos - AP._rot_half(qr) * sin, kr * cos - AP._rot_half(kr) * sin          # a rotation is orthogonal: the projections, exactly
-    ql, kl, vl = (qr / q_scale).requires_grad_(True), kr.requires_grad_(True), v.to(F64).requires_grad_(True)
-    qs, ks = ql * q_scale, kl
-    if cos is not None:
-        qs, ks = qs * cos + AP._rot_half(qs) * sin, ks * cos + AP._rot_half(ks) * sin
-    s = qs @ ks.transpose(-1, -2)
-    if bias is not None:
-        s = s + bias.to(F64)[:, None, None, :]
-    o = (torch.softmax(s, -1) * keep * scale) @ vl
-    o.backward(bhld(dctx, B, H, L, hd).to(F64))
-    return ql.grad, kl.grad, vl.grad
-
-
-def bwd_ref_reading_ctx(q, k, v, bias, ctx_in, dctx, keep, scale, q_scale, cos=None, sin=None):
-    """The same gradients in closed form, with delta = rowsum(dO * ctx_in) from a given ctx [B, H, L, hd] (fp64): dS = P (keep scale dP - delta),
-    dq = q_scale R^T (dS k), dk = R^T (dS^T q / log2 e), dv = (keep P scale)^T dO, R^T the inverse rotation.  With the fp64 ctx it IS bwd_ref (asserted
-    where it is used); with the bf16 ctx the backward is handed it is the fp64 value of what that call is asked to compute from its inputs."""
-    B, H, L, hd = q.shape
-    s = (q.to(F64) @ k.to(F64).transpose(-1, -2)) * LN2
-    if bias is not None:
-        s = s + bias.to(F64)[:, None, None, :]
-    P = torch.softmax(s, -1)
-    dO = bhld(dctx, B, H, L, hd).to(F64)
-    dS = P * (keep * scale * (dO @ v.to(F64).transpose(-1, -2)) - (dO * ctx_in).sum(-1, keepdim=True))
-    dq, dk, dv = dS @ k.to(F64), dS.transpose(-1, -2) @ (q.to(F64) / hip.LOG2E), (P * keep * scale).transpose(-1, -2) @ dO
-    if cos is not None:
-        dq, dk = dq * cos - AP._rot_half(dq) * sin, dk * cos - AP._rot_half(dk) * sin
-    return q_scale * dq, dk, dv
 
 
 GRAD_GATE = (2e-2, 5e-2, 5e-2)                  # per slab rel_err; per element (rtol, atol / max|ref of the slab|)
@@ -209,7 +155,7 @@ def grad_gates(got, ref, name, atol_scale=1.0, xslab=None, gate_x=GRAD_GATE):
     print(f"{name}: worst slab rel_err {float(torch.nan_to_num(rel, nan=9.9).max()):.3e}" + (f", with +-400 scores {float(torch.nan_to_num(rel[xslab], nan=9.9).max()):.3e}" if bool(xslab.any()) else ""))
     ok = rel < g[0]
     assert bool(ok.all()), f"{name}: rel err {float(torch.nan_to_num(rel, nan=9.9)[~ok].max()):.3e} in slab {tuple(int(i) for i in (~ok).nonzero()[0])}"
-    AP.check(got, ref, g[1][:, :, None, None], (g[2] * atol_scale * ref.abs().flatten(2).amax(-1))[..., None, None], name)
+    close(got, ref, g[1][:, :, None, None], (g[2] * atol_scale * ref.abs().flatten(2).amax(-1))[..., None, None], name)
 
 
 def slab_gate(gate, gate_x, xslab, mult=1.0):
@@ -230,9 +176,9 @@ def check_case(q, k, v, bias, dctx, p, cosd=None, sind=None, xslab=None, atol_sc
     o_ref, lse_ref = fwd_ref(q, k, v, bias, keep, scale)
     got_ctx = bhld(ctx, B, H, L, hd)
     rt, at = slab_gate(CTX_GATE, CTX_GATE_X, xslab, scale)
-    AP.check(got_ctx, o_ref, rt, at, f"ctx [b, h, l, d] {tag}")
+    close(got_ctx, o_ref, rt, at, f"ctx [b, h, l, d] {tag}")
     rt, at = slab_gate(LSE_GATE, LSE_GATE_X, xslab)
-    AP.check(lse, lse_ref, rt[..., 0], at[..., 0], f"lse [b, h, l] {tag}")
+    close(lse, lse_ref, rt[..., 0], at[..., 0], f"lse [b, h, l] {tag}")
     valid = (bias > -1.0e30) if bias is not None else torch.ones(B, L, dtype=torch.bool, device=DEV)
     dead = ~(keep & valid[:, None, None, :]).any(-1)                                       # [B, H, L]: rows whose valid keys are all dropped
     assert bool((got_ctx[dead] == 0).all()), f"{tag}: a ctx row with every key dropped is not exactly zero"
@@ -246,7 +192,7 @@ def check_case(q, k, v, bias, dctx, p, cosd=None, sind=None, xslab=None, atol_sc
         cos, sin = torch.cat([cosd, cosd], -1).to(F64), torch.cat([sind, sind], -1).to(F64)      # the fp32 tables the kernel reads
     got = run_bwd_drop(q, k, v, bias, ctx, dctx, lse, p, q_scale, cosd, sind)
     assert bool(torch.isfinite(got.float()).all()), f"{tag}: non-finite or unwritten gradient"
-    refs = bwd_ref(q, k, v, bias, dctx, keep, scale, q_scale, cos, sin)
+    refs = bwd_ref(q, k, v, bias, dctx, q_scale, cos, sin, keep, scale)
     if L <= 2 or bool(xslab.any()):
         # (the file's docstring) the gradient is small against 2^-9 |dO| |ctx| here: delta from the bf16 ctx the call is handed, as the kernels form it
         closed = bwd_ref_reading_ctx(q, k, v, bias, o_ref, dctx, keep, scale, q_scale, cos, sin)
@@ -261,8 +207,8 @@ def check_case(q, k, v, bias, dctx, p, cosd=None, sind=None, xslab=None, atol_sc
 
 
 def make_case(B, H, L, hd, seed, padded=True):
-    q, k, v = AP.fwd_inputs(B, H, L, hd, seed)
-    dctx = AP._randn((B * L, H * hd), AP._gen(seed + 1), 1.0, torch.bfloat16)
+    q, k, v = fwd_inputs(B, H, L, hd, seed)
+    dctx = randn((B * L, H * hd), gen(seed + 1), 1.0, dtype=torch.bfloat16)
     return q, k, v, (drop_bias(B, L) if padded else None), dctx
 
 
@@ -315,7 +261,7 @@ def test_dropout_refused_arguments(B, H, L, hd):
         lse = torch.full((B, H, L), NAN, device=DEV)
         dqkv = torch.full((B * L, 3 * H * hd_), NAN, dtype=torch.bfloat16, device=DEV)
         keep = torch.full((B, H, L, L), 7, dtype=torch.uint8, device=DEV)
-        w = AP._ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
+        w = ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
         yield "fwd", lambda: hip.call("oneprot_attn_fwd_dropout", q, k, v, bias, ctx, lse, B, H, L, hd_, p, SEED_HI, STREAM_HI), ctx
         yield "bwd", lambda: hip.call("oneprot_attn_bwd_dropout", q, k, v, bias, q.new_zeros(B * L, H * hd_), dctx, lse.new_zeros(B, H, L), None, None, hd_ ** -0.5,
                                       dqkv, w, B, H, L, hd_, p, SEED_HI, STREAM_HI), dqkv
@@ -391,9 +337,9 @@ def test_dropout_mask_bits_of_all_three_kernels(L, hd, p):
     q_scale = hd ** -0.5
     keep = export_keep(B, H, L, p)
     assert abs(float(keep.float().mean()) - (1.0 - thr / 65536.0)) < 0.01 and not bool(keep.all())
-    g = AP._gen(7600 + L)
+    g = gen(7600 + L)
     q0 = torch.zeros(shape, dtype=torch.bfloat16, device=DEV)
-    k_any, v_any = AP._randn(shape, g, 1.0, torch.bfloat16), AP._randn(shape, g, 1.0, torch.bfloat16)
+    k_any, v_any = randn(shape, g, 1.0, dtype=torch.bfloat16), randn(shape, g, 1.0, dtype=torch.bfloat16)
     unit = scale / L                                                  # keep * scale * P with P = 1 / L
     windows = [(w0, min(hd, L - w0)) for w0 in range(0, L, hd)]
     assert len(windows) <= 33
@@ -408,7 +354,7 @@ def test_dropout_mask_bits_of_all_three_kernels(L, hd, p):
         ctx, lse = run_fwd_drop(q0, k_any, _unit_window(shape, w0, n), None, p)
         c = bhld(ctx, B, H, L, hd)
         assert bool(torch.isfinite(c.float()).all()) and bool((c[..., n:] == 0).all())
-        AP.check(lse, torch.full((B, H, L), math.log(L), dtype=F64, device=DEV), *LSE_GATE, f"lse = ln L, window {w0}")
+        close(lse, torch.full((B, H, L), math.log(L), dtype=F64, device=DEV), *LSE_GATE, f"lse = ln L, window {w0}")
         unit_values(c, f"ctx, key window {w0}")
         seen[:, :, :, w0:w0 + n] = c[..., :n] != 0
     bad = seen != keep
@@ -452,7 +398,7 @@ def test_dropout_extreme_scores(B, H, L, hd):
     """the +-400 rows of extreme_rows in slabs of both groups of eight (the forward rescales its accumulators while the masked copy of P is live), the
     other slabs ordinary and under the ordinary gates"""
     q, k, v, bias, dctx = make_case(B, H, L, hd, 7700 + L)
-    xslab = AP.extreme_rows(q, k, [1, 4, 6, 8, 9], AP._gen(7701 + L))
+    xslab = extreme_rows(q, k, [1, 4, 6, 8, 9], gen(7701 + L))
     check_case(q, k, v, bias, dctx, 0.1, xslab=xslab, tag=f"extreme L {L} hd {hd}")
 
 
@@ -461,13 +407,13 @@ def test_dropout_extreme_scores(B, H, L, hd):
 def test_dropout_bwd_rope_chain(B, H, L, hd):
     """oneprot_attn_bwd_dropout with rotary tables: dqkv is the gradient w.r.t. the un-rotated, un-scaled projections (test_attention_bwd_rope_chain with
     the mask), against fp64 autograd through the rotation"""
-    g = AP._gen(7800 + L)
+    g = gen(7800 + L)
     ylin = torch.randn(3, B, H, L, hd, generator=g, device=DEV)
     cos, sin = O.rope_tables(L, hd)
     cosd, sind = cos[:, : hd // 2].contiguous().to(DEV), sin[:, : hd // 2].contiguous().to(DEV)
     c, s = torch.cat([cosd, cosd], -1), torch.cat([sind, sind], -1)
-    rot = lambda x: x * c + AP._rot_half(x) * s
-    q = AP.bf(rot(ylin[0] * hd ** -0.5) * hip.LOG2E)
-    k, v = AP.bf(rot(ylin[1])), AP.bf(ylin[2])
-    dctx = AP._randn((B * L, H * hd), g, 1.0, torch.bfloat16)
+    rot = lambda x: x * c + rot_half(x) * s
+    q = bf(rot(ylin[0] * hd ** -0.5) * hip.LOG2E)
+    k, v = bf(rot(ylin[1])), bf(ylin[2])
+    dctx = randn((B * L, H * hd), g, 1.0, dtype=torch.bfloat16)
     check_case(q, k, v, drop_bias(B, L), dctx, 0.1, cosd=cosd, sind=sind, tag=f"rope L {L} hd {hd}")

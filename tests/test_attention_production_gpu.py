@@ -30,12 +30,11 @@ tests/test_kernels_gpu.py + tests/test_packed_gpu.py as they were before this fi
   4 k_attn_fwd3w: the redo mark written at bh - 1 for slabs that are not first in their walk
       here: extreme scores hd 64, both lengths, and the launch of REDO_SLABS slabs; parent: nothing
   5 k_attn_varlen_bwd_dkv: lse / delta read without the head offset for head >= 2
-      here: all three packed cases (dk of head 2, rel err > 80); parent: no kernel test (H = 2), four packed step tests
+      here: all three packed cases (dk of head 2, rel err above 80); parent: no kernel test (H = 2), four packed step tests
   6 k_gemm8: accumulators of a work-group's 8th and later tiles start at 0.25 instead of 0 (the zero_acc() behind the epilogue), static lists only
       here: FFN-1 at 131072 and 131328 rows, the 650M FFN-1, the QKV GEMM; parent: the two queue-vs-static comparisons
     the same in both modes: here the same four, against fp64 (gelu off by 0.29, q by 0.10); parent: only the co-residency test (the queues hand a disturbed launch other tiles)
 """
-import gc
 import math
 
 import pytest
@@ -46,53 +45,18 @@ pytestmark = pytest.mark.gpu
 from oneprot_amd import hip  # noqa: E402
 from oneprot_amd.packing import PackedTokens  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests import attn_ref as AR  # noqa: E402
+from tests.attn_cases import CTX_GATE, CTX_GATE_X, LSE_GATE, LSE_GATE_X, extreme_rows, fwd_inputs, run_fwd  # noqa: E402,F401
+from tests.attn_ref import rot_half  # noqa: E402
+from tests.cases import DEV, bf, cu as cu_of, free, gathered_tables, gen, randn, ws  # noqa: E402
+from tests.gate import close  # noqa: E402
 
-DEV = "cuda"
 F64 = torch.float64
-LN2 = math.log(2.0)
 NEG_MIN = torch.finfo(torch.float32).min
 REDO_SLABS = 32768                                                  # csrc/attention.hip: slabs the hd-64 persistent kernel keeps marks for
 
-CTX_GATE, LSE_GATE = (2 ** -7, 1e-2), (1e-4, 5e-3)                  # test_kernels_gpu.py test_attention_fwd_bwd
-CTX_GATE_X, LSE_GATE_X = (2 ** -6, 1.5e-2), (2e-4, 2e-2)            # ... test_attention_fwd_nomax_overflow_underflow_net
-
-
-def bf(x):
-    return x.to(torch.bfloat16)
-
-
-def _gen(seed):
-    return torch.Generator(device=DEV).manual_seed(seed)
-
-
-def _randn(shape, g, scale=1.0, dtype=torch.float32):
-    return (torch.randn(shape, generator=g, device=DEV) * scale).to(dtype)
-
-
-def _ws(nbytes):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=DEV)
-
-
-def _free():
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
 def _n_cu():
     return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def check(got, ref, rtol, atol, msg):
-    """|got - ref| <= atol + rtol |ref| for every element (ref fp64; atol a number or a tensor that broadcasts); a NaN in got fails"""
-    got = got.to(F64)
-    err = (got - ref).abs()
-    bad = ~(err <= atol + rtol * ref.abs())
-    n = int(bad.sum())
-    if n:
-        first = int(bad.flatten().nonzero()[0])
-        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(first), bad.shape))
-        raise AssertionError(f"{msg}: {n}/{bad.numel()} off, first at {idx} of {tuple(bad.shape)}: got {float(got.flatten()[first]):.6g} want {float(ref.flatten()[first]):.6g}, "
-                             f"max err {float(torch.nan_to_num(err, nan=float('inf')).max()):.3e}")
 
 
 # ====================================================================================================== key padding along the walks
@@ -156,21 +120,8 @@ def padded_case(B, H, L):
 def attn_ref(q, k, v, bias, b0, b1):
     """fp64 softmax(q k^T ln 2 + bias) v of batch elements [b0, b1): ctx as [(b1 - b0) * L, H * hd] and lse [b1 - b0, H, L]; q is in log2 units"""
     H, L, hd = q.shape[1:]
-    s = (q[b0:b1].to(F64) @ k[b0:b1].to(F64).transpose(-1, -2)) * LN2
-    if bias is not None:
-        s = s + bias[b0:b1].to(F64)[:, None, None, :]
-    lse = torch.logsumexp(s, -1)
-    p = torch.exp(s - lse[..., None])
-    o = p @ v[b0:b1].to(F64)
+    o, lse = AR.fwd_ref(q[b0:b1], k[b0:b1], v[b0:b1], None if bias is None else bias[b0:b1])
     return o.permute(0, 2, 1, 3).reshape((b1 - b0) * L, H * hd), lse
-
-
-def run_fwd(q, k, v, bias):
-    B, H, L, hd = q.shape
-    ctx = torch.full((B * L, H * hd), float("nan"), dtype=torch.bfloat16, device=DEV)      # an unwritten row shows
-    lse = torch.full((B, H, L), float("nan"), device=DEV)
-    hip.call("oneprot_attn_fwd", q, k, v, bias, ctx, lse, B, H, L, hd)
-    return ctx, lse
 
 
 def check_fwd(outs, q, k, v, bias, extreme=None, tag=""):
@@ -185,37 +136,10 @@ def check_fwd(outs, q, k, v, bias, extreme=None, tag=""):
         gate = lambda g, gx: [torch.where(x, torch.tensor(gx[i], dtype=F64, device=DEV), torch.tensor(g[i], dtype=F64, device=DEV)) for i in range(2)]
         (c_rt, c_at), (l_rt, l_at) = gate(CTX_GATE, CTX_GATE_X), gate(LSE_GATE, LSE_GATE_X)
         for name, ctx, lse in outs:
-            check(ctx[b0 * L:b1 * L].view(b1 - b0, L, H, hd), o_ref.view(b1 - b0, L, H, hd), c_rt[:, None, :, None], c_at[:, None, :, None],
+            close(ctx[b0 * L:b1 * L].view(b1 - b0, L, H, hd), o_ref.view(b1 - b0, L, H, hd), c_rt[:, None, :, None], c_at[:, None, :, None],
                   f"ctx {tag} {name} [b, l, h, d] from b0 = {b0}")
-            check(lse[b0:b1], lse_ref, l_rt[:, :, None], l_at[:, :, None], f"lse {tag} {name} [b, h, l] from b0 = {b0}")
+            close(lse[b0:b1], lse_ref, l_rt[:, :, None], l_at[:, :, None], f"lse {tag} {name} [b, h, l] from b0 = {b0}")
         del o_ref, lse_ref
-
-
-def extreme_rows(q, k, slabs, g):
-    """the construction of test_attention_fwd_nomax_overflow_underflow_net in the flat slabs `slabs` of q / k [B, H, L, hd] (in place): keys 4 u + noise,
-    query row i = alpha_i u + noise, so row i's scores sit near one of -400, -200, 0, 45, 70, 200, 400 (log2 units).  Returns bool [B, H]."""
-    B, H, L, hd = q.shape
-    u = torch.randn(hd, generator=g, device=DEV)
-    u = u / u.norm()
-    kinds = torch.tensor([-400.0, -200.0, 0.0, 45.0, 70.0, 200.0, 400.0], device=DEV)
-    n = len(slabs)
-    alpha = kinds[torch.randint(0, len(kinds), (n, L), generator=g, device=DEV)] / 4.0               # k ~ 4 u, so q = alpha u gives q.k ~ 4 alpha = the kind
-    idx = torch.tensor(slabs, device=DEV)
-    q.view(B * H, L, hd)[idx] = bf(alpha[..., None] * u + 0.3 * torch.randn(n, L, hd, generator=g, device=DEV))
-    k.view(B * H, L, hd)[idx] = bf(u * 4.0 + 0.05 * torch.randn(n, L, hd, generator=g, device=DEV))
-    sc = q.view(B * H, L, hd)[idx].float() @ k.view(B * H, L, hd)[idx].float().transpose(-1, -2)
-    assert float(sc.max()) > 300 and float(sc.min()) < -300
-    is_x = torch.zeros(B * H, dtype=torch.bool, device=DEV)
-    is_x[idx] = True
-    return is_x.view(B, H)
-
-
-def fwd_inputs(B, H, L, hd, seed):
-    g = _gen(seed)
-    q = _randn((B, H, L, hd), g, 0.7 * hip.LOG2E, torch.bfloat16)      # the kernels take q x log2(e) (scores in log2 units)
-    k = _randn((B, H, L, hd), g, 1.0, torch.bfloat16)
-    v = _randn((B, H, L, hd), g, 1.0, torch.bfloat16)
-    return q, k, v
 
 
 class tiles_mode:
@@ -267,7 +191,7 @@ def test_fwd_bench_launch_hd32():
     assert torch.equal(ctx_d2, ctx) and torch.equal(lse_d2, lse), "second launch on the work queues"
     bad = (ctx_s != ctx).view(B, L, H, hd).any(-1).any(1) | (lse_s != lse).any(-1)
     assert not bad.any(), f"{int(bad.sum())} slabs depend on their place in a walk, first (b, h) = {tuple(int(i) for i in bad.nonzero()[0])}"
-    _free()
+    free()
 
 
 @pytest.mark.parametrize("hd", [32, 16])
@@ -288,7 +212,7 @@ def test_fwd_slab_counts_at_the_edges_of_the_decomposition(B, H, hd):
         assert hip.sched_error() == 0
         check_fwd([("static", ctx, lse)], q, k, v, bias, tag=f"B {B} H {H} L {L} hd {hd}")
         assert torch.equal(ctx_d, ctx) and torch.equal(lse_d, lse), f"L {L}: work queues differ from static lists"
-    _free()
+    free()
 
 
 @pytest.mark.parametrize("path", [0, 1, 2])
@@ -317,7 +241,7 @@ def test_fwd_hd64_chunk_stream_across_slabs(B, H, L, nb):
     ctx_s, lse_s = sliced_fwd(q, k, v, bias, nb)
     bad = (ctx_s != ctx).view(B, L, H, hd).any(-1).any(1) | (lse_s != lse).any(-1)
     assert not bad.any(), f"{int(bad.sum())} slabs depend on their place in a walk, first (b, h) = {tuple(int(i) for i in bad.nonzero()[0])}"
-    _free()
+    free()
 
 
 @pytest.mark.parametrize("L,hd", [(400, 64), (512, 64), (512, 32)])
@@ -331,10 +255,10 @@ def test_fwd_extreme_scores_in_chosen_slabs_of_a_walk(L, hd):
     wk = [w for w in walks(B * H, _n_cu()) if len(w) >= 3]
     assert len(wk) >= 3, "B * H = 800 gives every work-group three or four slabs on 256 CUs"
     chosen = sorted({wk[5][1], wk[5][2], wk[len(wk) // 2][-1], wk[-1][1], wk[-3][-1]})
-    g = _gen(3000 + L + hd)
-    q_plain = _randn((B, H, L, hd), g, 0.3, torch.bfloat16)
+    g = gen(3000 + L + hd)
+    q_plain = randn((B, H, L, hd), g, 0.3, dtype=torch.bfloat16)
     k_plain = bf(torch.randn(hd, generator=g, device=DEV) * 0.7 + 0.05 * torch.randn(B, H, L, hd, generator=g, device=DEV))
-    v = _randn((B, H, L, hd), g, 1.0, torch.bfloat16)
+    v = randn((B, H, L, hd), g, 1.0, dtype=torch.bfloat16)
     q, k = q_plain.clone(), k_plain.clone()
     is_x = extreme_rows(q, k, chosen, g)
     assert float((q_plain.view(B * H, L, hd)[:8].float() @ k_plain.view(B * H, L, hd)[:8].float().transpose(-1, -2)).abs().max()) < 40
@@ -347,7 +271,7 @@ def test_fwd_extreme_scores_in_chosen_slabs_of_a_walk(L, hd):
     same = ~((ctx_p != ctx).view(B, L, H, hd).any(-1).any(1) | (lse_p != lse).any(-1))
     assert bool(same[~is_x].all()), f"{int((~same & ~is_x).sum())} ordinary slabs changed by extreme rows elsewhere, first flat slab {int((~same & ~is_x).flatten().nonzero()[0])} (chosen: {chosen})"
     assert not bool(same[is_x].any())
-    _free()
+    free()
 
 
 @pytest.mark.parametrize("B,H", [(10923, 3), (2048, 16)])
@@ -361,38 +285,19 @@ def test_fwd_hd64_at_the_limit_of_the_redo_marks(B, H):
     q, k, v = fwd_inputs(B, H, L, hd, 900 + H)
     wk = walks(B * H, _n_cu())
     chosen = sorted({B * H - 1, wk[3][len(wk[3]) // 2], wk[len(wk) // 2][-1], 6})          # the last slab of the launch: the last word of a set of marks
-    is_x = extreme_rows(q, k, chosen, _gen(901))
+    is_x = extreme_rows(q, k, chosen, gen(901))
     ctx, lse = run_fwd(q, k, v, bias)
     nonfinite = ~(torch.isfinite(ctx.float()).view(B, L, H, hd).all(-1).all(1) & torch.isfinite(lse).all(-1))
     assert not nonfinite.any(), f"non-finite output in flat slabs {nonfinite.flatten().nonzero().flatten().tolist()[:8]} (extreme rows in {chosen})"
     check_fwd([("", ctx, lse)], q, k, v, bias, extreme=is_x, tag=f"hd 64 L 32 B {B} H {H}")
-    _free()
+    free()
 
 
 # ====================================================================================================== B. backward at the bench's slab count
-def _rot_half(x):
-    h = x.shape[-1] // 2
-    return torch.cat((-x[..., h:], x[..., :h]), -1)
-
-
 def bwd_ref(q, k, v, bias, dctx, cos, sin, scale, b0, b1):
-    """fp64 autograd through rotary + scale + softmax for batch elements [b0, b1).  The kernel is handed the rotated, scaled q and the rotated k (bf16); the
-    un-rotated projections they came from are recovered exactly (a rotation is orthogonal), made the leaves, and rotated again inside the graph.
-    cos / sin fp64 [L, hd].  Returns d(q proj), d(k proj), d(v) as [b1 - b0, H, L, hd]."""
-    H, L, hd = q.shape[1:]
-    qr, kr = q[b0:b1].to(F64) / hip.LOG2E, k[b0:b1].to(F64)
-    ql = ((qr * cos - _rot_half(qr) * sin) / scale).requires_grad_(True)
-    kl = (kr * cos - _rot_half(kr) * sin).requires_grad_(True)
-    vl = v[b0:b1].to(F64).requires_grad_(True)
-    qs = ql * scale
-    qs = qs * cos + _rot_half(qs) * sin
-    ks = kl * cos + _rot_half(kl) * sin
-    s = qs @ ks.transpose(-1, -2)
-    if bias is not None:
-        s = s + bias[b0:b1].to(F64)[:, None, None, :]
-    o = torch.softmax(s, -1) @ vl
-    o.backward(dctx[b0 * L:b1 * L].to(F64).view(b1 - b0, L, H, hd).permute(0, 2, 1, 3))
-    return ql.grad, kl.grad, vl.grad
+    """tests/attn_ref.py bwd_ref for batch elements [b0, b1): d(q proj), d(k proj), d(v) as [b1 - b0, H, L, hd]"""
+    L = q.shape[2]
+    return AR.bwd_ref(q[b0:b1], k[b0:b1], v[b0:b1], None if bias is None else bias[b0:b1], dctx[b0 * L:b1 * L], scale, cos, sin)
 
 
 def grad_gates(got, ref, name):
@@ -400,7 +305,7 @@ def grad_gates(got, ref, name):
     got = got.to(F64)
     rel = (got - ref).flatten(2).norm(dim=-1) / (ref.flatten(2).norm(dim=-1) + 1e-20)
     assert bool(torch.isfinite(rel).all()) and float(rel.max()) < 2e-2, f"{name}: rel err {float(torch.nan_to_num(rel, nan=9.9).max()):.3e} in slab {tuple(int(i) for i in (~(rel < 2e-2)).nonzero()[0])}"
-    check(got, ref, 5e-2, 5e-2 * ref.abs().flatten(2).amax(-1)[..., None, None], name)
+    close(got, ref, 5e-2, 5e-2 * ref.abs().flatten(2).amax(-1)[..., None, None], name)
 
 
 def run_bwd_case(B, H, L, hd, seed, path=-1):
@@ -410,10 +315,10 @@ def run_bwd_case(B, H, L, hd, seed, path=-1):
     ctx = torch.empty(B * L, H * hd, dtype=torch.bfloat16, device=DEV)
     lse = torch.empty(B, H, L, device=DEV)
     hip.call("oneprot_attn_fwd", q, k, v, bias, ctx, lse, B, H, L, hd)
-    dctx = _randn((B * L, H * hd), _gen(seed + 1), 1.0, torch.bfloat16)
+    dctx = randn((B * L, H * hd), gen(seed + 1), 1.0, dtype=torch.bfloat16)
     cos, sin = O.rope_tables(L, hd)
     cosd, sind = cos[:, : hd // 2].contiguous().to(DEV), sin[:, : hd // 2].contiguous().to(DEV)
-    w = _ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
+    w = ws(hip.query("oneprot_attn_bwd_workspace", B, H, L))
     outs = []
     hip.query("oneprot_attn_force_bwd_path", path)
     try:
@@ -437,7 +342,7 @@ def run_bwd_case(B, H, L, hd, seed, path=-1):
         for i, name in enumerate(("dq", "dk", "dv")):
             grad_gates(got[b0:b1, :, i].permute(0, 2, 1, 3), refs[i], f"{name} B {B} H {H} L {L} hd {hd} path {path} from b0 = {b0}")
         del refs
-    _free()
+    free()
 
 
 def test_bwd_bench_launch_hd32():
@@ -470,8 +375,8 @@ def gemm_nt(A, W, epi, bias, o0, o1=None, o2=None, aux=None, cos=None, sin=None,
 
 
 def gemm_inputs(M, N, K, seed, wscale=0.1):
-    g = _gen(seed)
-    return _randn((M, K), g, 1.0, torch.bfloat16), _randn((N, K), g, wscale, torch.bfloat16), _randn((N,), g, 0.5)
+    g = gen(seed)
+    return randn((M, K), g, 1.0, dtype=torch.bfloat16), randn((N, K), g, wscale, dtype=torch.bfloat16), randn((N,), g, 0.5)
 
 
 def both_modes(fn):
@@ -500,8 +405,8 @@ def check_bias_gelu(A, W, bias, u, z, u2, A2=None, dz=None, tag=""):
     for r0, r1 in _rows(A.shape[0]):
         zr = A[r0:r1].to(F64) @ W64.t() + b64
         gz, dg = gelu64(zr)
-        check(u[r0:r1], gz, 2 ** -7, 2e-2, f"{tag} gelu(z) rows {r0}")
-        check(u2[r0:r1], gz, 2 ** -7, 2e-2, f"{tag} gelu(z), no derivative, rows {r0}")
+        close(u[r0:r1], gz, 2 ** -7, 2e-2, f"{tag} gelu(z) rows {r0}")
+        close(u2[r0:r1], gz, 2 ** -7, 2e-2, f"{tag} gelu(z), no derivative, rows {r0}")
         zdec = (z[r0:r1].to(F64) - 25.0) / 192.0
         # half a code step (1/384) + the slope of gelu' (<= 0.8) times the bf16-operand error of z itself; exact at the saturated ends
         d = (zdec - dg).abs()
@@ -510,7 +415,7 @@ def check_bias_gelu(A, W, bias, u, z, u2, A2=None, dz=None, tag=""):
         sat = zr.abs() > 6.0
         assert torch.equal(zdec[sat], (zr[sat] > 0).to(F64)), f"{tag} saturated codes rows {r0}"
         if dz is not None:
-            check(dz[r0:r1], (A2[r0:r1].to(F64) @ W64.t()) * zdec, 2 ** -6, 3e-2, f"{tag} gelu bwd rows {r0}")
+            close(dz[r0:r1], (A2[r0:r1].to(F64) @ W64.t()) * zdec, 2 ** -6, 3e-2, f"{tag} gelu bwd rows {r0}")
 
 
 @pytest.mark.parametrize("M", [131072, 131072 + 256])
@@ -519,7 +424,7 @@ def test_gemm_ffn1_gelu_and_its_backward_at_bench_rows(M):
     131328 rows = 513 row panels: whole tiles, work-groups with unequal tile counts"""
     N, K = 2560, 640
     A, W, bias = gemm_inputs(M, N, K, 2100)
-    A2 = _randn((M, K), _gen(2101), 1.0, torch.bfloat16)
+    A2 = randn((M, K), gen(2101), 1.0, dtype=torch.bfloat16)
 
     def run():
         u = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
@@ -532,7 +437,7 @@ def test_gemm_ffn1_gelu_and_its_backward_at_bench_rows(M):
         return u, z, u2, dz
     u, z, u2, dz = both_modes(run)
     check_bias_gelu(A, W, bias, u, z, u2, A2, dz, tag=f"M {M}")
-    _free()
+    free()
 
 
 @pytest.mark.parametrize("M", [131072, 131072 + 256])
@@ -540,7 +445,7 @@ def test_gemm_ffn2_resid_and_bf16_at_bench_rows(M):
     """(N, K) = (640, 2560): BIAS_RESID in place (as the encoder runs it) and BF16"""
     N, K = 640, 2560
     A, W, bias = gemm_inputs(M, N, K, 2200, 0.05)
-    resid = _randn((M, N), _gen(2201))
+    resid = randn((M, N), gen(2201))
 
     def run():
         x = resid.clone()
@@ -552,9 +457,9 @@ def test_gemm_ffn2_resid_and_bf16_at_bench_rows(M):
     W64, b64 = W.to(F64), bias.to(F64)
     for r0, r1 in _rows(M):
         ref = A[r0:r1].to(F64) @ W64.t() + b64
-        check(x[r0:r1], ref + resid[r0:r1].to(F64), 1e-4, 1e-3 * math.sqrt(K / 64), f"bias+resid rows {r0}")
-        check(o[r0:r1], ref, 2 ** -7, 2e-2, f"EPI_BF16 rows {r0}")
-    _free()
+        close(x[r0:r1], ref + resid[r0:r1].to(F64), 1e-4, 1e-3 * math.sqrt(K / 64), f"bias+resid rows {r0}")
+        close(o[r0:r1], ref, 2 ** -7, 2e-2, f"EPI_BF16 rows {r0}")
+    free()
 
 
 def test_gemm_640_by_1920_bf16_at_bench_rows():
@@ -568,8 +473,8 @@ def test_gemm_640_by_1920_bf16_at_bench_rows():
     (o,) = both_modes(run)
     W64 = W.to(F64)
     for r0, r1 in _rows(M):
-        check(o[r0:r1], A[r0:r1].to(F64) @ W64.t(), 2 ** -7, 2e-2, f"EPI_BF16 rows {r0}")
-    _free()
+        close(o[r0:r1], A[r0:r1].to(F64) @ W64.t(), 2 ** -7, 2e-2, f"EPI_BF16 rows {r0}")
+    free()
 
 
 def test_gemm_650m_width_ffn():
@@ -588,7 +493,7 @@ def test_gemm_650m_width_ffn():
     check_bias_gelu(A, W, bias, u, z, u2, tag="650M FFN-1")
     del u, z, u2
     A, W, bias = gemm_inputs(M, 1280, 5120, 2401, 0.035)
-    resid = _randn((M, 1280), _gen(2402))
+    resid = randn((M, 1280), gen(2402))
 
     def run2():
         x = resid.clone()
@@ -597,8 +502,8 @@ def test_gemm_650m_width_ffn():
     (x,) = both_modes(run2)
     W64, b64 = W.to(F64), bias.to(F64)
     for r0, r1 in _rows(M):
-        check(x[r0:r1], A[r0:r1].to(F64) @ W64.t() + b64 + resid[r0:r1].to(F64), 1e-4, 1e-3 * math.sqrt(5120 / 64), f"650M bias+resid rows {r0}")
-    _free()
+        close(x[r0:r1], A[r0:r1].to(F64) @ W64.t() + b64 + resid[r0:r1].to(F64), 1e-4, 1e-3 * math.sqrt(5120 / 64), f"650M bias+resid rows {r0}")
+    free()
 
 
 def test_gemm_qkv_rope_then_attention_at_bench_shape():
@@ -628,13 +533,13 @@ def test_gemm_qkv_rope_then_attention_at_bench_shape():
         b0, b1 = r0 // L, r1 // L
         y = (A[r0:r1].to(F64) @ W64.t() + b64).view(b1 - b0, L, 3, H, hd).permute(2, 0, 3, 1, 4)
         yq = y[0] * q_scale
-        check(q[b0:b1], yq * c64 + _rot_half(yq) * s64, 2 ** -7, 2e-2, f"q from b0 = {b0}")
-        check(k[b0:b1], y[1] * c64 + _rot_half(y[1]) * s64, 2 ** -7, 2e-2, f"k from b0 = {b0}")
-        check(v[b0:b1], y[2], 2 ** -7, 2e-2, f"v from b0 = {b0}")
+        close(q[b0:b1], yq * c64 + rot_half(yq) * s64, 2 ** -7, 2e-2, f"q from b0 = {b0}")
+        close(k[b0:b1], y[1] * c64 + rot_half(y[1]) * s64, 2 ** -7, 2e-2, f"k from b0 = {b0}")
+        close(v[b0:b1], y[2], 2 ** -7, 2e-2, f"v from b0 = {b0}")
     kb = padded_case(B, H, L)
     ctx, lse = run_fwd(q, k, v, kb)
     check_fwd([("after the QKV GEMM", ctx, lse)], q, k, v, kb, tag="chain")
-    _free()
+    free()
 
 
 # ====================================================================================================== D. packed attention per segment
@@ -653,29 +558,19 @@ def packed_lengths(total, seed):
     return [lengths[i] for i in torch.randperm(len(lengths), generator=g).tolist()]
 
 
-def _tables(lengths, T, hd):
-    """per-token rotary tables [T, hd / 2] fp32 (position inside the token's segment; tail: position 0)"""
-    inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))
-    f = torch.outer(torch.arange(1026, dtype=torch.float32), inv)
-    pos = torch.cat([torch.arange(n) for n in lengths] + [torch.zeros(T - sum(lengths), dtype=torch.long)])
-    return f.cos()[pos].contiguous().to(DEV), f.sin()[pos].contiguous().to(DEV)
-
-
 def _packed_case(H, hd, total, t_pad, seed):
     lengths = packed_lengths(total, seed)
     p = PackedTokens.from_list([torch.full((n,), 5, dtype=torch.int64) for n in lengths], t_pad=t_pad).to(DEV)
     T = p.T_pad
-    cu = [0]
-    for n in lengths:
-        cu.append(cu[-1] + n)
-    g = _gen(seed)
+    cu = cu_of(lengths)
+    g = gen(seed)
     scale = hd ** -0.5
-    cosd, sind = _tables(lengths, T, hd)
+    cosd, sind = (t.to(DEV) for t in gathered_tables(lengths, T, hd))
     c, s = torch.cat([cosd, cosd], -1), torch.cat([sind, sind], -1)
-    q0, k0 = _randn((H, T, hd), g), _randn((H, T, hd), g)
-    q = bf((q0 * c + _rot_half(q0) * s) * (scale * hip.LOG2E * 3.0))                  # (x 3: scores of a few units, as a trained tower has)
-    k = bf(k0 * c + _rot_half(k0) * s)
-    v = _randn((H, T, hd), g, 1.0, torch.bfloat16)
+    q0, k0 = randn((H, T, hd), g), randn((H, T, hd), g)
+    q = bf((q0 * c + rot_half(q0) * s) * (scale * hip.LOG2E * 3.0))                  # (x 3: scores of a few units, as a trained tower has)
+    k = bf(k0 * c + rot_half(k0) * s)
+    v = randn((H, T, hd), g, 1.0, dtype=torch.bfloat16)
     return p, lengths, cu, T, q, k, v, cosd, sind, scale
 
 
@@ -687,7 +582,7 @@ def varlen_fwd(p, work, q, k, v, T, H, hd):
 
 
 def varlen_bwd(p, work, q, k, v, ctx, dctx, lse, cosd, sind, scale, T, H, hd):
-    w = _ws(hip.query("oneprot_attn_varlen_bwd_workspace", H, T))
+    w = ws(hip.query("oneprot_attn_varlen_bwd_workspace", H, T))
     dqkv = torch.full((T, 3 * H * hd), float("nan"), dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_attn_varlen_bwd", q, k, v, p.cu_seqlens, work, work.shape[0], ctx, dctx, lse, cosd, sind, scale, dqkv, w, len(p), T, H, hd)
     return dqkv
@@ -724,7 +619,7 @@ def test_packed_attention_per_segment(H, hd, total, t_pad):
     ctx, lse = varlen_fwd(p, work, q, k, v, T, H, hd)
     assert bool((ctx[n_real:] == 0).all()) and bool((lse[:, n_real:] == 0).all()), "tail rows of the forward"
     assert torch.isfinite(ctx[:n_real].float()).all() and torch.isfinite(lse[:, :n_real]).all()
-    dctx = _randn((T, H * hd), _gen(77), 1.0, torch.bfloat16)
+    dctx = randn((T, H * hd), gen(77), 1.0, dtype=torch.bfloat16)
     dctx[n_real:] = 0
     dqkv = varlen_bwd(p, work, q, k, v, ctx, dctx, lse, cosd, sind, scale, T, H, hd)
     assert torch.equal(dqkv, varlen_bwd(p, work, q, k, v, ctx, dctx, lse, cosd, sind, scale, T, H, hd)), "two launches of the packed backward differ"
@@ -737,22 +632,15 @@ def test_packed_attention_per_segment(H, hd, total, t_pad):
     c64, s64 = torch.cat([cosd, cosd], -1).to(F64), torch.cat([sind, sind], -1).to(F64)
     refs = [torch.zeros(H, T, hd, dtype=F64, device=DEV) for _ in range(3)]
     for a, n in zip(cu[:-1], lengths):
-        cs, sn = c64[a:a + n], s64[a:a + n]
-        qr, kr = q[:, a:a + n].to(F64) / hip.LOG2E, k[:, a:a + n].to(F64)
-        ql = ((qr * cs - _rot_half(qr) * sn) / scale).requires_grad_(True)
-        kl = (kr * cs - _rot_half(kr) * sn).requires_grad_(True)
-        vl = v[:, a:a + n].to(F64).requires_grad_(True)
-        qs = ql * scale
-        sc = (qs * cs + _rot_half(qs) * sn) @ (kl * cs + _rot_half(kl) * sn).transpose(1, 2)
-        o = torch.softmax(sc, -1) @ vl
+        qkv = [x[None, :, a:a + n] for x in (q, k, v)]                     # the segment as a batch of one
+        o, lse64 = AR.fwd_ref(*qkv, None)
         got = ctx[a:a + n].to(F64).view(n, H, hd).transpose(0, 1)
-        e = float((got - o.detach()).abs().max())
+        e = float((got - o[0]).abs().max())
         assert e < 3e-2, f"ctx of the segment at {a} ({n} tokens): {e:.3e}"
-        e = float((lse[:, a:a + n].to(F64) - torch.logsumexp(sc.detach(), -1)).abs().max())
+        e = float((lse[:, a:a + n].to(F64) - lse64[0]).abs().max())
         assert e < 1e-2, f"lse of the segment at {a} ({n} tokens): {e:.3e}"
-        o.backward(dctx[a:a + n].to(F64).view(n, H, hd).transpose(0, 1))
-        for r, gr in zip(refs, (ql.grad, kl.grad, vl.grad)):
-            r[:, a:a + n] = gr
+        for r, gr in zip(refs, AR.bwd_ref(*qkv, None, dctx[a:a + n], scale, c64[a:a + n], s64[a:a + n])):
+            r[:, a:a + n] = gr[0]
     dm = H * hd
     for i, name in enumerate(("dq", "dk", "dv")):
         got = dqkv[:, i * dm:(i + 1) * dm].view(T, H, hd).transpose(0, 1)
@@ -763,4 +651,4 @@ def test_packed_attention_per_segment(H, hd, total, t_pad):
             else:
                 e = float((got[:, a:a + n].to(F64) - refs[i][:, a:a + n]).abs().max())
                 assert e < 0.05 * stream_max, f"{name} of the segment at {a} ({n} tokens): {e:.3e}"
-    _free()
+    free()

@@ -17,6 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests.gate import cos_sim  # noqa: E402
 
 DEV = "cuda"
 CFG150 = dict(layers=30, hidden=640, heads=20, ffn=2560, pad=1, mask=32, eps=1e-5)
@@ -25,11 +26,6 @@ CFG_BERT = dict(layers=12, hidden=768, heads=12, ffn=3072, vocab=30522, max_pos=
 SPEC_SEQ = dict(kind="esm", pooling="mean", proj_type="mlp", use_logit_scale=False)
 SPEC_ST = dict(kind="esm", pooling="mean", proj_type="linear", use_logit_scale=True)
 SPEC_TXT = dict(kind="bert", pooling="cls", proj_type="mlp", use_logit_scale=True)
-
-
-def _cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
 
 
 def _env():
@@ -88,9 +84,9 @@ def _check_arena_grads(got, ref_grads, pref, whole=0.9999, per_tensor=0.999):
     assert len(keys) > 50, len(keys)
     allg = torch.cat([got[k].flatten() for k in keys])
     allr = torch.cat([ref_grads[pref + "transformer." + k].flatten() for k in keys])
-    c = _cos(allg, allr)
+    c = cos_sim(allg, allr)
     big = max(float(ref_grads[pref + "transformer." + k].norm()) for k in keys)
-    table = sorted((_cos(got[k], ref_grads[pref + "transformer." + k]), float(ref_grads[pref + "transformer." + k].norm()) / big, k) for k in keys)
+    table = sorted((cos_sim(got[k], ref_grads[pref + "transformer." + k]), float(ref_grads[pref + "transformer." + k].norm()) / big, k) for k in keys)
     worst = "; ".join(f"{k}: cos {cs:.5f} share {sh:.3f}" for cs, sh, k in table[:6])
     assert c > whole, f"whole-gradient cosine {c} (worst tensors: {worst})"
     for cs, sh, k in table:
@@ -378,10 +374,10 @@ def test_cfg4_shape_150m_vs_bert_base_substep_vs_oracle(frozen_text):
                  for k, p_ in module.network[name].proj.named_parameters()]
         big = max(float(r.norm()) for _, _, _, r in pairs)
         for name, k, got, r in pairs:
-            assert _cos(got, r) > (0.999 if float(r.norm()) >= 0.01 * big else 0.99), (name, k, _cos(got, r), float(r.norm()), big)
+            assert cos_sim(got, r) > (0.999 if float(r.norm()) >= 0.01 * big else 0.99), (name, k, cos_sim(got, r), float(r.norm()), big)
         # 4 pairs with the logits scaled by 14.29: d loss / d logits = softmax - onehot amplifies the bf16 feature error (1 - cos ~ 2e-5) into
         # ~2 % of the head gradient; the 0.9999 gate belongs to the cfg-2 test, whose gradient is dominated by the transformer
-        assert _cos(torch.cat([g_.flatten() for _, _, g_, _ in pairs]), torch.cat([r.flatten() for _, _, _, r in pairs])) > 0.999
+        assert cos_sim(torch.cat([g_.flatten() for _, _, g_, _ in pairs]), torch.cat([r.flatten() for _, _, _, r in pairs])) > 0.999
     else:
         # cls pooling: the whole gradient of the text tower enters through ONE token per sequence, 4 sequences, logits x14.29 (see above)
         _check_arena_grads(grads["text"], ref["grads"], "mod.", whole=0.999, per_tensor=0.995)
@@ -455,7 +451,7 @@ def test_cfg5_shape_650m_width_anchor_vs_oracle(tmp_path):
     _check_arena_grads(grads["struct_token"], ref["grads"], "mod.")
     # the pooling convolution is a trainable leaf outside the frozen transformer (reference: only `transformer` is frozen, sequence_encoder.py:57-59)
     r = ref["grads"]["seq.pooling.layer.weight"]
-    assert _cos(seq.pooling.layer.weight.grad.cpu(), r) > 0.999
+    assert cos_sim(seq.pooling.layer.weight.grad.cpu(), r) > 0.999
 
 
 def test_cfg2_full_size_substep_properties():
@@ -506,7 +502,7 @@ def test_cfg2_full_size_substep_properties():
     assert l1 == l2 and g1 == g2 and torch.equal(f1, f2), (l1, l2, g1, g2)                    # bit-reproducible
     l3, g3, f3 = one(0)                                                                          # split attention backward
     assert l3 == l1, (l1, l3)
-    assert abs(g3 - g1) / g1 < 1e-3 and _cos(f1, f3) > 0.99999, (g1, g3, _cos(f1, f3))
+    assert abs(g3 - g1) / g1 < 1e-3 and cos_sim(f1, f3) > 0.99999, (g1, g3, cos_sim(f1, f3))
 
 
 def test_cfg5_full_depth_650m_anchor_properties():
@@ -556,7 +552,7 @@ def test_cfg5_full_depth_650m_anchor_properties():
     assert math.isfinite(l1) and abs(l1 - math.log(B)) < 1.0, l1
     assert l1 == l2 and g1 == g2 and torch.equal(f1, f2), (l1, l2, g1, g2)
     l3, g3, f3 = one(0)
-    assert l3 == l1 and abs(g3 - g1) / g1 < 1e-3 and _cos(f1, f3) > 0.99999, (l1, l3, g1, g3, _cos(f1, f3))
+    assert l3 == l1 and abs(g3 - g1) / g1 < 1e-3 and cos_sim(f1, f3) > 0.99999, (l1, l3, g1, g3, cos_sim(f1, f3))
     assert seq.pooling.layer.weight.grad is not None and seq.transformer.flat.grad is None      # only the pooling conv + head of the frozen anchor train
 
 

@@ -19,7 +19,7 @@ import torch
 from oneprot_amd import gbt, hip
 from tests import gbt_cases as C
 from tests import gbt_ref as R
-from tests.test_gbt_gpu import DEV, FACTOR, MEASURED, assert_same_trees, cuts_of, dev, fit_device, hist_reference, run_grad, run_hist
+from tests.gbt_cases import DEV, FACTOR, MEASURED, assert_same_trees, cuts_of, dev, fit_device, hist_reference, run_grad, run_hist
 
 pytestmark = pytest.mark.gpu
 ONE = 1 << R.FRAC

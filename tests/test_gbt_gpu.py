@@ -15,25 +15,9 @@ import torch
 from oneprot_amd import gbt, hip
 from tests import gbt_cases as C
 from tests import gbt_ref as R
+from tests.gbt_cases import DEV, FACTOR, MEASURED, assert_same_trees, cuts_of, dev, fit_device, hist_reference, run_grad, run_hist
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-# largest |device margin - restatement margin| over the rounds of every end-to-end fixture, measured on an MI355X (printed by the tests with -s); the
-# regression fixture has no exp in its chain and every operation of it is a single IEEE fp32 operation on both sides: it is exact
-MEASURED = {"logistic": 1.192e-7, "squared": 0.0, "softmax": 2.384e-7, "multilabel": 2.384e-7, "sampled": 3.576e-7}       # 1, 0, 2, 2 and 3 x 2^-23
-FACTOR = 16.0
-
-
-def dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a))
-    return t.to(DEV, dtype).contiguous() if dtype is not None else t.to(DEV).contiguous()
-
-
-def cuts_of(cuts, ncuts):
-    cuts, ncuts = cuts.cpu().numpy(), ncuts.cpu().numpy()
-    return [cuts[f, :ncuts[f]] for f in range(len(ncuts))]
-
-
 # ================================================================================================================== cuts / bins
 def special_columns(X, rng):
     """a constant column, a column of 3 distinct values, a column of +-0.0 and values around them -- wherever the matrix is wide enough"""
@@ -66,19 +50,6 @@ def test_cuts_and_bins_exact(B):
 
 
 # ================================================================================================================== gradients
-def run_grad(m, y, objective, keep=None):
-    N, K = m.shape
-    md = dev(m, torch.float32)
-    keep = np.ones(N, dtype=np.uint8) if keep is None else keep.astype(np.uint8)
-    gq, hq = (torch.empty(K, N, dtype=torch.int32, device=DEV) for _ in range(2))
-    expo, gmax = torch.empty(K, dtype=torch.int32, device=DEV), torch.empty(1, dtype=torch.int32, device=DEV)
-    if objective == R.SOFTMAX:
-        hip.call("oneprot_gbt_grad", md, None, dev(y, torch.int32), dev(keep), gq, hq, expo, gmax, N, K, 2)
-    else:
-        hip.call("oneprot_gbt_grad", md, dev(y.reshape(N, K), torch.float32), None, dev(keep), gq, hq, expo, gmax, N, K, gbt.OBJECTIVES[objective])
-    return gq, hq, expo
-
-
 def test_gradients_at_the_extremes():
     """|g| = 1 with h = 0 (a saturated logistic), a regression round whose max |g| is 3e4 and another at 1e-6; dropped rows are 0; exact integers"""
     rng = np.random.default_rng(5)
@@ -120,30 +91,6 @@ def node_layout(N, level, rng):
     if N >= 16:
         pos[rng.random(N) < 0.1] = max(base - 1, 0) if level else 5          # rows that stopped at a leaf above (or sit elsewhere): not of this level
     return pos
-
-
-def hist_reference(bins, gq, hq, pos, level, B):
-    """int64 [K, L, F, B, 2]: every (row, feature) adds its row's integers at (node, feature, bin) -- one np.add.at per output and component"""
-    K, (N, F) = gq.shape[0], bins.shape
-    L, base = 1 << level, (1 << level) - 1
-    out = np.zeros((K, L, F, B, 2), dtype=np.int64)
-    for k in range(K):
-        rows = np.nonzero((pos[k] >= base) & (pos[k] < base + L))[0]
-        flat = ((pos[k][rows, None].astype(np.int64) - base) * F + np.arange(F)[None, :]) * B + bins[rows].astype(np.int64)
-        for c, q in enumerate((gq[k], hq[k])):
-            acc = np.zeros(L * F * B, dtype=np.int64)
-            np.add.at(acc, flat.reshape(-1), np.repeat(q[rows], F))
-            out[k, ..., c] = acc.reshape(L, F, B)
-    return out
-
-
-def run_hist(bins, gq, hq, pos, level, B):
-    K, N = gq.shape
-    F = bins.shape[1]
-    hist = torch.full((K, 1 << level, F, B, 2), -7, dtype=torch.int64, device=DEV)       # overwritten, not accumulated
-    assert hip.query("oneprot_gbt_hist_bytes", F, B, level) * K == hist.numel() * 8
-    hip.call("oneprot_gbt_hist", bins, gq, hq, pos, hist, N, F, B, level, K)
-    return hist
 
 
 @pytest.mark.parametrize("level", [0, 2, 5])
@@ -304,28 +251,6 @@ def test_split_corner_cases():
 
 
 # ================================================================================================================== partition / leaf / predict, end to end
-def fit_device(name, **over):
-    X, y = C.data(name)
-    objective = C.FIXTURES[name][0]
-    kw = dict(C.PARAMS, objective=objective)
-    if name == "sampled":
-        kw.update(subsample=C.SAMPLE_RATE, colsample_bytree=C.SAMPLE_RATE, random_state=C.SAMPLE_SEED)
-    kw.update(over)
-    cls = gbt.XGBRegressor if objective == R.SQUARED else gbt.XGBClassifier
-    return cls(**kw).fit(X, y), X, y
-
-
-def assert_same_trees(model, ref, label):
-    s = {k: v.cpu().numpy() for k, v in model.state_dict().items()}
-    for t, rnd in enumerate(ref["trees"]):
-        for k, tr in enumerate(rnd):
-            assert np.array_equal(s["tree_feat"][t, k], tr["feat"]), (label, t, k, s["tree_feat"][t, k], tr["feat"])
-            split = tr["feat"] >= 0
-            assert np.array_equal(s["tree_bin"][t, k][split], tr["bin"][split]) and np.array_equal(s["tree_thr"][t, k][split], tr["thr"][split]), (label, t, k)
-    got = cuts_of(model._state["cuts"], model._state["ncuts"])
-    assert all(np.array_equal(a, b) for a, b in zip(got, ref["cuts"]))
-
-
 @pytest.mark.parametrize("name", ["logistic", "squared", "softmax", "multilabel", "sampled"])
 def test_end_to_end_against_the_restatement(name):
     """tree structure exactly the restatement's; the final margin within 16 x the measured rounding difference; predict_margin of the training rows bit-equal to

@@ -12,9 +12,7 @@ bf16 outputs rtol 2^-7 / atol 2e-2, fp32 outputs rtol 1e-4 / atol 1e-3 sqrt(K / 
 sgemm is an fp32 fmaf chain and gets the dot-product bound |C - ref| <= (K + 2) u (|alpha| |A| |B| + |C_in|), u = 2^-24 (K roundings of the
 chain, one of alpha * acc, one of the add to C; holds for any summation order)."""
 import functools
-import json
 import math
-import os
 
 import numpy as np
 import pytest
@@ -25,34 +23,14 @@ pytestmark = pytest.mark.gpu
 from oneprot_amd import hip  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
 from tests import gemm_forms  # noqa: E402
+from tests.cases import bf, esm_dir, f64, nans  # noqa: E402
+from tests.gate import close  # noqa: E402
 from tests.philox_ref import dropout_threshold, philox_keep  # noqa: E402
 
 DEV = "cuda"
 NAN = float("nan")
 BF = torch.bfloat16
 GUARD_ROWS = 64
-
-
-def bf(x):
-    return x.to(BF)
-
-
-def f64(x):
-    return x.detach().cpu().double()
-
-
-def assert_close(a, ref, rtol, atol, msg=""):
-    """|a - ref| <= atol + rtol |ref| elementwise against an fp64 CPU reference; `atol` may be a tensor.  NaN in `a` fails."""
-    a = f64(a)
-    assert a.shape == ref.shape, f"{msg}: shape {tuple(a.shape)} vs {tuple(ref.shape)}"
-    err = (a - ref).abs()
-    bad = ~(err <= atol + rtol * ref.abs())
-    assert not bad.any(), (f"{msg}: {int(bad.sum())}/{bad.numel()} off ({int(torch.isnan(a).sum())} NaN), max err {float(err[~torch.isnan(err)].max()) if (~torch.isnan(err)).any() else NAN:.3e} "
-                           f"(ref max {float(ref.abs().max()):.3e})")
-
-
-def nans(*shape, dtype=torch.float32):
-    return torch.full(shape, NAN, dtype=dtype, device=DEV)
 
 
 def tol_f32(K):
@@ -119,10 +97,10 @@ def test_gemm_nt_narrow(M, N, K, gemm_shape):
     Ad, Wd, bd = A.to(DEV), W.to(DEV), bias.to(DEV)
     out = nans(M, N, dtype=BF)
     gemm_nt(Ad, Wd, M, N, K, K, K, hip.EPI_BF16, None, out)                  # as the host calls it: no bias
-    assert_close(out, ref, *TOL_BF16, "EPI_BF16")
+    close(out, ref, *TOL_BF16, "EPI_BF16")
     outf = nans(M, N)
     gemm_nt(Ad, Wd, M, N, K, K, K, hip.EPI_F32, bd, outf)                    # the bias read at the gn < N edge
-    assert_close(outf, ref + bias.double(), *tol_f32(K), "EPI_F32 + bias")
+    close(outf, ref + bias.double(), *tol_f32(K), "EPI_F32 + bias")
 
 
 # ====================================================================================================== 2. NT GEMM with strides
@@ -141,10 +119,10 @@ def test_gemm_nt_strided(M, N, K, lda, ldb, off, gemm_shape):
     As, Ws, bd = strided(A, lda, off), strided(W, ldb), bias.to(DEV)
     out = nans(M, N, dtype=BF)
     gemm_nt(As, Ws, M, N, K, lda, ldb, hip.EPI_BF16, bd, out)
-    assert_close(out, ref + bias.double(), *TOL_BF16, "EPI_BF16, strided")
+    close(out, ref + bias.double(), *TOL_BF16, "EPI_BF16, strided")
     x = resid.to(DEV, copy=True)
     gemm_nt(As, Ws, M, N, K, lda, ldb, hip.EPI_BIAS_RESID, bd, x, aux=x)      # in place, as the layers run it
-    assert_close(x, ref + bias.double() + resid.double(), *tol_f32(K), "EPI_BIAS_RESID in place, strided")
+    close(x, ref + bias.double() + resid.double(), *tol_f32(K), "EPI_BIAS_RESID in place, strided")
 
 
 def _ln_case(M, N, K, seed):
@@ -179,10 +157,10 @@ def test_gemm_resid_ln_strided():
     for name, a, b in zip(("x", "h", "mean", "rstd"), *outs):
         assert torch.equal(a, b), f"{name}: strided call differs from the dense call"
     x, h, mean, rs = outs[0]
-    assert_close(x, xr, *tol_f32(K), "x = A W^T + bias + resid")
-    assert_close(mean, mu, 1e-4, 1e-4 * math.sqrt(K / 64), "mean")
-    assert_close(rs, rstd, 1e-3, 1e-5, "rstd")
-    assert_close(h, hr, *TOL_BF16, "h = LayerNorm(x)")
+    close(x, xr, *tol_f32(K), "x = A W^T + bias + resid")
+    close(mean, mu, 1e-4, 1e-4 * math.sqrt(K / 64), "mean")
+    close(rs, rstd, 1e-3, 1e-5, "rstd")
+    close(h, hr, *TOL_BF16, "h = LayerNorm(x)")
 
 
 def test_gemm_resid_ln8_strided():
@@ -201,10 +179,10 @@ def test_gemm_resid_ln8_strided():
     for name, a, b in zip(("x", "h", "stats"), *outs):
         assert torch.equal(a, b), f"{name}: strided call differs from the dense call"
     x, h, st = outs[0]
-    assert_close(x, xr, 2e-5, 3e-4, "x_out")
-    assert_close(h, hr, 2 ** -7, 4e-3, "h")
-    assert_close(st[0], mu, 1e-5, 1e-4, "mean")
-    assert_close(st[1], rstd, 1e-4, 0.0, "rstd")
+    close(x, xr, 2e-5, 3e-4, "x_out")
+    close(h, hr, 2 ** -7, 4e-3, "h")
+    close(st[0], mu, 1e-5, 1e-4, "mean")
+    close(st[1], rstd, 1e-4, 0.0, "rstd")
 
 
 # ====================================================================================================== 3. TN GEMM, narrow and strided
@@ -239,14 +217,14 @@ def test_gemm_tn_narrow_and_strided(M, N, K, ldy, ldx, off, tn_variant):
         dW = nans(N, K)
         db = nans(N) if with_db else None
         hip.call("oneprot_gemm_bf16_tn", dYs, Xs, M, N, K, ldy, ldx, dW, db, w, need, 0)
-        assert_close(dW, ref, rtol, atol, f"dW, dbias {with_db}")
+        close(dW, ref, rtol, atol, f"dW, dbias {with_db}")
         first, first_db = f64(dW), (f64(db) if with_db else None)
         if with_db:
-            assert_close(db, cs, 1e-4, 1e-2, "fused bias gradient")
+            close(db, cs, 1e-4, 1e-2, "fused bias gradient")
         hip.call("oneprot_gemm_bf16_tn", dYs, Xs, M, N, K, ldy, ldx, dW, db, w, need, 1)
-        assert_close(dW, first + ref, rtol, atol, f"dW accumulated, dbias {with_db}")
+        close(dW, first + ref, rtol, atol, f"dW accumulated, dbias {with_db}")
         if with_db:
-            assert_close(db, first_db + cs, 1e-4, 1e-2, "bias gradient accumulated")
+            close(db, first_db + cs, 1e-4, 1e-2, "bias gradient accumulated")
     assert bool((w[need:] == 0xA5).all()), "wrote past the workspace"
 
 
@@ -267,7 +245,7 @@ def _sgemm_check(M, N, K, tA, bkn, alpha, accumulate, seed=7):
     cin = C0.double() if accumulate else torch.zeros(M, N, dtype=torch.float64)
     ref = alpha32 * (A.double() @ Bm.double()) + cin
     bound = (K + 2) * U32 * (abs(alpha32) * (A.double().abs() @ Bm.double().abs()) + cin.abs())
-    assert_close(C, ref, 0.0, bound, f"sgemm {M}x{N}x{K} tA {tA} b_is_kn {bkn} alpha {alpha} accumulate {accumulate}")
+    close(C, ref, 0.0, bound, f"sgemm {M}x{N}x{K} tA {tA} b_is_kn {bkn} alpha {alpha} accumulate {accumulate}")
 
 
 LAYOUTS = [(0, 0), (0, 1), (1, 1), (1, 0)]
@@ -303,14 +281,6 @@ def test_sgemm_production_calls(M, N, K, tA, bkn, alpha, accumulate):
 
 
 # ====================================================================================================== 5. one layer's adapter branch
-def _esm_dir(tmp, name, layers, hidden, heads, ffn):
-    path = os.path.join(str(tmp), name)
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(dict(model_type="esm", vocab_size=33, hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=ffn), f)
-    return path
-
-
 @pytest.mark.parametrize("hidden,r", [(320, 4), (320, 12), (640, 8)])      # rp = 8, 16, 8; Kc = 384, 384, 768
 def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
     """The chain of esm.py's two-branch LoRA form for one layer -- dropout, down-projection, the K-concatenated QKV operand, du, dB, dA, the masked
@@ -321,7 +291,7 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
     torch.manual_seed(31)
     d, T, p_, i, call, n_layers = hidden, 576, 0.25, 1, 5, 2
     alpha = 3 * r // 2                                                     # scaling 1.5
-    enc = SequenceEncoder(_esm_dir(tmp_path, "esm", n_layers, d, 20, 2 * d), output_dim=128, pooling_type="mean", proj_type="linear", use_lora=True, lora_r=r,
+    enc = SequenceEncoder(esm_dir(tmp_path, "esm", n_layers, d, 20, 2 * d), output_dim=128, pooling_type="mean", proj_type="linear", use_lora=True, lora_r=r,
                           lora_alpha=alpha, lora_dropout=p_).to(DEV).train()
     tr = enc.transformer
     with torch.no_grad():
@@ -372,7 +342,7 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
     assert float(Xc[:, d + Rp:].float().abs().max()) == 0.0
     uc = u.cpu()
     for ti in range(3):
-        assert_close(uc[:, ti * rp:ti * rp + r], hdrop[ti].double() @ a16[i, ti].double().t(), *TOL_BF16, f"u of target {ti}")
+        close(uc[:, ti * rp:ti * rp + r], hdrop[ti].double() @ a16[i, ti].double().t(), *TOL_BF16, f"u of target {ti}")
         if rp > r:
             assert float(uc[:, ti * rp + r:(ti + 1) * rp].float().abs().max()) == 0.0, "pad columns of u"
 
@@ -381,10 +351,10 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
     two = h.double() @ W16[i].double().t()
     for ti in range(3):
         two[:, ti * d:(ti + 1) * d] += uc[:, ti * rp:ti * rp + r].double() @ b16[i, ti].double().t()
-    assert_close(cat, two, 1e-12, 1e-9, "concatenated operands against the two branches (fp64)")
+    close(cat, two, 1e-12, 1e-9, "concatenated operands against the two branches (fp64)")
     y = nans(T, 3 * d)
     gemm_nt(Xc, ops["Wc"][i], T, 3 * d, Kc, Kc, Kc, hip.EPI_F32, None, y)
-    assert_close(y, cat, *tol_f32(Kc), "kernel product at K = Kc")
+    close(y, cat, *tol_f32(Kc), "kernel product at K = Kc")
 
     # ---- backward
     dq = bf(torch.randn(T, 3 * d, generator=g) * 0.5)
@@ -394,7 +364,7 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
     du = nans(T, Rp, dtype=BF)      # the same launch as _lora_branch_backward's first: its own bf16 intermediate
     gemm_nt(dqd, ops["BsT"][i], T, Rp, 3 * d, 3 * d, 3 * d, hip.EPI_BF16, None, du)
     duc = du.cpu()
-    assert_close(duc, dq.double() @ BsT[i].double().t(), *TOL_BF16, "du = dqkv (s B)")
+    close(duc, dq.double() @ BsT[i].double().t(), *TOL_BF16, "du = dqkv (s B)")
     terms = []                       # mask_t * (du_t A_t) / keep from the kernel's own bf16 du_t A_t
     for ti in range(3):
         if rp > r:
@@ -402,7 +372,7 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
         dut = du[:, ti * rp:(ti + 1) * rp].contiguous()
         dhd = nans(T, d, dtype=BF)
         gemm_nt(dut, ops["AtT"][i, ti], T, d, rp, rp, rp, hip.EPI_BF16, None, dhd)
-        assert_close(dhd, duc[:, ti * rp:(ti + 1) * rp].double() @ AtT[i, ti].double().t(), *TOL_BF16, f"du_t A_t of target {ti}")
+        close(dhd, duc[:, ti * rp:(ti + 1) * rp].double() @ AtT[i, ti].double().t(), *TOL_BF16, f"du_t A_t of target {ti}")
         terms.append(torch.where(keep[ti], f64(dhd) * float(scale), torch.zeros((), dtype=torch.float64)))
     inc = sum(terms)
     mag = dh0.double().abs() + sum(t.abs() for t in terms)
@@ -412,16 +382,16 @@ def test_lora_two_branch_layer_stage_by_stage(hidden, r, tmp_path, monkeypatch):
         dh = (dh0 if form == "dh16" else dh0.float()).to(DEV, copy=True)
         tr._lora_branch_backward(i, hd_, u, dqd, T, call, ws_tn, raw, **{form: dh})
         assert bool(torch.isnan(raw[0][1 - i]).all()) and bool(torch.isnan(raw[1][1 - i]).all()), "another layer's gradients were touched"
-        assert_close(raw[1][i], dq.double().t() @ uc.double(), *tol_tn(T), "dB_raw = dqkv^T u")
+        close(raw[1][i], dq.double().t() @ uc.double(), *tol_tn(T), "dB_raw = dqkv^T u")
         for ti in range(3):
             rows = raw[0][i, ti * rp:(ti + 1) * rp]
-            assert_close(rows, duc[:, ti * rp:(ti + 1) * rp].double().t() @ hdrop[ti].double(), *tol_tn(T), f"dA_raw rows of target {ti}")
+            close(rows, duc[:, ti * rp:(ti + 1) * rp].double().t() @ hdrop[ti].double(), *tol_tn(T), f"dA_raw rows of target {ti}")
             if rp > r:
                 assert float(rows[r:].abs().max()) == 0.0, "pad rows of dA_raw"
         # three sequential adds; every partial sum is at most `mag` in size and is rounded to the gradient's format (unit roundoff 2^-8 for bf16: 8 significand bits,
         # 2^-24 for fp32), the fp32 product and add inside each step contribute 2 * 2^-24 more: |error| <= ((1 + e)^3 - 1) mag
         e = (2.0 ** -8 if form == "dh16" else 2.0 ** -24) + 2 * 2.0 ** -24
-        assert_close(dh, dh0.double() + inc, 0.0, ((1 + e) ** 3 - 1) * mag + 1e-30, f"{form} += sum_t mask_t (du_t A_t) / keep")
+        close(dh, dh0.double() + inc, 0.0, ((1 + e) ** 3 - 1) * mag + 1e-30, f"{form} += sum_t mask_t (du_t A_t) / keep")
         raws.append(raw)
     assert torch.equal(raws[0][0][i], raws[1][0][i]) and torch.equal(raws[0][1][i], raws[1][1][i])
 
@@ -458,4 +428,4 @@ def test_gemm_qkv_rope_short_sequences(B, L, H, hd, K, gemm_shape):
     gemm_nt(A.to(DEV), W.to(DEV), M, N, K, K, K, hip.EPI_QKV_ROPE, bias.to(DEV), q, k, v, None, cosh.to(DEV), sinh.to(DEV), hd ** -0.5, L, H, hd)
     for name, b, ref in (("q", bufs[0], qr), ("k", bufs[1], kr), ("v", bufs[2], vr)):
         assert bool(torch.isnan(b[:G]).all()) and bool(torch.isnan(b[G + n:]).all()), f"{name}: wrote outside the output"
-        assert_close(b[G:G + n].view(B, H, L, hd), ref, *TOL_BF16, name)
+        close(b[G:G + n].view(B, H, L, hd), ref, *TOL_BF16, name)

@@ -2,7 +2,8 @@
 functions where the op is composite).  Runs on the MI355X only (-m gpu); all calls go through the C ABI.
 
 Tolerances: fp32 kernels 1e-5-ish; bf16-operand MFMA kernels are compared against an fp32 reference computed from the
-SAME bf16-rounded inputs, so the only difference is accumulation order / output rounding (bf16 outputs: 2^-8 rel)."""
+SAME bf16-rounded inputs, so the only difference is accumulation order / output rounding (bf16 outputs: 2^-8 rel).
+Every comparison runs in fp64 through tests/gate.py (a NaN on either side fails); the attention reference is the fp64 tests/attn_ref.py."""
 import math
 
 import pytest
@@ -13,28 +14,9 @@ pytestmark = pytest.mark.gpu
 from oneprot_amd import hip  # noqa: E402
 from oracle import oneprot_oracle as O  # noqa: E402
 from tests import gemm_forms  # noqa: E402
-
-DEV = "cuda"
-
-
-def bf(x):
-    return x.to(torch.bfloat16)
-
-
-def rel_err(a, b):
-    return ((a.float() - b.float()).norm() / (b.float().norm() + 1e-20)).item()
-
-
-def assert_close(a, b, rtol, atol, msg=""):
-    a, b = a.float(), b.float()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    bad = (err > tol)
-    assert not bad.any(), f"{msg}: {int(bad.sum())}/{bad.numel()} off, max err {err.max().item():.3e} (ref max {b.abs().max().item():.3e})"
-
-
-def ws(nbytes):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=DEV)
+from tests.attn_ref import fwd_ref  # noqa: E402
+from tests.cases import DEV, bf, ws  # noqa: E402
+from tests.gate import close, rel_l2  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -57,13 +39,13 @@ def test_embed_fwd_bwd(B, L, d, vocab):
     hip.call("oneprot_esm_embed_fwd", idd, Wd, x, rs, B, L, d, vocab, 1, 32, 1)
     Wr = W.clone().requires_grad_(True)
     ref = O.esm_embeddings(ids, (ids != 1).long(), Wr, 32)
-    assert_close(x.cpu(), ref.detach(), 1e-6, 1e-6, "embed fwd")
+    close(x.cpu(), ref.detach(), 1e-6, 1e-6, "embed fwd")
     dx = torch.randn(B, L, d, generator=g)
     ref.backward(dx)
     dW = torch.full((vocab, d), 7.0, device=DEV)
     w = ws(hip.query("oneprot_esm_embed_bwd_workspace", B * L, d, vocab))
     hip.call("oneprot_esm_embed_bwd", idd, dx.to(DEV), rs, dW, w, B, L, d, vocab, 1, 32, 1, 0)
-    assert_close(dW.cpu(), Wr.grad, 1e-5, 1e-5, "embed bwd")
+    close(dW.cpu(), Wr.grad, 1e-5, 1e-5, "embed bwd")
 
 
 @pytest.mark.parametrize("T,d", [(37, 64), (1000, 640), (130, 1280), (64, 48)])
@@ -80,8 +62,8 @@ def test_layernorm_fwd_bwd(T, d):
     xr = x.clone().requires_grad_(True)
     gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     ref = torch.nn.functional.layer_norm(xr, (d,), gr, br, 1e-5)
-    assert_close(yf, ref.detach(), 1e-5, 1e-5, "ln fwd f32")
-    assert_close(yb, ref.detach(), 2 ** -8, 1e-6, "ln fwd bf16")
+    close(yf, ref.detach(), 1e-5, 1e-5, "ln fwd f32")
+    close(yb, ref.detach(), 2 ** -8, 1e-6, "ln fwd bf16")
     # backward, fp32 dy, accumulate into an existing residual gradient
     dy = torch.randn(T, d, generator=g).to(DEV)
     add = torch.randn(T, d, generator=g).to(DEV)
@@ -91,9 +73,9 @@ def test_layernorm_fwd_bwd(T, d):
     db = torch.zeros(d, device=DEV)
     w = ws(hip.query("oneprot_layernorm_bwd_workspace", d))
     hip.call("oneprot_layernorm_bwd", dy, 1, None, 0, x, 0, gamma, mean, rstd, add, dx, None, dg, db, w, T, d, 0)
-    assert_close(dx, xr.grad + add, 1e-4, 1e-4, "ln bwd dx")
-    assert_close(dg, gr.grad, 1e-4, 1e-3, "ln bwd dgamma")
-    assert_close(db, br.grad, 1e-4, 1e-3, "ln bwd dbeta")
+    close(dx, xr.grad + add, 1e-4, 1e-4, "ln bwd dx")
+    close(dg, gr.grad, 1e-4, 1e-3, "ln bwd dgamma")
+    close(db, br.grad, 1e-4, 1e-3, "ln bwd dbeta")
     # bf16 dy, in place on the residual gradient, accumulate param grads
     dyb = bf(dy)
     dx2 = add.clone()
@@ -102,7 +84,7 @@ def test_layernorm_fwd_bwd(T, d):
     assert torch.equal(dx2b, dx2.to(torch.bfloat16))
     xr2 = x.clone().requires_grad_(True)
     torch.nn.functional.layer_norm(xr2, (d,), gamma, beta, 1e-5).backward(dyb.float())
-    assert_close(dx2, xr2.grad + add, 1e-4, 1e-4, "ln bwd dx (bf16 dy, in place)")
+    close(dx2, xr2.grad + add, 1e-4, 1e-4, "ln bwd dx (bf16 dy, in place)")
 
 
 @pytest.mark.parametrize("mode", [0, 1])
@@ -123,17 +105,17 @@ def test_lnpool_fwd_and_pooled_bwd(mode):
     gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     h = O.layer_norm(xr, gr, br, 1e-5)
     ref = O.mean_pool(h, (ids != 1).long()) if mode == 0 else O.cls_pool(h)
-    assert_close(hid.cpu(), h.detach(), 1e-5, 1e-5, "hidden")
-    assert_close(pooled.cpu(), ref.detach(), 1e-5, 1e-5, "pooled")
+    close(hid.cpu(), h.detach(), 1e-5, 1e-5, "hidden")
+    close(pooled.cpu(), ref.detach(), 1e-5, 1e-5, "pooled")
     dp = torch.randn(B, d, generator=g)
     ref.backward(dp)
     dx = torch.empty(B * L, d, device=DEV)
     dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
     w = ws(hip.query("oneprot_layernorm_bwd_workspace", d))
     hip.call("oneprot_layernorm_bwd", dp.to(DEV), 2, wrow, L, xd, 0, gamma.to(DEV), mean, rstd, None, dx, None, dg, db, w, B * L, d, 0)
-    assert_close(dx.cpu().view(B, L, d), xr.grad, 1e-4, 1e-5, "pooled bwd dx")
-    assert_close(dg.cpu(), gr.grad, 1e-4, 1e-4, "pooled bwd dgamma")
-    assert_close(db.cpu(), br.grad, 1e-4, 1e-4, "pooled bwd dbeta")
+    close(dx.cpu().view(B, L, d), xr.grad, 1e-4, 1e-5, "pooled bwd dx")
+    close(dg.cpu(), gr.grad, 1e-4, 1e-4, "pooled bwd dgamma")
+    close(db.cpu(), br.grad, 1e-4, 1e-4, "pooled bwd dbeta")
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -165,10 +147,10 @@ def test_gemm_nt_epilogues(M, N, K, gemm_shape):
     ref = A.float() @ W.float().t()
     out = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_BF16, bias, out, None, None, None, None, None, 1.0, 0, 0, 0)
-    assert_close(out, ref + bias, 2 ** -7, 2e-2, "EPI_BF16")
+    close(out, ref + bias, 2 ** -7, 2e-2, "EPI_BF16")
     outf = torch.empty(M, N, device=DEV)
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, outf, None, None, None, None, None, 1.0, 0, 0, 0)
-    assert_close(outf, ref, 1e-4, 1e-3 * math.sqrt(K / 64), "EPI_F32")
+    close(outf, ref, 1e-4, 1e-3 * math.sqrt(K / 64), "EPI_F32")
     # bias + gelu (+z)
     u = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     z = torch.empty(M, N, dtype=torch.uint8, device=DEV)                 # gelu'(z) as one-byte codes c = rint(192 g' + 25) (include/oneprot_hip.h)
@@ -176,7 +158,7 @@ def test_gemm_nt_epilogues(M, N, K, gemm_shape):
     zr = (ref + bias).requires_grad_(True)
     gz = torch.nn.functional.gelu(zr)
     gz.sum().backward()
-    assert_close(u, gz.detach(), 2 ** -7, 2e-2, "gelu(z)")
+    close(u, gz.detach(), 2 ** -7, 2e-2, "gelu(z)")
     zdec = (z.float() - 25.0) / 192.0
     # half a code step (1/384) + the slope of gelu' (<= 0.8) times the bf16-operand error of z itself; exact at the saturated ends
     assert float((zdec - zr.grad).abs().max()) < 1 / 384 + 2e-3, "gelu'(z) codes"
@@ -186,21 +168,21 @@ def test_gemm_nt_epilogues(M, N, K, gemm_shape):
         assert torch.equal(zdec[sat], (zr.detach()[sat] > 0).float())
     u2 = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)            # forward-only form (frozen tower): no derivative output
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_BIAS_GELU, bias, u2, None, None, None, None, None, 1.0, 0, 0, 0)
-    assert_close(u2, gz.detach(), 2 ** -7, 2e-2, "gelu(z), no derivative")
+    close(u2, gz.detach(), 2 ** -7, 2e-2, "gelu(z), no derivative")
     # bias + fp32 residual, in place
     g = torch.Generator().manual_seed(4)
     resid = torch.randn(M, N, generator=g).to(DEV)
     x = resid.clone()
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_BIAS_RESID, bias, x, None, None, x, None, None, 1.0, 0, 0, 0)
-    assert_close(x, ref + bias + resid, 1e-4, 1e-3 * math.sqrt(K / 64), "bias+resid")
+    close(x, ref + bias + resid, 1e-4, 1e-3 * math.sqrt(K / 64), "bias+resid")
     x2, x2h = torch.empty(M, N, device=DEV), torch.empty(M, N, dtype=torch.bfloat16, device=DEV)      # out of place, with the bf16 copy
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_BIAS_RESID, bias, x2, x2h, None, resid, None, None, 1.0, 0, 0, 0)
-    assert_close(x2, ref + bias + resid, 1e-4, 1e-3 * math.sqrt(K / 64), "bias+resid out of place")
-    assert_close(x2h, ref + bias + resid, 2 ** -7, 2e-2, "bias+resid bf16 copy")
+    close(x2, ref + bias + resid, 1e-4, 1e-3 * math.sqrt(K / 64), "bias+resid out of place")
+    close(x2h, ref + bias + resid, 2 ** -7, 2e-2, "bias+resid bf16 copy")
     # gelu backward epilogue
     dz = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_GELU_BWD, None, dz, None, None, z, None, None, 1.0, 0, 0, 0)
-    assert_close(dz, ref * zdec, 2 ** -6, 3e-2, "gelu bwd")
+    close(dz, ref * zdec, 2 ** -6, 3e-2, "gelu bwd")
 
 
 def test_gemm_force_shape_rejects_unknown_ids():
@@ -221,12 +203,12 @@ def test_gemm_force_shape_rejects_unknown_ids():
             hip.query("oneprot_gemm_force_shape", shape)
             out.fill_(float("nan"))
             hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, out, None, None, None, None, None, 1.0, 0, 0, 0)
-            assert_close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), f"EPI_F32, forced id {shape}")
+            close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), f"EPI_F32, forced id {shape}")
     finally:
         hip.query("oneprot_gemm_force_shape", -1)
     out.fill_(float("nan"))
     hip.call("oneprot_gemm_bf16_nt", A, W, M, N, K, K, K, hip.EPI_F32, None, out, None, None, None, None, None, 1.0, 0, 0, 0)
-    assert_close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), "EPI_F32 after the hook is back at -1")
+    close(out, ref, 1e-4, 1e-3 * math.sqrt(K / 64), "EPI_F32 after the hook is back at -1")
 
 
 @pytest.mark.parametrize("form", [1, 0])
@@ -277,12 +259,12 @@ def test_gemm_resid_layernorm_across_work_groups(M, N, K, has_bias, inplace, sta
         if big:
             assert torch.equal(x, x_ref), f"x_out, launch {rep}"
         else:                                                    # (fewer than 192 tiles: the unfused GEMM runs on another kernel with another summation order)
-            assert_close(x, x_ref, 2e-5, 2e-4, f"x_out, launch {rep}")
+            close(x, x_ref, 2e-5, 2e-4, f"x_out, launch {rep}")
         if stats:
-            assert_close(st[0], m_ref, 1e-5, 1e-5 if big else 1e-4, "mean")
-            assert_close(st[1], r_ref, 2e-5 if big else 2e-4, 0.0, "rstd")
+            close(st[0], m_ref, 1e-5, 1e-5 if big else 1e-4, "mean")
+            close(st[1], r_ref, 2e-5 if big else 2e-4, 0.0, "rstd")
         assert torch.isfinite(h.float()).all()
-        assert_close(h.float(), h_ref.float(), 2 ** -7, 2e-3, f"h, launch {rep}")
+        close(h.float(), h_ref.float(), 2 ** -7, 2e-3, f"h, launch {rep}")
         assert (h.float() - h_ref.float()).abs().gt(1e-6).float().mean() < 0.02      # a bf16 ulp here and there, not a different function
         # ... and directly against fp32 torch: two-pass LayerNorm of A W^T + b + r (hf modeling_esm.py:442-463, then :429)
         if M <= 33024:
@@ -290,11 +272,11 @@ def test_gemm_resid_layernorm_across_work_groups(M, N, K, has_bias, inplace, sta
             mu = xr.mean(-1, keepdim=True)
             var = ((xr - mu) ** 2).mean(-1, keepdim=True)
             hr = (xr - mu) * torch.rsqrt(var + 1e-5) * gamma + beta
-            assert_close(x, xr, 2e-5, 3e-4, "x_out vs fp32 torch")
-            assert_close(h.float(), hr, 2 ** -7, 4e-3, "h vs fp32 torch two-pass LayerNorm")
+            close(x, xr, 2e-5, 3e-4, "x_out vs fp32 torch")
+            close(h.float(), hr, 2 ** -7, 4e-3, "h vs fp32 torch two-pass LayerNorm")
             if stats:
-                assert_close(st[0], mu[:, 0], 1e-5, 1e-4, "mean vs torch")
-                assert_close(st[1], torch.rsqrt(var + 1e-5)[:, 0], 1e-4, 0.0, "rstd vs torch")
+                close(st[0], mu[:, 0], 1e-5, 1e-4, "mean vs torch")
+                close(st[1], torch.rsqrt(var + 1e-5)[:, 0], 1e-4, 0.0, "rstd vs torch")
     assert hip.sched_error() == 0
 
 
@@ -594,10 +576,10 @@ def _gemm_resid_layernorm_fused(M, K, inplace):
     h = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
     hip.call("oneprot_gemm_bf16_nt_resid_ln", A, Wp, M, N, K, K, bias, x if inplace else resid, x, gamma, beta, 1e-5, h, mean, rstd)
-    assert_close(x, xr, 1e-4, 1e-3 * math.sqrt(K / 64), "x = A W^T + bias + resid")
-    assert_close(mean, mu.squeeze(-1), 1e-4, 1e-4 * math.sqrt(K / 64), "mean")
-    assert_close(rstd, torch.rsqrt(var + 1e-5).squeeze(-1), 1e-3, 1e-5, "rstd")
-    assert_close(h, hr, 2 ** -7, 2e-2, "h = LayerNorm(x)")
+    close(x, xr, 1e-4, 1e-3 * math.sqrt(K / 64), "x = A W^T + bias + resid")
+    close(mean, mu.squeeze(-1), 1e-4, 1e-4 * math.sqrt(K / 64), "mean")
+    close(rstd, torch.rsqrt(var + 1e-5).squeeze(-1), 1e-3, 1e-5, "rstd")
+    close(h, hr, 2 ** -7, 2e-2, "h = LayerNorm(x)")
     # not built for this: the caller keeps the GEMM + LayerNorm pair
     with pytest.raises(hip.HipKernelError):
         hip.call("oneprot_gemm_bf16_nt_resid_ln", A[:100].contiguous(), Wp, 100, N, K, K, bias, resid, x, gamma, beta, 1e-5, h, mean, rstd)
@@ -616,9 +598,9 @@ def test_gemm_qkv_rope_epilogue(B, L, H, hd, gemm_shape):
     y = (A.float() @ W.float().t() + bias).cpu().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
     qr = O.apply_rope(y[0] * hd ** -0.5, cos, sin)
     kr = O.apply_rope(y[1], cos, sin)
-    assert_close(q.cpu(), qr, 2 ** -7, 2e-2, "q")
-    assert_close(k.cpu(), kr, 2 ** -7, 2e-2, "k")
-    assert_close(v.cpu(), y[2], 2 ** -7, 2e-2, "v")
+    close(q.cpu(), qr, 2 ** -7, 2e-2, "q")
+    close(k.cpu(), kr, 2 ** -7, 2e-2, "k")
+    close(v.cpu(), y[2], 2 ** -7, 2e-2, "v")
 
 
 @pytest.fixture(params=gemm_forms.ids(gemm_forms.TN_VARIANTS), ids=gemm_forms.names(gemm_forms.TN_VARIANTS))
@@ -640,16 +622,16 @@ def test_gemm_tn(M, N, K, tn_variant):
     w = ws(hip.query("oneprot_gemm_bf16_tn_workspace", N, K))
     db = torch.full((N,), 5.0, device=DEV)
     hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, db, w, w.numel(), 0)
-    assert_close(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), "tn")
-    assert_close(db, dY.float().sum(0), 1e-4, 1e-2, "tn fused bias grad")
+    close(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), "tn")
+    close(db, dY.float().sum(0), 1e-4, 1e-2, "tn fused bias grad")
     hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, None, w, w.numel(), 1)
-    assert_close(dW, 2 * ref, 1e-4, 4e-3 * math.sqrt(M / 64), "tn accumulate")
+    close(dW, 2 * ref, 1e-4, 4e-3 * math.sqrt(M / 64), "tn accumulate")
     # (leading dimensions that differ from the logical width -- column slices of wider matrices -- and the narrow adapter shapes:
     # tests/test_gemm_small_shapes_gpu.py, test_gemm_tn_narrow_and_strided)
     cs = torch.full((N,), -1.0, device=DEV)
     w2 = ws(hip.query("oneprot_colsum_workspace", N))
     hip.call("oneprot_colsum_bf16", dY, cs, w2, M, N, 0)
-    assert_close(cs, dY.float().sum(0), 1e-4, 1e-2, "colsum")
+    close(cs, dY.float().sum(0), 1e-4, 1e-2, "colsum")
 
 
 @pytest.mark.parametrize("M,N,K", [(8192, 1280, 1280), (8192, 1280, 5120), (8448, 480, 640), (6400, 1920, 480), (8320, 768, 768), (8320, 768, 3072)])
@@ -668,8 +650,8 @@ def test_gemm_tn_large_m_every_width(M, N, K):
     hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, db, w, need, 0)
     assert bool((w[need:] == 0xA5).all()), "wrote past the workspace"
     ref = dY.float().t() @ X.float()
-    assert_close(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), "tn large M")
-    assert_close(db, dY.float().sum(0), 1e-4, 2e-2, "tn large M bias")
+    close(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), "tn large M")
+    close(db, dY.float().sum(0), 1e-4, 2e-2, "tn large M bias")
     with pytest.raises(hip.HipKernelError):
         hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, db, w, need // 2, 0)
 
@@ -702,16 +684,13 @@ def test_sgemm(tA, bkn):
     Bd = (Bm if bkn else Bm.t().contiguous()).to(DEV)
     C = torch.ones(M, N, device=DEV)
     hip.call("oneprot_sgemm", Ad, Bd, C, M, N, K, tA, bkn, 0.5, 1)
-    assert_close(C.cpu(), 1 + 0.5 * (A @ Bm), 1e-5, 1e-5, "sgemm")
+    close(C.cpu(), 1 + 0.5 * (A @ Bm), 1e-5, 1e-5, "sgemm")
 
 
 # ------------------------------------------------------------------------------------------------------
 def _attn_ref(q, k, v, bias):
-    s = q.float() @ k.float().transpose(-1, -2)
-    if bias is not None:
-        s = s + bias[:, None, None, :]
-    p = torch.softmax(s, -1)
-    return p @ v.float(), torch.logsumexp(s, -1)
+    """fwd_ref for a q in natural units (it takes the kernels' log2 units)"""
+    return fwd_ref(q.double() * hip.LOG2E, k, v, bias)
 
 
 @pytest.fixture(params=[0, 1, 2], ids=["bwd_split", "bwd_fused", "bwd_fused_64keys"])
@@ -744,10 +723,10 @@ def test_attention_fwd_bwd(B, H, L, hd, attn_bwd_path, attn_fwd_path):
     qr, kr, vr = ((q.float() / hip.LOG2E).requires_grad_(True), k.float().requires_grad_(True), v.float().requires_grad_(True))
     o_ref, lse_ref = _attn_ref(qr, kr, vr, bias)
     o_tok = o_ref.permute(0, 2, 1, 3).reshape(B * L, H * hd)
-    assert_close(ctx, o_tok.detach(), 2 ** -7, 1e-2, "attn fwd")
+    close(ctx, o_tok.detach(), 2 ** -7, 1e-2, "attn fwd")
     # the row sum is taken by an all-ones MFMA over the bf16-rounded probabilities (the same values the context numerator uses): a row
     # dominated by one key carries that key's 2^-9 rounding into log(l)
-    assert_close(lse, lse_ref.detach(), 1e-4, 5e-3, "lse")
+    close(lse, lse_ref.detach(), 1e-4, 5e-3, "lse")
     # backward (no rope: cos/sin NULL => dqkv is the raw gradient * q_scale)
     dctx = bf(torch.randn(B * L, H * hd, generator=g)).to(DEV)
     o_tok.backward(dctx.float())
@@ -756,8 +735,8 @@ def test_attention_fwd_bwd(B, H, L, hd, attn_bwd_path, attn_fwd_path):
     hip.call("oneprot_attn_bwd", q, k, v, bias, ctx, dctx, lse, None, None, 1.0, dqkv, w, B, H, L, hd)
     got = dqkv.float().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
     for name, gt, rf in (("dq", got[0], qr.grad), ("dk", got[1], kr.grad), ("dv", got[2], vr.grad)):
-        assert rel_err(gt, rf) < 2e-2, f"{name} rel err {rel_err(gt, rf)}"
-        assert_close(gt, rf, 5e-2, 5e-2 * rf.abs().max().item(), name)
+        assert rel_l2(gt, rf) < 2e-2, f"{name} rel err {rel_l2(gt, rf)}"
+        close(gt, rf, 5e-2, 5e-2 * rf.abs().max().item(), name)
 
 
 @pytest.mark.parametrize("L", [1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, 288, 479, 511, 512, 513, 777])
@@ -793,12 +772,12 @@ def test_attention_fwd_nomax_equals_rowmax_at_block_edges(L, hd):
     o_ref, lse_ref = _attn_ref(q.float() / hip.LOG2E, k.float(), v.float(), bias)
     for name, (c1, l1) in zip(("fwd3/fwd2", "fwd2"), outs[1:]):
         assert torch.isfinite(c1).all() and torch.isfinite(l1).all(), name
-        assert_close(c1, c0, 2 ** -7, 2 ** -8 * float(c0.abs().max()), f"ctx {name}")
+        close(c1, c0, 2 ** -7, 2 ** -8 * float(c0.abs().max()), f"ctx {name}")
         # the row sum is a sum of bf16-rounded probabilities in both kernels; with the maximum subtracted the largest one is exactly 1, without it
         # it carries its own 2^-9 rounding: log(l) of a row dominated by few keys differs by up to 2 x 2e-3
-        assert_close(l1, l0, 1e-5, 8e-3, f"lse {name}")
-        assert_close(c1, o_ref.permute(0, 2, 1, 3).reshape(B * L, H * hd), 2 ** -7, 1e-2, f"ctx vs fp32 {name}")
-        assert_close(l1, lse_ref, 1e-4, 5e-3, f"lse vs fp32 {name}")
+        close(l1, l0, 1e-5, 8e-3, f"lse {name}")
+        close(c1, o_ref.permute(0, 2, 1, 3).reshape(B * L, H * hd), 2 ** -7, 1e-2, f"ctx vs fp32 {name}")
+        close(l1, lse_ref, 1e-4, 5e-3, f"lse vs fp32 {name}")
 
 
 @pytest.mark.parametrize("L,hd", [(512, 32), (300, 16), (700, 32), (400, 64)])
@@ -837,8 +816,8 @@ def test_attention_fwd_nomax_overflow_underflow_net(L, hd):
         finally:
             hip.query("oneprot_attn_force_fwd_path", -1)
         assert torch.isfinite(ctx.float()).all() and torch.isfinite(lse).all(), path
-        assert_close(ctx, o_ref, 2 ** -6, 1.5e-2, f"ctx (extreme scores, path {path})")
-        assert_close(lse, lse_ref, 2e-4, 2e-2, f"lse (extreme scores, path {path})")
+        close(ctx, o_ref, 2 ** -6, 1.5e-2, f"ctx (extreme scores, path {path})")
+        close(lse, lse_ref, 2e-4, 2e-2, f"lse (extreme scores, path {path})")
 
 
 @pytest.mark.parametrize("L", [1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, 288, 479, 511, 512])
@@ -880,11 +859,11 @@ def test_attention_bwd_fused_equals_split_at_block_edges(L, hd):
         assert float(f64[L + L - L // 4: 2 * L, 1:].abs().max()) == 0.0 and float(fused[L + L - L // 4: 2 * L, 1:].abs().max()) == 0.0
     # two key blocks per wave: the walks start at other query blocks and dQ adds its two key blocks first -- the same sums in yet another order
     for part, name in enumerate(("dQ", "dK", "dV")):
-        assert_close(f64[:, part], split[:, part], 2 ** -7, 2 ** -7 * float(split[:, part].abs().max()), name + " (64 keys per wave)")
-        assert rel_err(f64[:, part], split[:, part]) < 3e-3, name
+        close(f64[:, part], split[:, part], 2 ** -7, 2 ** -7 * float(split[:, part].abs().max()), name + " (64 keys per wave)")
+        assert rel_l2(f64[:, part], split[:, part]) < 3e-3, name
     for part, name in enumerate(("dQ", "dK", "dV")):
-        assert_close(fused[:, part], split[:, part], 2 ** -7, 2 ** -7 * float(split[:, part].abs().max()), name)
-        assert rel_err(fused[:, part], split[:, part]) < 3e-3, name
+        close(fused[:, part], split[:, part], 2 ** -7, 2 ** -7 * float(split[:, part].abs().max()), name)
+        assert rel_l2(fused[:, part], split[:, part]) < 3e-3, name
 
 
 @pytest.mark.parametrize("B,H,L,hd", [(2, 3, 70, 64), (1, 2, 300, 64), (2, 2, 96, 32)])
@@ -919,10 +898,10 @@ def test_attention_probability_dropout_fwd_bwd(B, H, L, hd):
     s_ = ql @ kr.transpose(-1, -2) + bias[:, None, None, :]
     pr = torch.softmax(s_, -1)
     ref = ((pr * kf / kp) @ vr).permute(0, 2, 1, 3).reshape(B * L, H * hd)
-    assert_close(ctx.float().cpu(), ref.detach(), 2 ** -6, 2e-2, "ctx with probability dropout")
-    assert_close(lse.cpu(), torch.logsumexp(s_, -1).detach(), 2e-3, 2e-2, "lse (undropped)")
+    close(ctx.float().cpu(), ref.detach(), 2 ** -6, 2e-2, "ctx with probability dropout")
+    close(lse.cpu(), torch.logsumexp(s_, -1).detach(), 2e-3, 2e-2, "lse (undropped)")
     nodrop = (pr @ vr).permute(0, 2, 1, 3).reshape(B * L, H * hd).detach()
-    assert rel_err(ctx.float().cpu(), nodrop) > 5 * rel_err(ctx.float().cpu(), ref.detach())          # the mask matters
+    assert rel_l2(ctx.float().cpu(), nodrop) > 5 * rel_l2(ctx.float().cpu(), ref.detach())          # the mask matters
     dctx = bf(torch.randn(B * L, H * hd, generator=g))
     ref.backward(dctx.float())
     dqkv = torch.zeros(B * L, 3 * H * hd, dtype=torch.bfloat16, device=DEV)
@@ -931,7 +910,7 @@ def test_attention_probability_dropout_fwd_bwd(B, H, L, hd):
     got = dqkv.float().cpu().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
     # q was stored x log2(e): the kernel returns d/d(unscaled q) with q_scale = 1 applied to ... the gradient w.r.t. the stored q / log2(e)
     for i, (name, r_) in enumerate((("dq", ql.grad), ("dk", kr.grad), ("dv", vr.grad))):
-        assert rel_err(got[i], r_) < 2e-2, f"{name}: {rel_err(got[i], r_)}"
+        assert rel_l2(got[i], r_) < 2e-2, f"{name}: {rel_l2(got[i], r_)}"
     # and the masked backward is not the plain one
     dq0 = torch.zeros_like(dqkv)
     hip.query("oneprot_attn_force_bwd_path", 0)
@@ -939,7 +918,7 @@ def test_attention_probability_dropout_fwd_bwd(B, H, L, hd):
         hip.call("oneprot_attn_bwd", qd, k.to(DEV), v.to(DEV), bias.to(DEV), ctx, dctx.to(DEV), lse, None, None, 1.0, dq0, w, B, H, L, hd)
     finally:
         hip.query("oneprot_attn_force_bwd_path", -1)
-    assert rel_err(dq0.float().cpu().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)[2], vr.grad) > 5 * rel_err(got[2], vr.grad)
+    assert rel_l2(dq0.float().cpu().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)[2], vr.grad) > 5 * rel_l2(got[2], vr.grad)
 
 
 @pytest.mark.parametrize("L,expected", [(256, 0), (288, 0), (320, 1), (416, 1), (448, 2), (512, 2)])
@@ -992,7 +971,7 @@ def test_attention_bwd_rope_chain(L, hd, attn_bwd_path):
     hip.call("oneprot_attn_bwd", qb, kb, vb, None, ctx, dctx.to(DEV), lse, cosd, sind, hd ** -0.5, dqkv, w, B, H, L, hd)
     got = dqkv.float().cpu().view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4)
     for i, name in enumerate(("dq", "dk", "dv")):
-        assert rel_err(got[i], ylin.grad[i]) < 2e-2, f"{name}: {rel_err(got[i], ylin.grad[i])}"
+        assert rel_l2(got[i], ylin.grad[i]) < 2e-2, f"{name}: {rel_l2(got[i], ylin.grad[i])}"
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1007,7 +986,7 @@ def test_feature_ops():
     hip.call("oneprot_l2norm_fwd", xd, y, inv, R, D, scale)
     xr = x.clone().requires_grad_(True)
     yr = O.l2_normalize(xr) * scale
-    assert_close(y.cpu(), yr.detach(), 1e-5, 1e-5, "l2norm fwd")
+    close(y.cpu(), yr.detach(), 1e-5, 1e-5, "l2norm fwd")
     dy = torch.randn(R, D, generator=g)
     l1c = 0.01 / (R * D)
     (yr * dy).sum().backward(retain_graph=True)
@@ -1016,17 +995,17 @@ def test_feature_ops():
     ((yr * dy).sum() + 0.01 * yr.abs().mean()).backward()
     dx = torch.empty(R, D, device=DEV)
     hip.call("oneprot_l2norm_bwd", y, dy.to(DEV), inv, dx, R, D, scale, 0.0)
-    assert_close(dx.cpu(), g0, 1e-4, 1e-5, "l2norm bwd")
+    close(dx.cpu(), g0, 1e-4, 1e-5, "l2norm bwd")
     hip.call("oneprot_l2norm_bwd", y, dy.to(DEV), inv, dx, R, D, scale, l1c)
-    assert_close(dx.cpu(), xr.grad, 1e-4, 1e-5, "l2norm bwd + L1")
+    close(dx.cpu(), xr.grad, 1e-4, 1e-5, "l2norm bwd + L1")
     # gelu
     gy = torch.empty(R, D, device=DEV)
     hip.call("oneprot_gelu_f32", xd, gy, R * D)
-    assert_close(gy.cpu(), O.gelu_erf(x), 1e-5, 1e-6, "gelu")
+    close(gy.cpu(), O.gelu_erf(x), 1e-5, 1e-6, "gelu")
     x2 = x.clone().requires_grad_(True)
     O.gelu_erf(x2).backward(dy)
     hip.call("oneprot_gelu_bwd_f32", xd, dy.to(DEV), gy, R * D)
-    assert_close(gy.cpu(), x2.grad, 1e-4, 1e-5, "gelu bwd")
+    close(gy.cpu(), x2.grad, 1e-4, 1e-5, "gelu bwd")
     # abs sum
     acc = torch.ones(1, device=DEV)
     w = ws(hip.query("oneprot_sumsq_workspace"))
@@ -1047,7 +1026,7 @@ def test_cross_entropy(R, C, off):
     rw = torch.empty(R, device=DEV)
     hip.call("oneprot_ce_fwd_bwd", ld, out, rw, R, C, off, 0.5 / R)
     assert abs(out.item() - loss.item()) < 1e-5 * max(1, abs(loss.item()))
-    assert_close(ld.cpu(), lr.grad, 1e-4, 1e-7, "dlogits")
+    close(ld.cpu(), lr.grad, 1e-4, 1e-7, "dlogits")
 
 
 def test_optimizer_kernels():
@@ -1070,7 +1049,7 @@ def test_optimizer_kernels():
         hip.call("oneprot_clip_coef", ss, 1.0, coef, nrm, None)
         assert abs(nrm.item() - tn.item()) < 1e-3 * tn.item()
         hip.call("oneprot_adam_step", pd, gd, m, v, n, 1e-3, 0.9, 0.999, 1e-8, 0.0, step, coef)
-        assert_close(pd.cpu(), pr.detach(), 1e-5, 2e-6, f"adam step {step}")
+        close(pd.cpu(), pr.detach(), 1e-5, 2e-6, f"adam step {step}")
 
 
 def test_casts():
@@ -1158,10 +1137,10 @@ def test_dropout_add_layernorm_fused_equals_the_two_kernels(T, d):
     s, y16, y, m, r = torch.empty_like(x), torch.empty_like(y16_ref), torch.empty_like(x), torch.empty(T, device=DEV), torch.empty(T, device=DEV)
     hip.call("oneprot_dropout_add_layernorm_fwd", x, resid, s, gamma, beta, y16, y, m, r, T, d, 1e-12, p_, seed, stream)
     assert torch.equal(s, s_ref)
-    assert_close(m, m_ref, 1e-6, 1e-6, "mean")
-    assert_close(r, r_ref, 1e-5, 0.0, "rstd")
-    assert_close(y, y_ref, 1e-5, 2e-5, "LayerNorm fp32")
-    assert_close(y16.float(), y16_ref.float(), 2 ** -7, 1e-5, "LayerNorm bf16")
+    close(m, m_ref, 1e-6, 1e-6, "mean")
+    close(r, r_ref, 1e-5, 0.0, "rstd")
+    close(y, y_ref, 1e-5, 2e-5, "LayerNorm fp32")
+    close(y16.float(), y16_ref.float(), 2 ** -7, 1e-5, "LayerNorm bf16")
     # a frozen tower: no sum, fp32 output in place on the residual stream
     r2, y16b = resid.clone(), torch.empty_like(y16_ref)
     hip.call("oneprot_dropout_add_layernorm_fwd", x, r2, None, gamma, beta, y16b, r2, None, None, T, d, 1e-12, p_, seed, stream)
@@ -1206,7 +1185,7 @@ def test_dropout_bf16_mask_is_a_function_of_seed_stream_and_element():
     assert torch.equal(d16, ref16)
     d32 = base.clone().to(DEV)
     hip.call("oneprot_dropout_bwd_add_f32", dy, d32, n, p_, seed, 7)
-    assert_close(d32.cpu(), (base.to(DEV) + mask * scale * dy.float()).cpu(), 1e-6, 1e-6, "dropout bwd add f32")
+    close(d32.cpu(), (base.to(DEV) + mask * scale * dy.float()).cpu(), 1e-6, 1e-6, "dropout bwd add f32")
     with pytest.raises(hip.HipKernelError):
         hip.call("oneprot_dropout_bf16", x, y, n - 4, p_, seed, 7)            # whole 16-byte pieces only
     with pytest.raises(hip.HipKernelError):
@@ -1237,8 +1216,8 @@ def test_clip_loss_node_multirank_semantics(golden_dir, world, local_loss):
         loss.backward()
         rl, rgm, rgs = g["per_rank"][rank][f"clip_ll{int(local_loss)}_gwg0"]
         assert abs(loss.item() - rl.item()) / abs(rl.item()) < 1e-5
-        assert_close(m.grad.cpu(), rgm, 1e-4, 1e-6, "dm")
-        assert_close(s.grad.cpu(), rgs, 1e-4, 1e-6, "ds")
+        close(m.grad.cpu(), rgm, 1e-4, 1e-6, "dm")
+        close(s.grad.cpu(), rgs, 1e-4, 1e-6, "ds")
 
 
 @pytest.mark.parametrize("negative_only", [False, True])
@@ -1256,8 +1235,8 @@ def test_siglip_block(negative_only):
     loss = _SigLipBlockFn.apply(md, sd, 1.0, -2.5, negative_only, _siglip_block_hip)
     (loss * 0.7).backward()
     assert abs(loss.item() - ref.item()) < 1e-4 * abs(ref.item())
-    assert_close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "siglip dm")
-    assert_close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "siglip ds")
+    close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "siglip dm")
+    close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "siglip ds")
 
 
 @pytest.mark.parametrize("scale_on", ["cuda", "cpu"])
@@ -1280,8 +1259,8 @@ def test_siglip_tensor_scale_and_bias_stay_on_device_and_get_gradients(scale_on,
     loss = SigLipLoss(rank=0, world_size=1)(md, sd, logit_scale=sc, logit_bias=bi)
     (loss * 0.7).backward()
     assert abs(loss.item() - ref.item()) < 1e-4 * abs(ref.item())
-    assert_close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "siglip dm")
-    assert_close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "siglip ds")
+    close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "siglip dm")
+    close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "siglip ds")
     assert sc.grad.device.type == scale_on and sc.grad.shape == sc.shape
     assert abs(sc.grad.item() - sc_r.grad.item()) < 1e-4 * abs(sc_r.grad.item()) + 1e-6, (sc.grad, sc_r.grad)
     assert abs(bi.grad.item() - bi_r.grad.item()) < 1e-4 * abs(bi_r.grad.item()) + 1e-6, (bi.grad, bi_r.grad)
@@ -1341,8 +1320,8 @@ def test_clip_loss_tensor_logit_scale_stays_on_device_and_gets_a_gradient():
     loss = fn(md, sd, log_scale.exp())
     loss.backward()
     assert abs(loss.item() - ref.item()) < 1e-5 * abs(ref.item())
-    assert_close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "dm (tensor scale)")
-    assert_close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "ds (tensor scale)")
+    close(md.grad.cpu(), mr.grad, 1e-4, 1e-6, "dm (tensor scale)")
+    close(sd.grad.cpu(), sr.grad, 1e-4, 1e-6, "ds (tensor scale)")
     assert abs(log_scale.grad.item() - log_scale_ref.grad.item()) < 1e-4 * abs(log_scale_ref.grad.item()) + 1e-6
     with torch.no_grad():
         assert abs(fn(md, sd, log_scale.exp()).item() - fn(md, sd, float(log_scale.exp())).item()) < 1e-6
@@ -1387,16 +1366,16 @@ def test_attention1d_pooling_kernels_vs_fp64_torch(B, L, d, with_dx):
     xd, wd, bd, idd, dpd = x.to(DEV), w.to(DEV), bias.to(DEV), ids.to(DEV), dp.to(DEV)
     pooled, attn = torch.empty(B, d, device=DEV), torch.empty(B, L, device=DEV)
     hip.call("oneprot_attnpool_fwd", xd, idd, 1, wd, bd, pooled, attn, B, L, d)
-    assert_close(pooled.cpu().double(), ref.detach(), 2e-5, 2e-6, "attnpool pooled")
-    assert_close(attn.cpu().double(), a.detach(), 2e-5, 1e-7, "attnpool weights")
+    close(pooled.cpu().double(), ref.detach(), 2e-5, 2e-6, "attnpool pooled")
+    close(attn.cpu().double(), a.detach(), 2e-5, 1e-7, "attnpool weights")
     dw, db = torch.empty(d, device=DEV), torch.empty(1, device=DEV)
     dx = torch.empty(B, L, d, device=DEV) if with_dx else None
     ws = torch.empty(hip.query("oneprot_attnpool_bwd_workspace", B, d), dtype=torch.uint8, device=DEV)
     hip.call("oneprot_attnpool_bwd", xd, attn, wd, dpd, dw, db, dx, ws, B, L, d)
-    assert_close(dw.cpu().double(), wr.grad, 1e-4, 1e-5 * float(wr.grad.abs().max()) + 1e-7, "attnpool dw")
-    assert_close(db.cpu().double(), br.grad, 1e-4, 1e-5 * float(wr.grad.abs().max()) + 1e-6, "attnpool db")
+    close(dw.cpu().double(), wr.grad, 1e-4, 1e-5 * float(wr.grad.abs().max()) + 1e-7, "attnpool dw")
+    close(db.cpu().double(), br.grad, 1e-4, 1e-5 * float(wr.grad.abs().max()) + 1e-6, "attnpool db")
     if with_dx:
-        assert_close(dx.cpu().double(), xr.grad, 1e-4, 1e-6, "attnpool dx")
+        close(dx.cpu().double(), xr.grad, 1e-4, 1e-6, "attnpool dx")
 
 
 def test_public_pooling_and_normalize_modules():
@@ -1417,9 +1396,9 @@ def test_public_pooling_and_normalize_modules():
     xd = x.to(DEV).requires_grad_(True)
     got = MeanPooling()(xd, mask.to(DEV))
     (got * tgt.to(DEV)).sum().backward()
-    assert_close(got.detach().cpu(), ref.detach(), 1e-5, 1e-6, "mean pool")
-    assert_close(xd.grad.cpu(), xr.grad, 1e-5, 1e-7, "mean pool dx")
-    assert_close(MeanPooling()(xd.detach()).cpu(), x.mean(1), 1e-5, 1e-6, "mean pool without mask")
+    close(got.detach().cpu(), ref.detach(), 1e-5, 1e-6, "mean pool")
+    close(xd.grad.cpu(), xr.grad, 1e-5, 1e-7, "mean pool dx")
+    close(MeanPooling()(xd.detach()).cpu(), x.mean(1), 1e-5, 1e-6, "mean pool without mask")
     assert torch.equal(CLSTokenPooling()(xd.detach()), xd.detach()[:, 0])
     # attention1d
     pool = Attention1dPooling(d)
@@ -1434,12 +1413,12 @@ def test_public_pooling_and_normalize_modules():
     xd = x.to(DEV).requires_grad_(True)
     got = pool(xd, mask.to(DEV))
     (got * tgt.to(DEV)).sum().backward()
-    assert_close(got.detach().cpu(), ref.detach(), 1e-4, 1e-5, "attention1d pool")
-    assert_close(xd.grad.cpu(), xr.grad, 1e-3, 1e-5, "attention1d dx")
-    assert_close(pool.layer.weight.grad.cpu(), w_ref.grad, 1e-3, 1e-4, "attention1d dw")
+    close(got.detach().cpu(), ref.detach(), 1e-4, 1e-5, "attention1d pool")
+    close(xd.grad.cpu(), xr.grad, 1e-3, 1e-5, "attention1d dx")
+    close(pool.layer.weight.grad.cpu(), w_ref.grad, 1e-3, 1e-4, "attention1d dw")
     # Normalize over the last and over another dimension
     y = torch.randn(5, 7, generator=g)
-    assert_close(Normalize(dim=-1)(y.to(DEV)).cpu(), torch.nn.functional.normalize(y, dim=-1), 1e-5, 1e-6, "normalize -1")
-    assert_close(Normalize(dim=0)(y.to(DEV)).cpu(), torch.nn.functional.normalize(y, dim=0), 1e-5, 1e-6, "normalize 0")
+    close(Normalize(dim=-1)(y.to(DEV)).cpu(), torch.nn.functional.normalize(y, dim=-1), 1e-5, 1e-6, "normalize -1")
+    close(Normalize(dim=0)(y.to(DEV)).cpu(), torch.nn.functional.normalize(y, dim=0), 1e-5, 1e-6, "normalize 0")
     with pytest.raises(hip.HipKernelError):
         MeanPooling()(x, mask)                       # CPU tensors: no fallback

@@ -1,6 +1,5 @@
 """The MSA modality without a device: the fp64 restatement (tests/msa_ref.py) checked against itself, the public surface, the state-dict keys, the
 fair-esm file loader, the refusals, the group planner and the synthetic batches."""
-import argparse
 import inspect
 import math
 import os
@@ -8,15 +7,11 @@ import os
 import pytest
 import torch
 
+from tests import msa_cases as MC
 from tests import msa_ref as MR
+from tests.msa_cases import _tower, _write_fair_esm_file
 
 F64 = torch.float64
-ARCH = dict(layers=2, embed_dim=128, ffn_embed_dim=256, attention_heads=2, max_positions=160, embed_positions_msa=True)
-
-
-def _tower():
-    from oneprot_amd.msa import MsaTransformer, config_from_args
-    return MsaTransformer(config_from_args(ARCH))
 
 
 def _qkv(B, R, L, D, seed):
@@ -91,12 +86,10 @@ def test_ffn_gate_of_the_grouped_stage_test_is_the_measured_one(tmp_path):
     """tests/test_msa_edges_gpu.py runs the FFN stage of its grouped tower test at four times the reference's own difference (bf16-rounded LayerNorm and GELU
     outputs against exact ones): that figure, recomputed here from the same file of weights and the same tokens"""
     from oneprot_amd.msa import MsaTransformer
-    from tests import test_msa_edges_gpu as ME
-    from tests import test_msa_gpu as MG
-    tr = MsaTransformer.from_pretrained(MG._checkpoint(tmp_path))
-    shape, lens, rows, seed = ME.GROUPED
-    diff = MR.ffn_rounding_self_difference(MG._tokens(*shape, lens, rows, seed), tr.state_dict(), tr.H, ME.bf)
-    assert len(diff) == 2 and diff[0] > diff[1] and 0.995 * ME.FFN_SELF_DIFFERENCE_GROUPED < diff[0] <= ME.FFN_SELF_DIFFERENCE_GROUPED
+    tr = MsaTransformer.from_pretrained(MC._checkpoint(tmp_path))
+    shape, lens, rows, seed = MC.GROUPED
+    diff = MR.ffn_rounding_self_difference(MC._tokens(*shape, lens, rows, seed), tr.state_dict(), tr.H, MC.bf)
+    assert len(diff) == 2 and diff[0] > diff[1] and 0.995 * MC.FFN_SELF_DIFFERENCE_GROUPED < diff[0] <= MC.FFN_SELF_DIFFERENCE_GROUPED
 
 
 # ---------------------------------------------------------------------------------------------------------------- surface
@@ -139,11 +132,6 @@ def test_state_dict_keys_and_strict_round_trip():
     assert not any(p.requires_grad for p in other.parameters()) and not other.training
     other.train()
     assert not other.training                                            # frozen, eval only
-
-
-def _write_fair_esm_file(path, tr):
-    sw = lambda k: k.replace("row", "\0").replace("column", "row").replace("\0", "column")
-    torch.save({"args": argparse.Namespace(arch="msa_transformer", **ARCH), "model": {"encoder." + sw(k): v.clone() for k, v in tr.state_dict().items()}}, path)
 
 
 def test_loader_reads_a_fair_esm_file_and_swaps_row_and_column(tmp_path):

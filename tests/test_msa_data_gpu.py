@@ -181,7 +181,7 @@ def test_collate_into_the_encoder(tmp_path, packed):
     from oneprot_amd.packing import PackedMsa
     from src.data.datasets.msa_dataset import MSADataset
     from src.models.components.msa_encoder import MsaEncoder
-    from tests.test_msa_gpu import _checkpoint
+    from tests.msa_cases import _checkpoint
     fams = [R.draw(21, 5, 30), R.draw(22, 40, 64, kind="mutated"), R.draw(23, 200, 130)]
     files = []
     for i, seqs in enumerate(fams):

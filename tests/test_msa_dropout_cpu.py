@@ -11,16 +11,9 @@ import torch
 from tests import msa_dropout_ref as DR
 from tests import msa_ref as MR
 from tests import philox_ref as PR
+from tests.msa_cases import ARCH, _tower  # noqa: F401
 
 F64 = torch.float64
-ARCH = dict(layers=2, embed_dim=128, ffn_embed_dim=256, attention_heads=2, max_positions=160, embed_positions_msa=True)
-
-
-def _tower(arch=ARCH):
-    from oneprot_amd.msa import MsaTransformer, config_from_args
-    return MsaTransformer(config_from_args(arch))
-
-
 @pytest.mark.parametrize("R", [3, 1])
 def test_all_ones_masks_reproduce_the_eval_forward_exactly(R):
     tr = _tower()

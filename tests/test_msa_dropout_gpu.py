@@ -21,8 +21,9 @@ import torch
 
 from tests import msa_dropout_ref as DR
 from tests import msa_ref as MR
-from tests import test_msa_gpu as MG
-from tests.test_msa_gpu import DEV, F64, check
+from tests import msa_cases as MC
+from tests.gate import close
+from tests.msa_cases import DEV, F64
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 2 ** -7, 2e-2
@@ -51,19 +52,19 @@ def _moved_share(masked, plain, pad):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1, 2: the row kernel
-ROW_CASES = [c for c in MG.ROW_CASES if c[0] != (1, 1, 5, 1)]
+ROW_CASES = [c for c in MC.ROW_CASES if c[0] != (1, 1, 5, 1)]
 
 
 def _row_inputs(shape, lens, rows, holes):
     B, R, L, H = shape
-    return MG._ids(B, R, L, lens, rows, holes), _qkv(B, R, L, H, 11 + L, LONG_Q_GAIN if L > 130 else 1.0)
+    return MC._ids(B, R, L, lens, rows, holes), _qkv(B, R, L, H, 11 + L, LONG_Q_GAIN if L > 130 else 1.0)
 
 
 def _row_refs(ids, qkv, H, p, stream):
     """(fp64 context with the host mask, fp64 context without a mask)"""
     B, R, L = ids.shape
     pad = ids.eq(1)
-    q, k, v = MG._split(qkv, B, R, L, H)
+    q, k, v = MC._split(qkv, B, R, L, H)
     S64 = MR.row_scores(q, k, pad, H)
     return DR.row_context(S64, v, pad, H, DR.row_mask(B, H, L, p, SEED, stream)), MR.row_context(S64, v, pad, H)
 
@@ -71,7 +72,7 @@ def _row_refs(ids, qkv, H, p, stream):
 def _row_drop(qkv, ids, H, p, stream, b_first=0, S=None):
     from oneprot_amd import hip
     B, R, L = ids.shape
-    kb, qd = MG._key_bias(ids), qkv.to(DEV)
+    kb, qd = MC._key_bias(ids), qkv.to(DEV)
     if S is None:
         S = torch.empty(B, H, L, L, dtype=torch.float32, device=DEV)
         hip.call("oneprot_msa_row_scores", qd, kb, S, B, R, L, H, 64, 64 ** -0.5 / math.sqrt(R))
@@ -92,11 +93,11 @@ def test_row_context_dropout_vs_fp64_with_the_host_mask(shape, lens, rows, holes
     print(f"row {shape} p={p}: the mask moves {share:.2f} of the unpadded elements out of the tolerance")
     assert share >= 0.5
     _, ctx = _row_drop(qkv, ids, H, p, _stream(5))
-    check(ctx.view(B, R, L, H * 64), c_drop, RTOL, ATOL, f"row ctx dropout {shape} p={p}")
+    close(ctx.view(B, R, L, H * 64), c_drop, RTOL, ATOL, f"row ctx dropout {shape} p={p}")
 
 
 def test_row_b_first_places_the_mask_in_the_batch():
-    shape, lens, rows, holes = MG.ROW_CASES[1]            # (2, 3, 33, 2)
+    shape, lens, rows, holes = MC.ROW_CASES[1]            # (2, 3, 33, 2)
     B, R, L, H = shape
     ids, qkv = _row_inputs(shape, lens, rows, holes)
     _, both = _row_drop(qkv, ids, H, 0.1, _stream(5))
@@ -112,7 +113,7 @@ COL_STREAM = {}                                           # (R, L, p) -> stream 
 
 def _col_inputs(R, L):
     B, H = 2, 2
-    ids = MG._ids(B, R, L, [L, L], [R - R // 3, max(R // 2, 1)])          # the padding of test_col_attn_vs_fp64: trailing rows fully padded
+    ids = MC._ids(B, R, L, [L, L], [R - R // 3, max(R // 2, 1)])          # the padding of test_col_attn_vs_fp64: trailing rows fully padded
     ids[1, :, L - 1] = 1                                                  # one column with every key masked
     return ids, _qkv(B, R, L, H, 100 * R + L)
 
@@ -120,7 +121,7 @@ def _col_inputs(R, L):
 def _col_refs(ids, qkv, H, p, stream):
     B, R, L = ids.shape
     pad = ids.eq(1)
-    q, k, v = MG._split(qkv, B, R, L, H)
+    q, k, v = MC._split(qkv, B, R, L, H)
     return DR.col_context(q, k, v, pad, H, DR.col_mask(B, H, L, R, p, SEED, stream), general=True), MR.col_context(q, k, v, pad, H, general=True)
 
 
@@ -140,33 +141,33 @@ def test_col_attn_dropout_vs_fp64_with_the_host_mask(R, L, p):
     print(f"col R={R} L={L} p={p}: the mask moves {share:.2f} of the unpadded elements out of the tolerance")
     assert share >= 0.5
     ctx = torch.empty(B * R * L, H * 64, dtype=torch.bfloat16, device=DEV)
-    hip.call("oneprot_msa_col_attn_dropout", qkv.to(DEV), MG._key_bias(ids), ctx, B, R, L, H, 64, 64 ** -0.5, p, SEED, stream)
+    hip.call("oneprot_msa_col_attn_dropout", qkv.to(DEV), MC._key_bias(ids), ctx, B, R, L, H, 64, 64 ** -0.5, p, SEED, stream)
     torch.cuda.synchronize()
     ctx = ctx.view(B, R, L, H * 64)
     assert torch.isfinite(ctx).all()
     sel = live[:, None, :, None].expand_as(c_drop)
-    check(torch.where(sel.to(DEV), ctx.float(), torch.zeros((), device=DEV)), torch.where(sel, c_drop, torch.zeros((), dtype=F64)), RTOL, ATOL,
+    close(torch.where(sel.to(DEV), ctx.float(), torch.zeros((), device=DEV)), torch.where(sel, c_drop, torch.zeros((), dtype=F64)), RTOL, ATOL,
           f"col ctx dropout R={R} L={L} p={p}")
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4: p = 0 and the refusals
 def test_p_zero_equals_the_undropped_calls_and_bad_arguments_are_refused():
     from oneprot_amd import hip
-    shape, lens, rows, holes = MG.ROW_CASES[1]
+    shape, lens, rows, holes = MC.ROW_CASES[1]
     B, R, L, H = shape
     ids, qkv = _row_inputs(shape, lens, rows, holes)
-    S, plain = MG._row(qkv, ids, H)
+    S, plain = MC._row(qkv, ids, H)
     for p in (0.0, 2.0 ** -18):                           # below 2^-17: thr16 = 0, no dropout at all
         assert torch.equal(_row_drop(qkv, ids, H, p, _stream(5), S=S)[1], plain)
     ids_c, qkv_c = _col_inputs(17, 33)
-    kb, qd = MG._key_bias(ids_c), qkv_c.to(DEV)
+    kb, qd = MC._key_bias(ids_c), qkv_c.to(DEV)
     got = torch.empty(2 * 17 * 33, 128, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_msa_col_attn_dropout", qd, kb, got, 2, 17, 33, 2, 64, 0.125, 0.0, SEED, _stream(6))
     torch.cuda.synchronize()
-    assert torch.equal(got, MG._col(qkv_c, ids_c, 2))
+    assert torch.equal(got, MC._col(qkv_c, ids_c, 2))
     # refusals, each before any launch: the outputs keep their contents
     h = hip.lib()
-    kbr, qr = MG._key_bias(ids), qkv.to(DEV)
+    kbr, qr = MC._key_bias(ids), qkv.to(DEV)
     ctx = torch.full((B * R * L, H * 64), 3.0, dtype=torch.bfloat16, device=DEV)
     ws = torch.full((hip.query("oneprot_msa_row_context_workspace", B, R, L, H),), 7, dtype=torch.uint8, device=DEV)
     row = lambda p, b_first, B_=B: h.oneprot_msa_row_context_dropout(S.data_ptr(), qr.data_ptr(), kbr.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel(), B_, R, L,
@@ -187,7 +188,7 @@ def test_p_zero_equals_the_undropped_calls_and_bad_arguments_are_refused():
 # ---------------------------------------------------------------------------------------------------------------- 5: the tower
 def _encoder(tmp_path, use_all_msa=True, pooling="mean", proj="linear"):
     from src.models.components.msa_encoder import MsaEncoder
-    enc = MsaEncoder(MG._checkpoint(tmp_path), output_dim=64, pooling_type=pooling, proj_type=proj, use_all_msa=use_all_msa)
+    enc = MsaEncoder(MC._checkpoint(tmp_path), output_dim=64, pooling_type=pooling, proj_type=proj, use_all_msa=use_all_msa)
     sd = {k: v.detach().clone() for k, v in enc.state_dict().items()}
     return enc.to(DEV), sd
 
@@ -196,13 +197,13 @@ def _masks(tr, call, shape, seed):
     return DR.tower_masks(functools.partial(tr._drop_stream, call), shape, tr.d, tr.f, tr.H, tr.n_layers, tr._drop_probs(), seed)
 
 
-@pytest.mark.parametrize("shape,lens,rows", MG.E2E, ids=[str(c[0]) for c in MG.E2E])
+@pytest.mark.parametrize("shape,lens,rows", MC.E2E, ids=[str(c[0]) for c in MC.E2E])
 def test_tower_dropout_vs_restatement_with_every_mask_rebuilt(tmp_path, shape, lens, rows):
     """The gates of test_msa_encoder_vs_restatement.  The encoder's features are taken from row 0 / position 0 (cls): a mean over every token would average
     the dropout away and the guard on the features could not tell a tower that ignores its masks."""
     enc, sd = _encoder(tmp_path, use_all_msa=False, pooling="cls")
     tr = enc.transformer
-    tok = MG._tokens(*shape, lens, rows, 9)
+    tok = MC._tokens(*shape, lens, rows, 9)
     tr.set_rng_state({"_drop_seed": SEED, "_drop_calls": 0})
     enc.train_dropout = True
     enc.train()
@@ -237,8 +238,8 @@ def test_tower_dropout_vs_restatement_with_every_mask_rebuilt(tmp_path, shape, l
 # ---------------------------------------------------------------------------------------------------------------- 6: determinism and state
 def test_same_seed_and_call_repeat_bit_for_bit_and_the_state_restores(tmp_path, monkeypatch):
     from oneprot_amd.msa import MsaTransformer, plan_groups
-    tr = MsaTransformer.from_pretrained(MG._checkpoint(tmp_path)).to(DEV)
-    tok = MG._tokens(3, 4, 50, [50, 31, 45], [4, 2, 3], 2).to(DEV)
+    tr = MsaTransformer.from_pretrained(MC._checkpoint(tmp_path)).to(DEV)
+    tok = MC._tokens(3, 4, 50, [50, 31, 45], [4, 2, 3], 2).to(DEV)
     monkeypatch.delenv("ONEPROT_MSA_SCORE_BYTES", raising=False)
 
     def run():
@@ -271,7 +272,7 @@ def test_default_is_untouched_and_the_switch_needs_train_mode(tmp_path, monkeypa
     monkeypatch.delenv("ONEPROT_MSA_DROPOUT", raising=False)
     enc, _ = _encoder(tmp_path)
     tr = enc.transformer
-    tok = MG._tokens(2, 5, 70, [70, 44], [5, 3], 9).to(DEV)
+    tok = MC._tokens(2, 5, 70, [70, 44], [5, 3], 9).to(DEV)
     pooled = lambda: enc.hidden_and_pooled(tok, want_hidden=False)[1].clone()
     enc.train()
     assert enc.training and not tr.training
@@ -310,7 +311,7 @@ def test_module_training_step_with_the_switch_on(tmp_path):
     from src.models.oneprot_module import OneProtLitModule
     torch.manual_seed(0)
     seq = SequenceEncoder("facebook/esm2_t6_8M_UR50D", output_dim=64, pooling_type="mean", proj_type="mlp", use_lora=False, frozen=False)
-    msa = MsaEncoder(MG._checkpoint(tmp_path), output_dim=64, pooling_type="mean", proj_type="mlp", use_logit_scale=True, use_all_msa=True)
+    msa = MsaEncoder(MC._checkpoint(tmp_path), output_dim=64, pooling_type="mean", proj_type="mlp", use_logit_scale=True, use_all_msa=True)
     msa.train_dropout = True
     module = OneProtLitModule(components={"sequence": seq, "msa": msa}, optimizer=functools.partial(FusedAdam, lr=1e-3), loss_fn="CLIP").to(DEV)
     before = msa.transformer.flat.detach().clone()

@@ -42,8 +42,8 @@ import pytest
 import torch
 
 from tests import msa_ref as MR
-from tests import test_msa_gpu as MG
-from tests.test_msa_gpu import DEV, F64, _col, _ids, _qkv, _row, _split, _tokens, check
+from tests.gate import close
+from tests.msa_cases import DEV, F64, FFN_SELF_DIFFERENCE_GROUPED, GROUPED, _checkpoint, _col, _ids, _qkv, _row, _split, _tokens, bf
 
 pytestmark = pytest.mark.gpu
 BF16_GATE = (2 ** -7, 2e-2)
@@ -51,10 +51,6 @@ BF16_GATE = (2 ** -7, 2e-2)
 
 def f32_gate(K):
     return 1e-4, 1e-3 * math.sqrt(K / 64)
-
-
-def bf(t):
-    return t.to(torch.bfloat16).to(F64)
 
 
 def _check_row(shape, ids, qkv):
@@ -65,8 +61,8 @@ def _check_row(shape, ids, qkv):
     assert not bool(pad[:, 0].all(dim=1).any())                          # row 0 holds a key in every MSA: excluded and -10000-biased keys are the same thing
     q, k, v = _split(qkv, B, R, L, H)
     S64 = MR.row_scores(q, k, pad, H)
-    check(S, S64, *f32_gate(R * 64), f"S {shape}")
-    check(ctx.view(B, R, L, H * 64), MR.row_context(S64, v, pad, H), *BF16_GATE, f"row ctx {shape}")
+    close(S, S64, *f32_gate(R * 64), f"S {shape}")
+    close(ctx.view(B, R, L, H * 64), MR.row_context(S64, v, pad, H), *BF16_GATE, f"row ctx {shape}")
     return S64
 
 
@@ -80,7 +76,7 @@ def _check_col(shape, ids, qkv):
     c64 = MR.col_context(q, k, v, pad, H, general=True)
     sel = (~pad).any(dim=1)[:, None, :, None].expand_as(c64)
     zero = torch.zeros((), dtype=F64)
-    check(torch.where(sel, ctx.cpu().to(F64), zero), torch.where(sel, c64, zero), *BF16_GATE, f"col ctx {shape}")
+    close(torch.where(sel, ctx.cpu().to(F64), zero), torch.where(sel, c64, zero), *BF16_GATE, f"col ctx {shape}")
     return q, k
 
 
@@ -145,7 +141,7 @@ def test_embed_edges(L, d, spare):
     hip.call("oneprot_msa_embed_fwd", tok.to(DEV), *[sd[k].to(DEV).contiguous() for k in sd], x, B, R, L, d, V, n_pos, rows_tab, 1, 1e-5)
     torch.cuda.synchronize()
     x = x.view(B, R, L, d).cpu()
-    check(x, MR.embed(tok, {k: v.to(F64) for k, v in sd.items()}), 1e-5, 1e-5, f"msa embed L={L} d={d}")
+    close(x, MR.embed(tok, {k: v.to(F64) for k, v in sd.items()}), 1e-5, 1e-5, f"msa embed L={L} d={d}")
     assert bool((x[tok.eq(1)] == 0).all())
 
 
@@ -289,12 +285,8 @@ def test_padded_column_keys_leave_column_context_bit_identical():
 WIDE = dict(layers=1, embed_dim=768, ffn_embed_dim=3072, attention_heads=12, max_positions=64, embed_positions_msa=True)      # one layer of the published width
 
 
-GROUPED = ((3, 4, 50), [50, 31, 45], [2, 4, 3], 23)                     # _tokens arguments of test_tower_stages_one_msa_per_group
-FFN_SELF_DIFFERENCE_GROUPED = 9.44e-3                                   # recomputed by tests/test_msa_cpu.py::test_ffn_gate_of_the_grouped_stage_test_is_the_measured_one
-
-
 def _wide_checkpoint(tmp_path):
-    return MG._checkpoint(tmp_path, seed=1, arch=WIDE, name="msa_wide.pt", std=0.05)
+    return _checkpoint(tmp_path, seed=1, arch=WIDE, name="msa_wide.pt", std=0.05)
 
 
 def _check_stages(tr, tok, ffn_atol=None):
@@ -317,13 +309,13 @@ def _check_stages(tr, tok, ffn_atol=None):
     assert not bool(pad[:, 0].all(dim=1).any())
     v4 = lambda t: t.to(F64).view(B, R, L, -1)
     zero = torch.zeros((), dtype=F64)
-    check(v4(st[0][2]), MR.embed(tok, sd), 1e-5, 1e-5, "embedding")
+    close(v4(st[0][2]), MR.embed(tok, sd), 1e-5, 1e-5, "embedding")
     xs, ins = [s for s in st if "." not in s[0]], [s for s in st if "." in s[0]]
     a = 0
     for (kind, i, x_in), (_, _, x_next) in zip(xs, xs[1:]):
         x_in, x_next, tag = v4(x_in), v4(x_next), f"layer {i} {kind}"
         if kind == "ffn":
-            check(x_next, MR.ffn(x_in, sd, i, rnd=bf), 1e-4, f32_gate(f)[1] if ffn_atol is None else ffn_atol, tag)
+            close(x_next, MR.ffn(x_in, sd, i, rnd=bf), 1e-4, f32_gate(f)[1] if ffn_atol is None else ffn_atol, tag)
             continue
         blk = {"row": "row_self_attention", "col": "column_self_attention"}[kind]
         (name, _, t_in), (ck, ci, ctx) = ins[a], cap[a]
@@ -332,16 +324,16 @@ def _check_stages(tr, tok, ffn_atol=None):
         proj = MR.qkv_proj(x_in, sd, i, blk, rnd=bf)
         if name.endswith(".v"):                                           # one row: the column attention is the v projection
             assert torch.equal(t_in, ctx)
-            check(v4(ctx), proj[..., 2 * d:], *BF16_GATE, tag + " ctx = v_proj")
+            close(v4(ctx), proj[..., 2 * d:], *BF16_GATE, tag + " ctx = v_proj")
         else:
-            check(v4(t_in), proj, *BF16_GATE, tag + " qkv")
+            close(v4(t_in), proj, *BF16_GATE, tag + " qkv")
             q, k, v = v4(t_in).chunk(3, dim=-1)
             if kind == "row":
-                check(v4(ctx), MR.row_context(MR.row_scores(q, k, pad, H), v, pad, H), *BF16_GATE, tag + " ctx")
+                close(v4(ctx), MR.row_context(MR.row_scores(q, k, pad, H), v, pad, H), *BF16_GATE, tag + " ctx")
             else:
                 sel = (~pad).any(dim=1)[:, None, :, None].expand(B, R, L, d)
-                check(torch.where(sel, v4(ctx), zero), torch.where(sel, MR.col_context(q, k, v, pad, H), zero), *BF16_GATE, tag + " ctx")
-        check(x_next, MR.attn_out(x_in, v4(ctx), sd, i, blk), *f32_gate(d), tag + " out-projection")
+                close(torch.where(sel, v4(ctx), zero), torch.where(sel, MR.col_context(q, k, v, pad, H), zero), *BF16_GATE, tag + " ctx")
+        close(x_next, MR.attn_out(x_in, v4(ctx), sd, i, blk), *f32_gate(d), tag + " out-projection")
     assert a == len(ins) == len(cap)
 
 
@@ -357,7 +349,7 @@ def test_tower_stages_at_published_width(tmp_path):
 
 def test_tower_stages_one_row(tmp_path):
     from oneprot_amd.msa import MsaTransformer
-    tr = MsaTransformer.from_pretrained(MG._checkpoint(tmp_path)).to(DEV)
+    tr = MsaTransformer.from_pretrained(_checkpoint(tmp_path)).to(DEV)
     _check_stages(tr, _tokens(1, 1, 40, [33], [1], 22))
 
 
@@ -367,6 +359,6 @@ def test_tower_stages_one_msa_per_group(tmp_path, monkeypatch):
     from oneprot_amd.msa import MsaTransformer, plan_groups
     monkeypatch.setenv("ONEPROT_MSA_SCORE_BYTES", "1")
     assert len(plan_groups(3, 4, 50, 2)) == 3
-    tr = MsaTransformer.from_pretrained(MG._checkpoint(tmp_path)).to(DEV)
+    tr = MsaTransformer.from_pretrained(_checkpoint(tmp_path)).to(DEV)
     shape, lens, rows, seed = GROUPED
     _check_stages(tr, _tokens(*shape, lens, rows, seed), ffn_atol=4 * FFN_SELF_DIFFERENCE_GROUPED)

@@ -4,7 +4,6 @@ identically to both, batch independence and grouping bit for bit, MsaEncoder end
 Tolerances are the project's (tests/test_gemm_small_shapes_gpu.py): fp32 outputs rtol 1e-4, atol 1e-3 * sqrt(K / 64) -- K = R * 64 for the tied scores --;
 bf16 outputs rtol 2^-7, atol 2e-2, which covers the bf16 rounding of the probabilities (their rows sum to 1: at most about 2^-9 * max|v|).  A NaN or Inf
 anywhere fails, padded positions included.  Parity with fair-esm itself is unpinned (see tests/msa_ref.py)."""
-import argparse
 import functools
 import math
 import os
@@ -15,81 +14,10 @@ import torch
 
 from tests import msa_ref as MR
 
+from tests.gate import close
+from tests.msa_cases import DEV, E2E, F64, ROW_CASES, _checkpoint, _col, _ids, _qkv, _row, _split, _tokens
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-F64 = torch.float64
-
-
-def check(got, ref, rtol, atol, msg):
-    assert torch.isfinite(got).all(), f"{msg}: non-finite values"
-    got = got.to(F64).cpu()
-    ref = ref.cpu()
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    n = int(bad.sum())
-    print(f"{msg}: max err {float(err.max()):.3e} (atol {atol:.2e}, ref max {float(ref.abs().max()):.3e})")
-    assert n == 0, f"{msg}: {n}/{bad.numel()} off, max err {float(err.max()):.3e} (atol {atol:.2e}, ref max {float(ref.abs().max()):.3e})"
-
-
-def _ids(B, R, L, lens, rows, holes=()):
-    """token-like ids [B, R, L]: 5 = token, 1 = pad; MSA b has lens[b] columns and rows[b] rows; holes: (b, r, l) single pads"""
-    ids = torch.full((B, R, L), 5, dtype=torch.int64)
-    for b in range(B):
-        ids[b, :, lens[b]:] = 1
-        ids[b, rows[b]:] = 1
-    for b, r, l in holes:
-        ids[b, r, l] = 1
-    return ids
-
-
-def _qkv(B, R, L, H, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(B * R * L, 3 * H * 64, generator=g).to(torch.bfloat16)
-
-
-def _split(qkv, B, R, L, H):
-    q, k, v = qkv.to(F64).view(B, R, L, 3, H * 64).unbind(3)
-    return q, k, v
-
-
-def _key_bias(ids):
-    from oneprot_amd import hip
-    kb = torch.empty(ids.numel(), dtype=torch.float32, device=DEV)
-    hip.call("oneprot_key_padding_bias", ids.to(DEV), kb, ids.numel(), 1)
-    return kb
-
-
-def _row(qkv, ids, H):
-    from oneprot_amd import hip
-    B, R, L = ids.shape
-    kb, qd = _key_bias(ids), qkv.to(DEV)
-    S = torch.empty(B, H, L, L, dtype=torch.float32, device=DEV)
-    ctx = torch.empty(B * R * L, H * 64, dtype=torch.bfloat16, device=DEV)
-    hip.call("oneprot_msa_row_scores", qd, kb, S, B, R, L, H, 64, 64 ** -0.5 / math.sqrt(R))
-    ws = torch.empty(hip.query("oneprot_msa_row_context_workspace", B, R, L, H), dtype=torch.uint8, device=DEV)
-    hip.call("oneprot_msa_row_context", S, qd, kb, ctx, ws, ws.numel(), B, R, L, H, 64)
-    torch.cuda.synchronize()
-    return S, ctx
-
-
-def _col(qkv, ids, H):
-    from oneprot_amd import hip
-    B, R, L = ids.shape
-    ctx = torch.empty(B * R * L, H * 64, dtype=torch.bfloat16, device=DEV)
-    hip.call("oneprot_msa_col_attn", qkv.to(DEV), _key_bias(ids), ctx, B, R, L, H, 64, 64 ** -0.5)
-    torch.cuda.synchronize()
-    return ctx
-
-
-# (B, R, L, H), lens, rows, holes: the smallest shapes that cross every tile edge in L (16 / 32 / 64), take an odd trip count in R and reach L = 1024
-ROW_CASES = [
-    ((1, 1, 5, 1), [5], [1], ()),
-    ((2, 3, 33, 2), [33, 20], [3, 2], ((0, 2, 7),)),                    # interior pad at (r = 2, i = 7) with row 0 not padded there: the q zeroing
-    ((1, 50, 70, 2), [70], [50], ((0, 0, 66), (0, 0, 67), (0, 0, 68), (0, 0, 69))),      # row 0 shorter than the other rows: the key mask is row 0's
-    ((2, 5, 130, 1), [130, 97], [5, 3], ()),
-    ((1, 2, 257, 1), [250], [2], ()),
-    ((1, 4, 1024, 1), [1000], [3], ()),
-]
 
 
 @pytest.mark.parametrize("shape,lens,rows,holes", ROW_CASES, ids=[str(c[0]) for c in ROW_CASES])
@@ -101,9 +29,9 @@ def test_row_scores_and_context_vs_fp64(shape, lens, rows, holes):
     pad = ids.eq(1)
     q, k, v = _split(qkv, B, R, L, H)
     S64 = MR.row_scores(q, k, pad, H)
-    check(S, S64, 1e-4, 1e-3 * math.sqrt(R), f"S {shape}")
+    close(S, S64, 1e-4, 1e-3 * math.sqrt(R), f"S {shape}")
     c64 = MR.row_context(S64, v, pad, H)
-    check(ctx.view(B, R, L, H * 64), c64, 2 ** -7, 2e-2, f"row ctx {shape}")
+    close(ctx.view(B, R, L, H * 64), c64, 2 ** -7, 2e-2, f"row ctx {shape}")
 
 
 @pytest.mark.parametrize("L", [1, 33])
@@ -121,7 +49,7 @@ def test_col_attn_vs_fp64(R, L):
     live = (~pad).any(dim=1)                                              # [B, L]: columns with at least one key
     assert not bool(live[1, L - 1])
     sel = live[:, None, :, None].expand_as(c64)
-    check(torch.where(sel.to(DEV), ctx.float(), torch.zeros((), device=DEV)), torch.where(sel, c64, torch.zeros((), dtype=F64)), 2 ** -7, 2e-2, f"col ctx R={R} L={L}")
+    close(torch.where(sel.to(DEV), ctx.float(), torch.zeros((), device=DEV)), torch.where(sel, c64, torch.zeros((), dtype=F64)), 2 ** -7, 2e-2, f"col ctx R={R} L={L}")
 
 
 def test_col_attn_refuses_more_than_128_rows():
@@ -162,45 +90,11 @@ def test_embed_vs_fp64():
     hip.call("oneprot_msa_embed_fwd", tok.to(DEV), *a, x, B, R, L, d, V, max_pos + 2, rows_tab, 1, 1e-5)
     torch.cuda.synchronize()
     ref = MR.embed(tok, {k: v.to(F64) for k, v in sd.items()})
-    check(x.view(B, R, L, d), ref, 1e-5, 1e-5, "msa embed")
+    close(x.view(B, R, L, d), ref, 1e-5, 1e-5, "msa embed")
     assert bool((x.view(B, R, L, d)[tok.eq(1).to(DEV)] == 0).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------- tower / encoder
-ARCH = dict(layers=2, embed_dim=128, ffn_embed_dim=256, attention_heads=2, max_positions=160, embed_positions_msa=True)
-
-
-def _checkpoint(tmp_path, seed=0, arch=ARCH, name="msa_tiny.pt", std=0.08):
-    """a random model (by default the 2-layer ARCH) written as a fair-esm file (encoder.-prefixed keys, row / column swapped), so that the encoder is built
-    through the loader"""
-    from oneprot_amd.msa import MsaTransformer, config_from_args
-    path = os.path.join(str(tmp_path), name)
-    if not os.path.exists(path):
-        torch.manual_seed(seed)
-        tr = MsaTransformer(config_from_args(arch))
-        with torch.no_grad():
-            tr.flat.normal_(0.0, std)
-            for k in tr._spec:
-                if k.endswith("layer_norm.weight") or k.startswith("emb_layer_norm") and k.endswith("weight"):
-                    tr.view(k).add_(1.0)
-        sw = lambda k: k.replace("row", "\0").replace("column", "row").replace("\0", "column")
-        torch.save({"args": argparse.Namespace(arch="msa_transformer", **arch), "model": {"encoder." + sw(k): v.clone() for k, v in tr.state_dict().items()}}, path)
-    return path
-
-
-def _tokens(B, R, L, lens, rows, seed):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randint(4, 30, (B, R, L), generator=g)
-    t[:, :, 0] = 0
-    for b in range(B):
-        t[b, :, lens[b]:] = 1
-        t[b, rows[b]:] = 1
-    return t
-
-
-E2E = [((2, 5, 70), [70, 44], [5, 3]), ((1, 1, 40), [33], [1])]
-
-
 @pytest.mark.parametrize("pooling,proj", [("mean", "linear"), ("cls", "mlp")])
 @pytest.mark.parametrize("use_all_msa", [True, False])
 @pytest.mark.parametrize("shape,lens,rows", E2E, ids=[str(c[0]) for c in E2E])

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from tests import msa_ref as MR
-from tests.test_msa_cpu import _tower, _write_fair_esm_file
+from tests.msa_cases import _tower, _write_fair_esm_file
 
 F64 = torch.float64
 RAGGED_SYMBOLS = ("oneprot_msa_embed_ragged_fwd", "oneprot_msa_row_scores_ragged", "oneprot_msa_row_context_ragged_workspace", "oneprot_msa_row_context_ragged",

@@ -13,7 +13,8 @@ import pytest
 import torch
 
 from tests import msa_ref as MR
-from tests.test_msa_gpu import ARCH, DEV, F64, _checkpoint, _ids, _key_bias, _tokens, check
+from tests.gate import close
+from tests.msa_cases import ARCH, DEV, F64, _checkpoint, _ids, _key_bias, _tokens
 
 pytestmark = pytest.mark.gpu
 
@@ -148,8 +149,8 @@ def _check_row(pk, S_of, ctx, ref, order=None, fp64=True):
         assert torch.equal(S_of[i], S_pad[b, :, :lb, :lb]), f"S of MSA {b} {rb}x{lb} differs from the padded kernel's"
         assert torch.equal(blk, ctx_pad[b, :rb, :lb]), f"row ctx of MSA {b} {rb}x{lb} differs from the padded kernel's"
         if fp64:
-            check(S_of[i], S64[b, :, :lb, :lb], 1e-4, 1e-3 * math.sqrt(R), f"ragged S, MSA {b} {rb}x{lb}")
-            check(blk, c64[b, :rb, :lb], 2 ** -7, 2e-2, f"ragged row ctx, MSA {b} {rb}x{lb}")
+            close(S_of[i], S64[b, :, :lb, :lb], 1e-4, 1e-3 * math.sqrt(R), f"ragged S, MSA {b} {rb}x{lb}")
+            close(blk, c64[b, :rb, :lb], 2 ** -7, 2e-2, f"ragged row ctx, MSA {b} {rb}x{lb}")
 
 
 @pytest.mark.parametrize("which", ["mixed", "L1024"])
@@ -215,7 +216,7 @@ def test_col_attention_ragged_vs_fp64_and_bit_equal_to_padded():
         assert torch.equal(blk[valid], ctx_pad[b, :rb, :lb][valid]), f"col ctx of MSA {b} {rb}x{lb} differs from the padded kernel's"
         sel = live[b, None, :lb, None].expand(rb, lb, H * 64)
         zero64, zero32 = torch.zeros((), dtype=F64, device=DEV), torch.zeros((), device=DEV)
-        check(torch.where(sel, blk.float(), zero32), torch.where(sel, c64[b, :rb, :lb], zero64), 2 ** -7, 2e-2, f"ragged col ctx, MSA {b} {rb}x{lb}")
+        close(torch.where(sel, blk.float(), zero32), torch.where(sel, c64[b, :rb, :lb], zero64), 2 ** -7, 2e-2, f"ragged col ctx, MSA {b} {rb}x{lb}")
         assert bool((blk[:, ~live[b, :lb]] == 0).all())                     # every key masked: 0
 
 
@@ -243,7 +244,7 @@ def test_embed_ragged_bit_equal_to_padded_and_vs_fp64():
     for b, blk in enumerate(pk.unpack(x)):
         rb, lb = pk.shapes[b]
         assert torch.equal(blk, xp.view(B, R, L, d)[b, :rb, :lb]), f"embedding of MSA {b} differs from the padded kernel's"
-        check(blk, ref[b, :rb, :lb], 1e-5, 1e-5, f"ragged embed, MSA {b}")
+        close(blk, ref[b, :rb, :lb], 1e-5, 1e-5, f"ragged embed, MSA {b}")
         assert bool((blk[pk.unpack()[b].eq(1)] == 0).all())
 
 

@@ -12,41 +12,13 @@ import torch
 from oneprot_amd import hip
 from oneprot_amd.packing import PackedTokens
 
+from tests.cases import cu as cu_of, gathered_tables, pack_shape, rope_half
+from tests.gate import cos_sim
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 NAN = float("nan")
-
-
-def _cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
-
-
-def _cu(lengths):
-    c = [0]
-    for n in lengths:
-        c.append(c[-1] + n)
-    return c
-
-
-def _pack_shape(lengths, pad_id=0):
-    p = PackedTokens.from_list([torch.full((n,), 5, dtype=torch.int64) for n in lengths], pad_id=pad_id).to(DEV)
-    return p, p.T_pad, _cu(lengths)
-
-
-def _rope_half(L, hd):
-    inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))
-    f = torch.outer(torch.arange(L, dtype=torch.float32), inv)
-    return f.cos(), f.sin()
-
-
-def _gathered_tables(lengths, T, hd):
-    cos, sin = _rope_half(max(lengths), hd)
-    pos = torch.zeros(T, dtype=torch.long)
-    for a, n in zip(_cu(lengths)[:-1], lengths):
-        pos[a:a + n] = torch.arange(n)
-    return cos[pos].contiguous(), sin[pos].contiguous()
 
 
 def _rc(name, *args):
@@ -64,7 +36,7 @@ def test_dropout_kernels_padded_equals_packed(hd, lengths):
     torch.manual_seed(100 * hd + sum(lengths))
     H, B, L = 2, len(lengths), lengths[0]
     n_real = B * L
-    p, T, cu = _pack_shape(lengths)
+    p, T, cu = pack_shape(lengths, pad_id=0)
     w = p.attn_work()
     scale = hd ** -0.5
     to_padded = lambda x: x[:, :n_real].reshape(H, B, L, -1).transpose(0, 1).contiguous()      # [H, T, *] -> [B, H, L, *]
@@ -73,8 +45,8 @@ def test_dropout_kernels_padded_equals_packed(hd, lengths):
     v = torch.randn(H, T, hd).to(torch.bfloat16).to(DEV)
     dctx = torch.randn(T, H * hd).to(torch.bfloat16).to(DEV)
     q_pad, k_pad, v_pad, dctx_pad = to_padded(q), to_padded(k), to_padded(v), dctx[:n_real].contiguous()
-    cos_pk, sin_pk = (t.to(DEV) for t in _gathered_tables(lengths, T, hd))
-    cos_pad, sin_pad = (t.to(DEV) for t in _rope_half(L, hd))
+    cos_pk, sin_pk = (t.to(DEV) for t in gathered_tables(lengths, T, hd))
+    cos_pad, sin_pad = (t.to(DEV) for t in rope_half(L, hd))
     ws = torch.empty(hip.query("oneprot_attn_varlen_bwd_workspace", H, T), dtype=torch.uint8, device=DEV)
     ws_pad = torch.empty(hip.query("oneprot_attn_bwd_workspace", B, H, L), dtype=torch.uint8, device=DEV)
     for prob in (0.1, 0.5):
@@ -107,7 +79,7 @@ def test_varlen_dropout_vs_float64_with_exported_mask(hd):
     torch.manual_seed(20 + hd)
     lengths, H, prob, seed, stream = [1, 33, 130, 257, 64], 2, 0.5, 1234, 3
     N, Lmax = len(lengths), max(lengths)
-    p, T, cu = _pack_shape(lengths)
+    p, T, cu = pack_shape(lengths, pad_id=0)
     w = p.attn_work()
     scale = hd ** -0.5
     q = (torch.randn(H, T, hd) * scale * hip.LOG2E).to(torch.bfloat16)
@@ -171,7 +143,7 @@ def test_varlen_dropout_vs_float64_with_exported_mask(hd):
 def test_varlen_dropout_refused_arguments():
     H, hd = 2, 16
     lengths = [33, 5]
-    p, T, cu = _pack_shape(lengths)
+    p, T, cu = pack_shape(lengths, pad_id=0)
     w = p.attn_work()
 
     def attempt(hd_, prob, cos=None, sin=None, fwd=True, bwd=True):
@@ -245,7 +217,7 @@ def test_packed_bert_embedding_forward_backward(tmp_path, random_init):
     seqs = _captions(lengths, V, 3)
     seqs[1][2] = seqs[2][10] = seqs[3][1] = 17                     # one token id in three segments
     p = PackedTokens.from_list(seqs, pad_id=0, t_pad=256).to(DEV)
-    T, cu = p.T_pad, _cu(lengths)
+    T, cu = p.T_pad, cu_of(lengths)
     tr = bert.BertTransformer(bert.ModelConfig(**dict(bert.BERT_DEFAULTS, vocab_size=V, hidden_size=d, num_hidden_layers=1, num_attention_heads=4,
                                                       intermediate_size=128, max_position_embeddings=n_pos, layer_norm_eps=eps))).to(DEV)
     e = "embeddings."
@@ -330,7 +302,7 @@ def test_packed_pooling_without_layernorm(mode):
     seqs = _captions(lengths, 120, 11)
     seqs[2][40] = 0                                                               # a pad id inside a segment: left out of the mean, as oneprot_pool_fwd does
     p = PackedTokens.from_list(seqs, pad_id=0).to(DEV)
-    N, T, cu = len(p), p.T_pad, _cu(lengths)
+    N, T, cu = len(p), p.T_pad, cu_of(lengths)
     x = torch.randn(T, d)
     dpooled = torch.randn(N, d)
     pooled = torch.empty(N, d, device=DEV)
@@ -445,7 +417,7 @@ def test_trainable_text_tower_padded_vs_packed(tmp_path, random_init, name, lora
     assert set(g_pad) == set(g_pk) and ("lora" if lora else "arena") in g_pad
     for k_ in g_pad:
         assert float(g_pad[k_].abs().max()) > 0, k_
-        assert _cos(g_pad[k_], g_pk[k_]) >= 0.999, (k_, _cos(g_pad[k_], g_pk[k_]))
+        assert cos_sim(g_pad[k_], g_pk[k_]) >= 0.999, (k_, cos_sim(g_pad[k_], g_pk[k_]))
 
 
 def _golden_encoder(golden_dir, fname, tmp_path, **kw):
@@ -474,7 +446,7 @@ def test_packed_text_encoder_vs_reference(golden_dir, tmp_path, random_init):
         hidden = enc.transformer(input_ids=packed).last_hidden_state.cpu()
     ref_h = g["acts"]["last_hidden"]
     worst = 0.0
-    for b, (a, n) in enumerate(zip(_cu(packed.lengths)[:-1], packed.lengths)):
+    for b, (a, n) in enumerate(zip(cu_of(packed.lengths)[:-1], packed.lengths)):
         worst = max(worst, float((hidden[a:a + n] - ref_h[b, :n]).abs().max()))
     assert worst < 0.05 * ref_h.abs().max()
     cs = torch.nn.functional.cosine_similarity(feats, g["features"], dim=-1)
@@ -500,7 +472,7 @@ def test_packed_trainable_text_encoder_gradients_vs_reference(golden_dir, tmp_pa
         assert k in got, k
         if float(ref.norm()) < 1e-6:
             continue
-        c = _cos(got[k], ref)
+        c = cos_sim(got[k], ref)
         assert c > 0.98, (k, c)
         if float(ref.norm()) > 0.05 * max(float(v.norm()) for v in g["grads"].values()):
             assert c > 0.999, (k, c)
@@ -511,7 +483,7 @@ def test_packed_trainable_text_encoder_gradients_vs_reference(golden_dir, tmp_pa
     unused = [r for r in range(cfg["vocab"]) if r not in set(g["ids"].flatten().tolist())]
     assert float(wg[unused].abs().max()) == 0.0
     allg = torch.cat([got[k].flatten() for k in g["grads"]]); allr = torch.cat([v.flatten() for v in g["grads"].values()])
-    assert _cos(allg, allr) > 0.9995
+    assert cos_sim(allg, allr) > 0.9995
 
 
 # ------------------------------------------------------------------------------------------------------------------ 7. the tower, train mode
@@ -531,7 +503,7 @@ def test_train_mode_attention_dropout_padded_vs_packed(tmp_path, random_init, na
     _assert_features_close(f_pad, f_pk)
     assert abs(l_pad - l_pk) / abs(l_pad) < 1e-3, (l_pad, l_pk)
     for k_ in g_pad:
-        assert _cos(g_pad[k_], g_pk[k_]) >= 0.999, (k_, _cos(g_pad[k_], g_pk[k_]))
+        assert cos_sim(g_pad[k_], g_pk[k_]) >= 0.999, (k_, cos_sim(g_pad[k_], g_pk[k_]))
     enc.eval()
     with torch.no_grad():
         assert not torch.allclose(enc(packed), f_pk, atol=1e-4)     # the dropout did act

@@ -14,42 +14,11 @@ from oneprot_amd.packing import PackedTokens
 pytestmark = pytest.mark.gpu
 
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests.cases import cu as cu_of, esm_dir, gathered_tables, golden_pair_module, pack_shape, rope_half  # noqa: E402
+from tests.gate import cos_sim  # noqa: E402
 
 DEV = "cuda"
 SEG_LENGTHS = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1024, 1026]
-
-
-def _cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
-
-
-def _cu(lengths):
-    c = [0]
-    for n in lengths:
-        c.append(c[-1] + n)
-    return c
-
-
-def _pack_shape(lengths):
-    T = -(-sum(lengths) // 256) * 256
-    p = PackedTokens.from_list([torch.full((n,), 5, dtype=torch.int64) for n in lengths]).to(DEV)
-    return p, T, _cu(lengths)
-
-
-def _rope_half(L, hd):
-    inv = 1.0 / (10000.0 ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))
-    f = torch.outer(torch.arange(L, dtype=torch.float32), inv)
-    return f.cos(), f.sin()
-
-
-def _gathered_tables(lengths, T, hd):
-    """[T, hd/2] rotary tables per token (position within its segment; tail: position 0)"""
-    cos, sin = _rope_half(1026, hd)
-    pos = torch.zeros(T, dtype=torch.long)
-    for a, n in zip(_cu(lengths)[:-1], lengths):
-        pos[a:a + n] = torch.arange(n)
-    return cos[pos].contiguous(), sin[pos].contiguous()
 
 
 def _rot(x, cos, sin):       # x [..., T, hd]; cos / sin [T, hd/2] (half-split layout, hf modeling_esm.py:48-79)
@@ -62,7 +31,7 @@ def _rot(x, cos, sin):       # x [..., T, hd]; cos / sin [T, hd/2] (half-split l
 def test_varlen_attention_forward(hd):
     torch.manual_seed(hd)
     H = 2
-    p, T, cu = _pack_shape(SEG_LENGTHS)
+    p, T, cu = pack_shape(SEG_LENGTHS)
     q = (torch.randn(H, T, hd) * 0.5).to(torch.bfloat16).to(DEV)
     k = torch.randn(H, T, hd).to(torch.bfloat16).to(DEV)
     v = torch.randn(H, T, hd).to(torch.bfloat16).to(DEV)
@@ -86,7 +55,7 @@ def test_varlen_attention_forward_large_scores():
     torch.manual_seed(3)
     H, hd = 2, 32
     lengths = [5, 300, 1026, 77]
-    p, T, cu = _pack_shape(lengths)
+    p, T, cu = pack_shape(lengths)
     qd = torch.randn(H, T, hd)
     kd = torch.randn(H, T, hd)
     qd = qd / qd.norm(dim=-1, keepdim=True)
@@ -119,8 +88,8 @@ def test_varlen_attention_backward(hd):
     torch.manual_seed(10 + hd)
     H = 2
     lengths = [1, 17, 33, 130, 257, 600, 1026]
-    p, T, cu = _pack_shape(lengths)
-    cos, sin = _gathered_tables(lengths, T, hd)
+    p, T, cu = pack_shape(lengths)
+    cos, sin = gathered_tables(lengths, T, hd)
     scale = hd ** -0.5
     q0, k0, v0 = (torch.randn(H, T, hd) for _ in range(3))
     q = (_rot(q0, cos, sin) * scale * hip.LOG2E).to(torch.bfloat16)
@@ -159,7 +128,7 @@ def test_varlen_attention_backward(hd):
     for i, ref in enumerate((q0r.grad, k0r.grad, v0r.grad)):
         got = dqkv[:n_real, i * dm:(i + 1) * dm].view(n_real, H, hd).transpose(0, 1)
         r = ref[:, :n_real]
-        assert _cos(got, r) > 0.999, (i, _cos(got, r))
+        assert cos_sim(got, r) > 0.999, (i, cos_sim(got, r))
         assert (got - r).abs().max() < 0.05 * r.abs().max(), i
 
 
@@ -173,9 +142,9 @@ def test_split_kernels_padded_equals_packed(hd, lengths):
     H, B, L = 2, len(lengths), lengths[0]
     assert all(n == L for n in lengths)
     n_real = B * L
-    p, T, cu = _pack_shape(lengths)
-    cos_pk, sin_pk = _gathered_tables(lengths, T, hd)
-    cos_pad, sin_pad = _rope_half(L, hd)
+    p, T, cu = pack_shape(lengths)
+    cos_pk, sin_pk = gathered_tables(lengths, T, hd)
+    cos_pad, sin_pad = rope_half(L, hd)
     for a in cu[:-1]:
         assert torch.equal(cos_pk[a:a + L], cos_pad) and torch.equal(sin_pk[a:a + L], sin_pad)
     scale = hd ** -0.5
@@ -227,7 +196,7 @@ def test_row_kernels_padded_equals_packed(d):
     torch.manual_seed(7 + d)
     lengths = [1, 7, 33, 130, 257]
     N, L, T, V, hd, PAD, MASK, eps = len(lengths), 257, 512, 33, 32, 1, 32, 1e-5
-    cu = _cu(lengths)
+    cu = cu_of(lengths)
     n_real = cu[-1]
     gen = torch.Generator().manual_seed(11)
     ids_pad = torch.full((N, L), PAD, dtype=torch.int64)
@@ -249,7 +218,7 @@ def test_row_kernels_padded_equals_packed(d):
 
     # ---- embedding: x, the token-dropout factor per token = per row, the gathered rotary rows
     W = torch.randn(V, d).to(DEV)
-    cos_t, sin_t = (t.to(DEV) for t in _rope_half(1026, hd))
+    cos_t, sin_t = (t.to(DEV) for t in rope_half(1026, hd))
     x_pad, row_scale = torch.full((N, L, d), 5.0, device=DEV), torch.empty(N, device=DEV)
     hip.call("oneprot_esm_embed_fwd", ids_pad, W, x_pad, row_scale, N, L, d, V, PAD, MASK, 1)
     x_pk, tok_scale = torch.full((T, d), 5.0, device=DEV), torch.full((T,), 5.0, device=DEV)
@@ -315,7 +284,7 @@ def test_packed_embedding_forward_backward():
     p = PackedTokens.from_list(seqs).to(DEV)
     T, d, V, hd = p.T_pad, 64, 33, 32
     W = torch.randn(V, d)
-    cos_t, sin_t = _rope_half(1026, hd)
+    cos_t, sin_t = rope_half(1026, hd)
     x = torch.full((T, d), 5.0, device=DEV)
     tok_scale = torch.empty(T, device=DEV)
     cos_o, sin_o = torch.empty(T, hd // 2, device=DEV), torch.empty(T, hd // 2, device=DEV)
@@ -329,7 +298,7 @@ def test_packed_embedding_forward_backward():
     x, cos_o, sin_o = x.cpu(), cos_o.cpu(), sin_o.cpu()
     Wr = W.clone().requires_grad_()
     loss = 0.0
-    cu = _cu(lengths)
+    cu = cu_of(lengths)
     for a, n, s in zip(cu[:-1], lengths, seqs):
         ref = O.esm_embeddings(s[None], torch.ones(1, n, dtype=torch.int64), Wr, 32, True)[0]
         assert (x[a:a + n] - ref.detach()).abs().max() < 1e-5, n
@@ -345,7 +314,7 @@ def test_packed_embedding_forward_backward():
 def test_segment_layernorm_pooling(mode):
     torch.manual_seed(5)
     lengths = [3, 1, 64, 257, 1026, 40]
-    p, T, cu = _pack_shape(lengths)
+    p, T, cu = pack_shape(lengths)
     d, eps = 128, 1e-5
     x = torch.randn(T, d)
     gamma, beta = 1 + 0.1 * torch.randn(d), 0.1 * torch.randn(d)
@@ -398,34 +367,6 @@ def test_segment_layernorm_pooling(mode):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. reference goldens
-def _write_cfg(tmp, cfg):
-    path = os.path.join(tmp, "esm")
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(dict(model_type="esm", vocab_size=cfg["vocab"], hidden_size=cfg["hidden"], num_hidden_layers=cfg["layers"],
-                       num_attention_heads=cfg["heads"], intermediate_size=cfg["ffn"], pad_token_id=cfg["pad"], mask_token_id=cfg["mask"],
-                       layer_norm_eps=cfg["eps"], token_dropout=True, position_embedding_type="rotary", emb_layer_norm_before=False), f)
-    return path
-
-
-def _golden_module(golden_dir, tag, tmp_path, frozen_seq=False):
-    os.environ.update(RANK="0", WORLD_SIZE="1")
-    from src.models.components.sequence_encoder import SequenceEncoder
-    from src.models.components.struct_token_encoder import StructTokenEncoder
-    from src.models.oneprot_module import OneProtLitModule
-    from oneprot_amd.optim import FusedAdam
-    g = torch.load(os.path.join(golden_dir, f"esm_pair_{tag}.pt"), weights_only=False)
-    cfg = g["cfg"]
-    p = _write_cfg(str(tmp_path), cfg)
-    seq = SequenceEncoder(p, output_dim=cfg["output_dim"], pooling_type="mean", proj_type="mlp", use_lora=False, frozen=frozen_seq)
-    st = StructTokenEncoder(p, output_dim=cfg["output_dim"], pooling_type="mean", proj_type="linear", use_logit_scale=True, learnable_logit_scale=False)
-    seq.load_state_dict(g["sd_seq"], strict=True)
-    st.load_state_dict(g["sd_st"], strict=True)
-    module = OneProtLitModule(components={"sequence": seq, "struct_token": st}, optimizer=functools.partial(FusedAdam, lr=1e-3, weight_decay=0.0),
-                              loss_fn="CLIP", use_l1_regularization=True, local_loss=True, gather_with_grad=True).to(DEV)
-    return g, module
-
-
 @pytest.fixture
 def random_init(monkeypatch):
     monkeypatch.setenv("ONEPROT_ALLOW_RANDOM_INIT", "1")
@@ -433,7 +374,7 @@ def random_init(monkeypatch):
 
 @pytest.mark.parametrize("tag", ["hd16", "hd24", "hd32"])
 def test_packed_forward_features_vs_reference(golden_dir, tag, tmp_path, random_init):
-    g, module = _golden_module(golden_dir, tag, tmp_path)
+    g, module = golden_pair_module(golden_dir, tag, tmp_path)
     pad = g["cfg"]["pad"]
     with torch.no_grad():
         sf = module(PackedTokens.from_padded(g["seq_ids"], pad_id=pad).to(DEV), "sequence").cpu()
@@ -448,7 +389,7 @@ def test_packed_forward_features_vs_reference(golden_dir, tag, tmp_path, random_
 
 @pytest.mark.parametrize("tag,frozen_seq", [("hd16", False), ("hd24", False), ("hd32", False), ("hd32", True)])
 def test_packed_training_substep_vs_reference(golden_dir, tag, frozen_seq, tmp_path, random_init):
-    g, module = _golden_module(golden_dir, tag, tmp_path, frozen_seq=frozen_seq)
+    g, module = golden_pair_module(golden_dir, tag, tmp_path, frozen_seq=frozen_seq)
     pad = g["cfg"]["pad"]
     batch = {"struct_token": (PackedTokens.from_padded(g["seq_ids"], pad_id=pad).to(DEV), PackedTokens.from_padded(g["st_ids"], pad_id=pad).to(DEV),
                               "struct_token", None)}
@@ -477,12 +418,12 @@ def test_packed_training_substep_vs_reference(golden_dir, tag, frozen_seq, tmp_p
         assert not any(k.startswith("seq.transformer.") for k in grads)
     big = max(float(g["grads"][k].norm()) for k in keys)
     for k in keys:
-        c = _cos(grads[k], g["grads"][k])
+        c = cos_sim(grads[k], g["grads"][k])
         assert c > 0.98, (k, c)
         if float(g["grads"][k].norm()) >= 0.01 * big:
             assert c > 0.999, (k, c)
     allg = torch.cat([grads[k].flatten() for k in keys]); allr = torch.cat([g["grads"][k].flatten() for k in keys])
-    assert _cos(allg, allr) > 0.9999
+    assert cos_sim(allg, allr) > 0.9999
     if frozen_seq:
         return            # the reference's post-Adam weights are those of the trainable form
     gn = float(module.last_grad_norm)
@@ -501,14 +442,6 @@ def test_packed_training_substep_vs_reference(golden_dir, tag, frozen_seq, tmp_p
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6. padded against packed
-def _esm_dir(tmp, name, layers, hidden, heads, ffn):
-    path = os.path.join(str(tmp), name)
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(dict(model_type="esm", vocab_size=33, hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=ffn), f)
-    return path
-
-
 def _pair_module(path, lora=False, seed=0):
     os.environ.update(RANK="0", WORLD_SIZE="1")
     from oneprot_amd.encoders import SequenceEncoder, StructTokenEncoder
@@ -542,7 +475,7 @@ def _substep_with_grads(module, batch):
 def test_padded_vs_packed_substep_150m_shape(tmp_path, random_init, lora):
     """ESM-2-150M layer shape (640 wide, 20 heads of 32, 30 layers) on ragged synthetic data, random init: the same sub-step in both layouts"""
     from oneprot_amd.data import SyntheticPairs
-    path = _esm_dir(tmp_path, "esm150", 30, 640, 20, 2560)
+    path = esm_dir(tmp_path, "esm150", 30, 640, 20, 2560)
     rag = next(iter(SyntheticPairs("struct_token", 24, 512, seed=21, ragged=True)))
     pk = next(iter(SyntheticPairs("struct_token", 24, 512, seed=21, packed=True)))
     m_pad = _pair_module(path, lora=lora)
@@ -553,14 +486,14 @@ def test_padded_vs_packed_substep_150m_shape(tmp_path, random_init, lora):
     assert abs(l_pad - l_pk) / abs(l_pad) < 1e-3, (l_pad, l_pk)
     assert set(g_pad) == set(g_pk) and len(g_pad) >= 2
     for k in g_pad:
-        assert _cos(g_pad[k], g_pk[k]) >= 0.999, (k, _cos(g_pad[k], g_pk[k]))
+        assert cos_sim(g_pad[k], g_pk[k]) >= 0.999, (k, cos_sim(g_pad[k], g_pk[k]))
 
 
 def test_padded_vs_packed_forward_650m_attention1d(tmp_path, random_init):
     """ESM-2-650M layer shape (1280 wide, 20 heads of 64; 6 of its 33 layers) with attention1d pooling, forward only"""
     from oneprot_amd.data import SyntheticPairs
     from oneprot_amd.encoders import SequenceEncoder
-    path = _esm_dir(tmp_path, "esm650", 6, 1280, 20, 5120)
+    path = esm_dir(tmp_path, "esm650", 6, 1280, 20, 5120)
     torch.manual_seed(2)
     enc = SequenceEncoder(path, output_dim=512, pooling_type="attention1d", proj_type="linear", use_lora=False, frozen=True).to(DEV).eval()
     rag = next(iter(SyntheticPairs("sequence", 16, 512, seed=8, ragged=True)))[0]
@@ -578,7 +511,7 @@ def test_padded_vs_packed_forward_650m_attention1d(tmp_path, random_init):
 # ------------------------------------------------------------------------------------------------------------------ 7. pack composition
 def test_features_independent_of_pack_composition(tmp_path, random_init):
     from oneprot_amd.encoders import SequenceEncoder
-    path = _esm_dir(tmp_path, "esm", 4, 320, 20, 1280)
+    path = esm_dir(tmp_path, "esm", 4, 320, 20, 1280)
     torch.manual_seed(6)
     enc = SequenceEncoder(path, output_dim=128, pooling_type="mean", proj_type="mlp", use_lora=False, frozen=True).to(DEV)
     gen = torch.Generator().manual_seed(1)
@@ -598,7 +531,7 @@ def test_mixed_pair_packed_esm_padded_bert(tmp_path, random_init):
     from oneprot_amd.module import OneProtLitModule
     from oneprot_amd.optim import FusedAdam
     os.environ.update(RANK="0", WORLD_SIZE="1")
-    esm = _esm_dir(tmp_path, "esm", 4, 320, 20, 1280)
+    esm = esm_dir(tmp_path, "esm", 4, 320, 20, 1280)
     bert = os.path.join(str(tmp_path), "bert")
     os.makedirs(bert)
     with open(os.path.join(bert, "config.json"), "w") as f:

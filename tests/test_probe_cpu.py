@@ -9,23 +9,15 @@ import torch
 
 from oneprot_amd import hip, probe
 from tests import probe_ref as R
+from tests.gate import rel_l2
+from tests.probe_cases import GOLDEN, make
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "probe_mlp.pt")
 U = 2.0 ** -24
 
 
 @pytest.fixture(scope="module")
 def golden():
     return torch.load(GOLDEN, map_location="cpu", weights_only=False)
-
-
-def make(cfg, g, dropout_rate=0.0):
-    return probe.MLP(g["input_dim"], g["output_dim"], cfg["hidden_dims"], dropout_rate, cfg["norm"] == "batch", cfg["norm"] == "layer", cfg["activation"], cfg["use_residual"])
-
-
-def rel_l2(a, ref):
-    a, ref = a.detach().double(), ref.detach().double()
-    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
 def test_state_dict_names_and_shapes_equal_the_reference(golden):

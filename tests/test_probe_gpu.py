@@ -20,7 +20,8 @@ import torch.nn.functional as F
 from oneprot_amd import downstream, hip, probe
 from oneprot_amd.optim import FusedAdamW
 from tests import probe_ref as R
-from tests.test_probe_cpu import GOLDEN, make
+from tests.gate import rel_l2
+from tests.probe_cases import GOLDEN, make
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,11 +33,6 @@ N_EDGES = (1, 10, 15, 16, 17, 256, 585)
 K_EDGES = (1, 24, 63, 64, 65, 1280)
 ACT_NAMES = ("relu", "gelu", "leaky_relu", "identity")
 SEED, STREAM = 0x1234ABCD5, (5 << 60) | 77
-
-
-def rel_l2(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
 def check(rows, label):

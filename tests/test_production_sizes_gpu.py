@@ -10,7 +10,6 @@ Tolerances follow from fp32 arithmetic: eps32 = 2^-24 ~ 6e-8 per rounding.  A pe
 sums (1e-5, as in test_kernels_gpu.py); a column sum over T rows in fixed-order partials drifts like eps32 * sqrt(#terms) * sqrt(#partials) * term size,
 for which 1e-5 * sqrt(T) * rms(term) keeps a margin of ten or more.  Every deliberate error these tests guard against (a lost grid-stride pass, a lost
 partial, a mask indexed by thread) is an O(1) fraction of the result, far above them."""
-import gc
 import math
 
 import pytest
@@ -21,38 +20,10 @@ from tests import philox_ref as PR
 pytestmark = pytest.mark.gpu
 
 from oneprot_amd import hip  # noqa: E402
+from tests.cases import DEV, SEED_HI, STREAM_HI, free, gen, randn, ws  # noqa: E402
+from tests.gate import close  # noqa: E402
 
-DEV = "cuda"
 F64 = torch.float64
-SEED_HI, STREAM_HI = (0x5EED << 32) | 0x1234ABCD, (0x3 << 60) | (0x2A << 32) | 0x91      # non-zero high words: both halves of the Philox key / counter
-
-
-def _gen(seed):
-    return torch.Generator(device=DEV).manual_seed(seed)
-
-
-def _randn(shape, g, scale=1.0, shift=0.0, dtype=torch.float32):
-    return (torch.randn(shape, generator=g, device=DEV) * scale + shift).to(dtype)
-
-
-def _ws(nbytes):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=DEV)
-
-
-def _free():
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def check(got, ref, rtol, atol, msg):
-    """|got - ref| <= atol + rtol |ref| elementwise, in fp64 (ref is fp64)"""
-    got = got.to(F64)
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    n = int(bad.sum())
-    assert n == 0, f"{msg}: {n}/{bad.numel()} off, max err {float(err.max()):.3e} (atol {atol:.2e}, ref max {float(ref.abs().max()):.3e}, first at {int(bad.flatten().nonzero()[0])})"
-
-
 def colsum_atol(terms_rms, n):
     """fp32 fixed-order sum of n terms of rms `terms_rms`: rounding drift ~ eps32 * n^(1/2 ... 3/4) * rms; 1e-5 * sqrt(n) * rms bounds it with margin"""
     return 1e-5 * math.sqrt(n) * float(terms_rms) + 1e-30
@@ -77,55 +48,55 @@ def _ln_bwd_ref(dy64, x64, gamma64, mean64, rstd64):
 def test_layernorm_fwd_bwd_production_rows(T, d):
     """k_layernorm_fwd past its 4096 x 4-row grid, k_layernorm_bwd + k_ln_reduce with all 1024 partials each covering many rows; fp32 and bf16 x; every
     dy_mode; add_to separate and in place; the bf16 dx copy; dgamma / dbeta overwritten and accumulated -- against fp64 sums over all rows"""
-    g = _gen(T + d)
+    g = gen(T + d)
     eps = 1e-5
-    gamma, beta = _randn(d, g, 0.2, 1.0), _randn(d, g, 0.2)
+    gamma, beta = randn(d, g, 0.2, 1.0), randn(d, g, 0.2)
     gamma64, beta64 = gamma.to(F64), beta.to(F64)
-    w = _ws(hip.query("oneprot_layernorm_bwd_workspace", d))
+    w = ws(hip.query("oneprot_layernorm_bwd_workspace", d))
     for x_bf16 in (0, 1):
-        x = _randn((T, d), g, 2.0, 0.5, torch.bfloat16 if x_bf16 else torch.float32)
+        x = randn((T, d), g, 2.0, 0.5, torch.bfloat16 if x_bf16 else torch.float32)
         x64 = x.to(F64)
         yb, yf = torch.empty(T, d, dtype=torch.bfloat16, device=DEV), torch.empty(T, d, device=DEV)
         mean, rstd = torch.empty(T, device=DEV), torch.empty(T, device=DEV)
         hip.call("oneprot_layernorm_fwd", x, x_bf16, gamma, beta, yb, yf, mean, rstd, T, d, eps)
         y64, m64, r64 = _ln_ref(x64, gamma64, beta64, eps)
-        check(yf, y64, 1e-5, 1e-5, f"ln fwd f32 (x bf16 {x_bf16})")
-        check(yb, y64, 2 ** -8, 1e-6, f"ln fwd bf16 copy (x bf16 {x_bf16})")      # one bf16 rounding of the fp32 value
-        check(mean, m64, 1e-5, 1e-6, "mean")
-        check(rstd, r64, 1e-5, 0.0, "rstd")
+        close(yf, y64, 1e-5, 1e-5, f"ln fwd f32 (x bf16 {x_bf16})")
+        close(yb, y64, 2 ** -8, 1e-6, f"ln fwd bf16 copy (x bf16 {x_bf16})")      # one bf16 rounding of the fp32 value
+        close(mean, m64, 1e-5, 1e-6, "mean")
+        close(rstd, r64, 1e-5, 0.0, "rstd")
         del yb, yf, y64
         # dy_mode 1 (fp32 dy), separate add_to, fresh dgamma / dbeta
-        dy = _randn((T, d), g)
-        add = _randn((T, d), g)
+        dy = randn((T, d), g)
+        add = randn((T, d), g)
         dx, dx16 = torch.empty(T, d, device=DEV), torch.empty(T, d, dtype=torch.bfloat16, device=DEV)
         dg, db = torch.full((d,), 7.0, device=DEV), torch.full((d,), -3.0, device=DEV)
         hip.call("oneprot_layernorm_bwd", dy, 1, None, 0, x, x_bf16, gamma, mean, rstd, add, dx, None, dg, db, w, T, d, 0)
         dx64, dg64, db64, rg, rb = _ln_bwd_ref(dy.to(F64), x64, gamma64, m64, r64)
-        check(dx, dx64 + add.to(F64), 1e-4, 1e-4, "ln bwd dx (dy f32, add_to)")
-        check(dg, dg64, 1e-5, colsum_atol(rg, T), "ln bwd dgamma (dy f32)")
-        check(db, db64, 1e-5, colsum_atol(rb, T), "ln bwd dbeta (dy f32)")
+        close(dx, dx64 + add.to(F64), 1e-4, 1e-4, "ln bwd dx (dy f32, add_to)")
+        close(dg, dg64, 1e-5, colsum_atol(rg, T), "ln bwd dgamma (dy f32)")
+        close(db, db64, 1e-5, colsum_atol(rb, T), "ln bwd dbeta (dy f32)")
         # dy_mode 0 (bf16 dy), in place on the residual gradient, bf16 copy of dx, accumulated into the previous dgamma / dbeta
         dyb = dy.to(torch.bfloat16)
         dx2 = add.clone()
         hip.call("oneprot_layernorm_bwd", dyb, 0, None, 0, x, x_bf16, gamma, mean, rstd, dx2, dx2, dx16, dg, db, w, T, d, 1)
         dx64b, dg64b, db64b, rg, rb = _ln_bwd_ref(dyb.to(F64), x64, gamma64, m64, r64)
-        check(dx2, dx64b + add.to(F64), 1e-4, 1e-4, "ln bwd dx (dy bf16, in place)")
+        close(dx2, dx64b + add.to(F64), 1e-4, 1e-4, "ln bwd dx (dy bf16, in place)")
         assert torch.equal(dx16, dx2.to(torch.bfloat16)), "bf16 dx copy is not the rounding of the fp32 dx"
-        check(dg, dg64 + dg64b, 1e-5, 2 * colsum_atol(rg, T), "ln bwd dgamma accumulated")
-        check(db, db64 + db64b, 1e-5, 2 * colsum_atol(rb, T), "ln bwd dbeta accumulated")
+        close(dg, dg64 + dg64b, 1e-5, 2 * colsum_atol(rg, T), "ln bwd dgamma accumulated")
+        close(db, db64 + db64b, 1e-5, 2 * colsum_atol(rb, T), "ln bwd dbeta accumulated")
         del dy, dyb, add, dx2, dx64, dx64b
         # dy_mode 2: dy[t] = dpool[t / L] * wrow[t] (the pooled-gradient broadcast), no add_to
         L = 512
-        dpool = _randn((T // L, d), g)
+        dpool = randn((T // L, d), g)
         wrow = torch.rand(T, generator=g, device=DEV) / L
         hip.call("oneprot_layernorm_bwd", dpool, 2, wrow, L, x, x_bf16, gamma, mean, rstd, None, dx, dx16, dg, db, w, T, d, 0)
         dyp = dpool.to(F64).repeat_interleave(L, 0) * wrow.to(F64)[:, None]
         dx64, dg64, db64, rg, rb = _ln_bwd_ref(dyp, x64, gamma64, m64, r64)
-        check(dx, dx64, 1e-4, 1e-4 * float(dx64.abs().max()), "ln bwd dx (pooled broadcast)")
-        check(dg, dg64, 1e-5, colsum_atol(rg, T), "ln bwd dgamma (pooled broadcast)")
-        check(db, db64, 1e-5, colsum_atol(rb, T), "ln bwd dbeta (pooled broadcast)")
+        close(dx, dx64, 1e-4, 1e-4 * float(dx64.abs().max()), "ln bwd dx (pooled broadcast)")
+        close(dg, dg64, 1e-5, colsum_atol(rg, T), "ln bwd dgamma (pooled broadcast)")
+        close(db, db64, 1e-5, colsum_atol(rb, T), "ln bwd dbeta (pooled broadcast)")
         del x, x64, dx, dx16, dyp, dx64
-        _free()
+        free()
 
 
 def _packed_lengths(g, target, n_min):
@@ -153,13 +124,13 @@ def test_packed_layernorm_pooling_production_stream(d):
     seg = torch.repeat_interleave(torch.arange(N, device=DEV), torch.tensor(lens, device=DEV))
     ids = torch.full((T,), 1, dtype=torch.int64, device=DEV)
     ids[:cu_l[-1]] = torch.randint(4, 24, (cu_l[-1],), generator=gcpu).to(DEV)
-    g = _gen(d)
+    g = gen(d)
     eps = 1e-5
-    x = _randn((T, d), g, 1.5, 0.3)
-    gamma, beta = _randn(d, g, 0.2, 1.0), _randn(d, g, 0.2)
-    pw, pb = _randn(d, g, 0.1), _randn(1, g, 0.1)
-    dpool = _randn((N, d), g)
-    w = _ws(hip.query("oneprot_layernorm_bwd_workspace", d))
+    x = randn((T, d), g, 1.5, 0.3)
+    gamma, beta = randn(d, g, 0.2, 1.0), randn(d, g, 0.2)
+    pw, pb = randn(d, g, 0.1), randn(1, g, 0.1)
+    dpool = randn((N, d), g)
+    w = ws(hip.query("oneprot_layernorm_bwd_workspace", d))
     real = cu_l[-1]
     lens64 = torch.tensor(lens, dtype=F64, device=DEV)
     for mode in ("mean", "cls", "attention1d"):
@@ -187,48 +158,48 @@ def test_packed_layernorm_pooling_production_stream(d):
         if mode == "attention1d":
             hidden = torch.empty(T, d, device=DEV)
             hip.call("oneprot_lnpool_packed_fwd", x, ids, cu, 1, gamma, beta, pooled, mean, rstd, wrow, hidden, N, T, d, eps, 0)
-            check(hidden, h.detach(), 1e-5, 1e-5, "packed hidden")
+            close(hidden, h.detach(), 1e-5, 1e-5, "packed hidden")
             attn = torch.empty(T, device=DEV)
             hip.call("oneprot_attnpool_packed_fwd", hidden, ids, cu, 1, pw, pb, pooled, attn, N, max(lens), d)
             dh = torch.full((T, d), 9.0, device=DEV)
             dw, dbias = torch.empty(d, device=DEV), torch.empty(1, device=DEV)
-            hip.call("oneprot_attnpool_packed_bwd", hidden, attn, cu, pw, dpool, dw, dbias, dh, _ws(hip.query("oneprot_attnpool_bwd_workspace", N, d)),
+            hip.call("oneprot_attnpool_packed_bwd", hidden, attn, cu, pw, dpool, dw, dbias, dh, ws(hip.query("oneprot_attnpool_bwd_workspace", N, d)),
                      N, T, max(lens), d)
             assert bool((dh[real:] == 0).all()), "attention1d: tail rows of dhidden are not exactly zero"
             hip.call("oneprot_layernorm_bwd", dh, 1, None, 0, x, 0, gamma, mean, rstd, None, dx, dx16, dg, db, w, T, d, 0)
             # the softmax weights carry __expf's relative error (~1e-6 over this range of scores) on top of the fp32 sums over <= 1026 rows
-            check(dw, pwr.grad, 1e-4, colsum_atol(1.0, real) * float(pwr.grad.abs().max()), "attention1d dw")
+            close(dw, pwr.grad, 1e-4, colsum_atol(1.0, real) * float(pwr.grad.abs().max()), "attention1d dw")
             # sum_l ds_l vanishes per segment: the kernel's value is rounding noise of the sum of |ds| terms
-            check(dbias, pbr.grad, 1e-4, colsum_atol(float(s.grad.pow(2).mean().sqrt()), real), "attention1d dbias")
+            close(dbias, pbr.grad, 1e-4, colsum_atol(float(s.grad.pow(2).mean().sqrt()), real), "attention1d dbias")
             prt = 1e-4
         else:
             hip.call("oneprot_lnpool_packed_fwd", x, ids, cu, 1, gamma, beta, pooled, mean, rstd, wrow, None, N, T, d, eps, 0 if mode == "mean" else 1)
             hip.call("oneprot_lnpool_packed_bwd", dpool, cu, wrow, x, gamma, mean, rstd, dx, dx16, dg, db, w, N, T, d)
             prt = 1e-5
-        check(pooled, ref.detach(), prt, 1e-5, f"packed pooled ({mode})")
+        close(pooled, ref.detach(), prt, 1e-5, f"packed pooled ({mode})")
         _, m64, r64 = _ln_ref(x.to(F64), gamma.to(F64), beta.to(F64), eps)
-        check(mean, m64, 1e-5, 1e-6, f"packed mean ({mode})")
-        check(rstd, r64, 1e-5, 0.0, f"packed rstd ({mode})")
+        close(mean, m64, 1e-5, 1e-6, f"packed mean ({mode})")
+        close(rstd, r64, 1e-5, 0.0, f"packed rstd ({mode})")
         assert bool((wrow[real:] == 0).all()), f"{mode}: tail rows carry a pooling weight"
         assert bool((dx[real:] == 0).all()) and bool((dx16[real:] == 0).all()), f"{mode}: tail rows of dx are not exactly zero"
         # dx per row: cancellation inside rstd * (g - mean(g) - xhat mean(g xhat)) leaves errors of a few eps32 * d^(1/2) of the row's largest term
-        check(dx[:real], xr.grad[:real], 1e-4, 4e-5 * float(xr.grad.abs().max()), f"packed dx ({mode})")
+        close(dx[:real], xr.grad[:real], 1e-4, 4e-5 * float(xr.grad.abs().max()), f"packed dx ({mode})")
         xh = (x.to(F64) - m64[:, None]) * r64[:, None]
         ref_dg, ref_db = gr.grad, br.grad
         term = float(dpool.abs().max()) * (1.0 if mode != "mean" else 1.0 / min(lens))
-        check(dg, ref_dg, 1e-5, colsum_atol(term * float(xh.abs().max()), real), f"packed dgamma ({mode})")
-        check(db, ref_db, 1e-5, colsum_atol(term, real), f"packed dbeta ({mode})")
+        close(dg, ref_dg, 1e-5, colsum_atol(term * float(xh.abs().max()), real), f"packed dgamma ({mode})")
+        close(db, ref_db, 1e-5, colsum_atol(term, real), f"packed dbeta ({mode})")
         del xr, h, hs, ref, xh
-        _free()
+        free()
 
 
 def test_dropout_add_layernorm_fwd_production_rows():
     """oneprot_dropout_add_layernorm_fwd at 40 000 rows of d = 768 (BERT hidden dropout + residual + LayerNorm; the grid caps at 4096 x 4 rows): the sum
     bit for bit against the independent Philox mask, the LayerNorm against fp64"""
     T, d, p, eps = 40000, 768, 0.1, 1e-12
-    g = _gen(768)
-    x, resid = _randn((T, d), g), _randn((T, d), g)
-    gamma, beta = _randn(d, g, 0.1, 1.0), _randn(d, g, 0.1)
+    g = gen(768)
+    x, resid = randn((T, d), g), randn((T, d), g)
+    gamma, beta = randn(d, g, 0.1, 1.0), randn(d, g, 0.1)
     keep = torch.from_numpy(PR.philox_keep(T * d, p, SEED_HI, STREAM_HI)).to(DEV).view(T, d)
     _, scale = PR.dropout_threshold(p)
     s_ref = torch.where(keep, x * float(scale), torch.zeros((), device=DEV)) + resid
@@ -237,43 +208,43 @@ def test_dropout_add_layernorm_fwd_production_rows():
     hip.call("oneprot_dropout_add_layernorm_fwd", x, resid, s, gamma, beta, y16, y, m, r, T, d, eps, p, SEED_HI, STREAM_HI)
     assert torch.equal(s, s_ref), f"sum differs from resid + Philox dropout(x) at {int((s != s_ref).sum())} elements"
     y64, m64, r64 = _ln_ref(s_ref.to(F64), gamma.to(F64), beta.to(F64), eps)
-    check(y, y64, 1e-5, 1e-5, "dropout+LN fp32")
-    check(y16, y64, 2 ** -8, 1e-6, "dropout+LN bf16")
-    check(m, m64, 1e-5, 1e-6, "dropout+LN mean")
-    check(r, r64, 1e-5, 0.0, "dropout+LN rstd")
+    close(y, y64, 1e-5, 1e-5, "dropout+LN fp32")
+    close(y16, y64, 2 ** -8, 1e-6, "dropout+LN bf16")
+    close(m, m64, 1e-5, 1e-6, "dropout+LN mean")
+    close(r, r64, 1e-5, 0.0, "dropout+LN rstd")
 
 
 def test_bert_embed_fwd_production_rows():
     """oneprot_bert_embed_fwd at B x L = 128 x 512 (65 536 rows, past the 16 384-row grid) with the BERT-base table: LayerNorm(word[id] + pos[l] + type0);
     ids out of [0, vocab) read row 0, pad ids (0) embed like any other token"""
     B, L, d, V, eps = 128, 512, 768, 30522, 1e-12
-    g = _gen(30522)
+    g = gen(30522)
     ids = torch.randint(1, V, (B, L), generator=g, device=DEV)
     ids[:, 0] = 101
     ids[5, 300:] = 0
     ids[127, 1:] = 0
     ids[3, 17], ids[100, 511], ids[64, 2] = -1, V, V + 12345
-    word, pos, type0 = _randn((V, d), g, 0.05), _randn((512, d), g, 0.05), _randn(d, g, 0.05)
-    gamma, beta = _randn(d, g, 0.1, 1.0), _randn(d, g, 0.1)
+    word, pos, type0 = randn((V, d), g, 0.05), randn((512, d), g, 0.05), randn(d, g, 0.05)
+    gamma, beta = randn(d, g, 0.1, 1.0), randn(d, g, 0.1)
     xf, xb = torch.empty(B * L, d, device=DEV), torch.empty(B * L, d, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_bert_embed_fwd", ids, word, pos, type0, gamma, beta, xf, xb, B, L, d, V, eps)
     idc = torch.where((ids >= 0) & (ids < V), ids, torch.zeros_like(ids)).view(-1)
     e64 = word.to(F64)[idc] + pos.to(F64).repeat(B, 1) + type0.to(F64)
     y64, _, _ = _ln_ref(e64, gamma.to(F64), beta.to(F64), eps)
-    check(xf, y64, 1e-5, 1e-5, "bert embed fp32")
-    check(xb, y64, 2 ** -8, 1e-6, "bert embed bf16")
+    close(xf, y64, 1e-5, 1e-5, "bert embed fp32")
+    close(xb, y64, 2 ** -8, 1e-6, "bert embed bf16")
 
 
 @pytest.mark.parametrize("mode", [0, 1], ids=["mean", "cls"])
 def test_pool_fwd_bwd_ragged(mode):
     """oneprot_pool_fwd / _bwd (pooling of an already normalised tower output, BERT) at (256, 256, 768) with ragged padding, the bf16 gradient copy"""
     B, L, d, pad = 256, 256, 768, 0
-    g = _gen(256 + mode)
+    g = gen(256 + mode)
     ids = torch.randint(1, 30000, (B, L), generator=g, device=DEV)
     lens = torch.randint(1, L + 1, (B,), generator=g, device=DEV)
     lens[0], lens[1], lens[2] = 1, L, L - 1
     ids[torch.arange(L, device=DEV)[None, :] >= lens[:, None]] = pad
-    x = _randn((B, L, d), g)
+    x = randn((B, L, d), g)
     pooled = torch.empty(B, d, device=DEV)
     hip.call("oneprot_pool_fwd", x, ids, pad, pooled, B, L, d, mode)
     valid = (ids != pad).to(F64)
@@ -283,12 +254,12 @@ def test_pool_fwd_bwd_ragged(mode):
         wt = torch.zeros(B, L, dtype=F64, device=DEV)
         wt[:, 0] = 1.0
     ref = (x.to(F64) * wt[:, :, None]).sum(1)
-    check(pooled, ref, 1e-5, 1e-6, "pool fwd")                # a sum of <= 256 rows per column
-    dp = _randn((B, d), g)
+    close(pooled, ref, 1e-5, 1e-6, "pool fwd")                # a sum of <= 256 rows per column
+    dp = randn((B, d), g)
     gx, g16 = torch.full((B, L, d), 9.0, device=DEV), torch.empty(B, L, d, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_pool_bwd", dp, ids, pad, gx, g16, B, L, d, mode)
     gref = dp.to(F64)[:, None, :] * wt[:, :, None]
-    check(gx, gref, 2e-7, 0.0, "pool bwd")                    # dp * fl(1/n): two roundings
+    close(gx, gref, 2e-7, 0.0, "pool bwd")                    # dp * fl(1/n): two roundings
     assert torch.equal(g16, gx.to(torch.bfloat16))
     assert bool((gx[wt == 0] == 0).all()), "pool bwd writes a gradient on padding"
 
@@ -298,12 +269,12 @@ def test_embed_scatter_sorted_and_rowsum_bert_backward_shapes():
     padding row is skipped and keeps what it held), oneprot_rowsum_f32 for the position rows (sum over the batch) and the token-type row"""
     B, L, d, V, pad = 128, 512, 768, 30522, 0
     T = B * L
-    g = _gen(317)
+    g = gen(317)
     ids = torch.randint(0, 2000, (B, L), generator=g, device=DEV)         # a small id range: runs of up to ~80 equal ids
     ids[:, 0] = 101
     ids[7, 100:] = pad
     ids[9, 3] = V - 1
-    de = _randn((T, d), g)
+    de = randn((T, d), g)
     sorted_ids, perm = torch.sort(ids.reshape(-1), stable=True)
     rows, counts = torch.unique_consecutive(sorted_ids, return_counts=True)
     starts = (torch.cumsum(counts, 0) - counts).contiguous()
@@ -313,36 +284,36 @@ def test_embed_scatter_sorted_and_rowsum_bert_backward_shapes():
     used = torch.zeros(V, dtype=torch.bool, device=DEV)
     used[rows] = True
     used[pad] = False
-    check(table[used], ref[used], 1e-5, colsum_atol(1.0, int(counts.max())), "scatter sorted")
+    close(table[used], ref[used], 1e-5, colsum_atol(1.0, int(counts.max())), "scatter sorted")
     assert bool((table[~used] == 3.25).all()), "rows no token used (or the skipped padding row) were written"
     dpos = torch.full((L + 3, d), -1.0, device=DEV)
     hip.call("oneprot_rowsum_f32", de, dpos[:L], B, L * d)
     ref_pos = de.to(F64).view(B, L * d).sum(0).view(L, d)
-    check(dpos[:L], ref_pos, 1e-5, colsum_atol(1.0, B), "rowsum over the batch")
+    close(dpos[:L], ref_pos, 1e-5, colsum_atol(1.0, B), "rowsum over the batch")
     assert bool((dpos[L:] == -1.0).all())
     tt = torch.empty(d, device=DEV)
     hip.call("oneprot_rowsum_f32", dpos[:L], tt, L, d)
-    check(tt, dpos[:L].to(F64).sum(0), 1e-5, colsum_atol(float(dpos[:L].pow(2).mean().sqrt()), L), "rowsum token type")
+    close(tt, dpos[:L].to(F64).sum(0), 1e-5, colsum_atol(float(dpos[:L].pow(2).mean().sqrt()), L), "rowsum token type")
 
 
 def test_esm_embed_bwd_production_rows():
     """oneprot_esm_embed_bwd at B x L = 256 x 512 (cfg-2) with the token-dropout row scale: ~4000 tokens per vocabulary row through the 512 chunk partials"""
     B, L, d, V = 256, 512, 640, 33
-    g = _gen(33)
+    g = gen(33)
     ids = torch.randint(4, 24, (B, L), generator=g, device=DEV)
     ids[:, 0] = 0
     ids[10, 200:] = 1
     ids[torch.rand(B, L, generator=g, device=DEV) < 0.02] = 32
-    dx = _randn((B * L, d), g)
+    dx = randn((B * L, d), g)
     rs = torch.rand(B, generator=g, device=DEV) + 0.5
     dt = torch.full((V, d), 0.5, device=DEV)
-    hip.call("oneprot_esm_embed_bwd", ids, dx, rs, dt, _ws(hip.query("oneprot_esm_embed_bwd_workspace", B * L, d, V)), B, L, d, V, 1, 32, 1, 1)
+    hip.call("oneprot_esm_embed_bwd", ids, dx, rs, dt, ws(hip.query("oneprot_esm_embed_bwd_workspace", B * L, d, V)), B, L, d, V, 1, 32, 1, 1)
     flat = ids.reshape(-1)
     keep = (flat != 1) & (flat != 32)
     contrib = dx.to(F64) * rs.to(F64).repeat_interleave(L)[:, None]
     ref = torch.zeros(V, d, dtype=F64, device=DEV).index_add(0, flat[keep], contrib[keep]) + 0.5
     cnt = int(torch.bincount(flat[keep]).max())
-    check(dt, ref, 1e-5, colsum_atol(1.5, cnt), "esm embed bwd (accumulated)")
+    close(dt, ref, 1e-5, colsum_atol(1.5, cnt), "esm embed bwd (accumulated)")
 
 
 # ================================================================================================================== 2. elementwise, reductions, optimiser
@@ -350,25 +321,25 @@ N_EW = 5 * (1 << 20) + 77                                      # past 4096 x 256
 
 
 def test_elementwise_kernels_past_their_grid():
-    g = _gen(5)
-    x = _randn(N_EW, g, 2.0)
+    g = gen(5)
+    x = randn(N_EW, g, 2.0)
     x[:7] = 0.0
     x64 = x.to(F64)
     y = torch.empty_like(x)
     hip.call("oneprot_gelu_f32", x, y, N_EW)
     cdf = 0.5 * (1 + torch.erf(x64 / math.sqrt(2)))
-    check(y, x64 * cdf, 1e-5, 1e-6, "gelu")                   # erff: a few ulp
-    dy = _randn(N_EW, g)
+    close(y, x64 * cdf, 1e-5, 1e-6, "gelu")                   # erff: a few ulp
+    dy = randn(N_EW, g)
     hip.call("oneprot_gelu_bwd_f32", x, dy, y, N_EW)
     pdf = torch.exp(-0.5 * x64 * x64) / math.sqrt(2 * math.pi)
-    check(y, dy.to(F64) * (cdf + x64 * pdf), 1e-4, 1e-5, "gelu bwd")    # __expf in the pdf term
+    close(y, dy.to(F64) * (cdf + x64 * pdf), 1e-4, 1e-5, "gelu bwd")    # __expf in the pdf term
     # L1 backward: dx (+)= coef * upstream * sign(x) -- exact in fp32
     coef = 0.37
     up = torch.tensor([1.75], device=DEV)
     sgn = torch.sign(x)
     for accumulate in (0, 1):
         for upstream in (None, up):
-            base = _randn(N_EW, g)
+            base = randn(N_EW, g)
             out = base.clone()
             hip.call("oneprot_l1_bwd", x, out, N_EW, coef, upstream, accumulate)
             c = torch.tensor(coef, device=DEV) * (upstream[0] if upstream is not None else 1.0)
@@ -409,38 +380,38 @@ def test_reductions_past_their_grid(size, arena_numel):
     tail elements past the last float4 are large so that losing them cannot hide in rounding; `out` is accumulated into"""
     n = arena_numel + 3 - arena_numel % 4 if size == "arena" else int(size)
     assert n % 4
-    g = _gen(n)
-    x = _randn(n, g)
+    g = gen(n)
+    x = randn(n, g)
     x[n - n % 4:] = 30.0
     y = x * (torch.rand(n, generator=g, device=DEV) + 0.5)           # x . y: non-negative terms, like sumsq
-    w = _ws(hip.query("oneprot_sumsq_workspace"))
+    w = ws(hip.query("oneprot_sumsq_workspace"))
     x64 = x.to(F64)
     # fp32: each thread sums up to ~150 float4 groups in order, then 256-wide block and 1024-partial sums: relative drift well under 1e-5 for
     # non-negative terms (the tail of 30.0s is ~1e-4 of the arena sum and all of it for n <= 3)
     rt = 1e-5
     out = torch.tensor([1.5], device=DEV)
     hip.call("oneprot_sumsq", x, n, out, w)
-    check(out, 1.5 + (x64 * x64).sum(), rt, 0.0, f"sumsq n={n}")
+    close(out[0], 1.5 + (x64 * x64).sum(), rt, 0.0, f"sumsq n={n}")
     out = torch.tensor([-2.0], device=DEV)
     hip.call("oneprot_abs_sum", x, out, w, n, 0.25)
-    check(out, -2.0 + 0.25 * x64.abs().sum(), rt, 0.0, f"abs_sum n={n}")
+    close(out[0], -2.0 + 0.25 * x64.abs().sum(), rt, 0.0, f"abs_sum n={n}")
     out = torch.tensor([4.0], device=DEV)
     hip.call("oneprot_dot_f32", x, y, out, w, n, 0.5)
-    check(out, 4.0 + 0.5 * (x64 * y.to(F64)).sum(), rt, 0.0, f"dot n={n}")
+    close(out[0], 4.0 + 0.5 * (x64 * y.to(F64)).sum(), rt, 0.0, f"dot n={n}")
     del x, y, x64
-    _free()
+    free()
 
 
 def test_adam_past_its_grid():
     """k_adam over 9 437 188 parameters (past 8192 x 256 x 4 = 8 388 608), three steps, weight decay and a device grad scale, against fp64 Adam arithmetic"""
     n = 9437188
     lr, b1, b2, eps, wd = 1e-3, 0.9, 0.999, 1e-8, 0.01
-    g = _gen(9)
-    p = _randn(n, g)
+    g = gen(9)
+    p = randn(n, g)
     m, v = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
     p64, m64, v64 = p.to(F64), torch.zeros(n, dtype=F64, device=DEV), torch.zeros(n, dtype=F64, device=DEV)
     for step in (1, 2, 3):
-        gr = _randn(n, g, 3.0)
+        gr = randn(n, g, 3.0)
         gs = torch.tensor([0.5 + 0.1 * step], device=DEV)
         hip.call("oneprot_adam_step", p, gr, m, v, n, lr, b1, b2, eps, wd, step, gs)
         gg = gr.to(F64) * float(gs) + wd * p64
@@ -448,14 +419,14 @@ def test_adam_past_its_grid():
         v64 = b2 * v64 + (1 - b2) * gg * gg
         p64 = p64 - lr / (1 - b1 ** step) * m64 / (torch.sqrt(v64) / math.sqrt(1 - b2 ** step) + eps)
         # fp32 state: a rounding of p per step (6e-8 |p|) plus the update's own few-eps32 relative error (times lr): as test_optimizer_kernels
-        check(p, p64, 1e-5, 2e-6, f"adam p step {step}")
-        check(m, m64, 1e-5, 1e-6, f"adam m step {step}")
-        check(v, v64, 1e-5, 1e-6, f"adam v step {step}")
+        close(p, p64, 1e-5, 2e-6, f"adam p step {step}")
+        close(m, m64, 1e-5, 1e-6, f"adam m step {step}")
+        close(v, v64, 1e-5, 1e-6, f"adam v step {step}")
 
 
 def test_cast_f32_to_bf16_past_its_grid():
     n = 8388608 + 4 * 12345                                    # past 8192 x 256 x 4
-    x = _randn(n, _gen(8), 3.0)
+    x = randn(n, gen(8), 3.0)
     x[-4:] = torch.tensor([65504.5, -1e-30, float("inf"), 3.0e38], device=DEV)
     y = torch.empty(n, dtype=torch.bfloat16, device=DEV)
     hip.call("oneprot_cast_f32_to_bf16", x, y, n)
@@ -466,7 +437,7 @@ def test_cast_f32_to_bf16_past_its_grid():
 @pytest.mark.parametrize("negative_only", [0, 1])
 def test_siglip_block_large(B, negative_only):
     """oneprot_siglip_fwd_bwd (host bias) and _dev (device bias) at B up to 2048 with logits up to +-100: loss and dloss/dlogit against fp64"""
-    g = _gen(B + negative_only)
+    g = gen(B + negative_only)
     logits = (torch.rand(B, B, generator=g, device=DEV) * 200 - 100)
     logits[torch.arange(B), torch.arange(B)] = torch.linspace(-100, 100, B, device=DEV)
     bias = -2.5
@@ -486,8 +457,8 @@ def test_siglip_block_large(B, negative_only):
         else:
             hip.call("oneprot_siglip_fwd_bwd", lg, loss, rw, B, bias, negative_only)
         # __expf carries ~|z| eps32 relative error at |z| <= 100; the loss is a sum of non-negative terms (B row sums of B terms each)
-        check(loss, 0.75 + loss_ref, 2e-5, 0.0, f"siglip loss dev_bias={dev_bias}")
-        check(lg, grad_ref, 2e-5, 1e-12 / B, f"siglip dlogits dev_bias={dev_bias}")
+        close(loss[0], 0.75 + loss_ref, 2e-5, 0.0, f"siglip loss dev_bias={dev_bias}")
+        close(lg, grad_ref, 2e-5, 1e-12 / B, f"siglip dlogits dev_bias={dev_bias}")
 
 
 # ================================================================================================================== 3. dropout masks against Philox
@@ -506,9 +477,9 @@ def test_dropout_masks_equal_philox(philox_mask):
     """every Philox dropout kernel applies exactly the reference mask, element for element, past one grid pass"""
     p, keep, scale = philox_mask
     n = N_DROP
-    g = _gen(11)
+    g = gen(11)
     zero = torch.zeros((), device=DEV)
-    x = _randn(n, g)
+    x = randn(n, g)
     x[x == 0] = 1.0
     xb = x.to(torch.bfloat16)
     # bf16 forward: kept = bf16(x * scale), dropped = 0
@@ -520,7 +491,7 @@ def test_dropout_masks_equal_philox(philox_mask):
     hip.call("oneprot_dropout_f32", x, yf, n, p, SEED_HI, STREAM_HI)
     ref = torch.where(keep, x * scale, zero)
     assert torch.equal(yf, ref), f"dropout_f32: {int((yf != ref).sum())} elements differ"
-    resid = _randn(n, g)
+    resid = randn(n, g)
     hip.call("oneprot_dropout_add_f32", x, resid, yf, n, p, SEED_HI, STREAM_HI)
     assert torch.equal(yf, ref + resid), "dropout_add_f32"
     # both backward-add forms: onto zeros the result IS the masked, scaled gradient (exact); onto a live gradient, to one rounding of the sum
@@ -530,13 +501,13 @@ def test_dropout_masks_equal_philox(philox_mask):
     d32 = torch.zeros(n, device=DEV)
     hip.call("oneprot_dropout_bwd_add_f32", xb, d32, n, p, SEED_HI, STREAM_HI)
     assert torch.equal(d32, torch.where(keep, xb.float() * scale, zero)), "dropout_bwd_add_f32 mask"
-    base = _randn(n, g)
+    base = randn(n, g)
     d32 = base.clone()
     hip.call("oneprot_dropout_bwd_add_f32", xb, d32, n, p, SEED_HI, STREAM_HI)
-    check(d32, base.to(F64) + torch.where(keep, xb.to(F64) * scale, zero.to(F64)), 2e-7, 1e-6, "dropout_bwd_add_f32 onto a gradient")   # <= 2 roundings
+    close(d32, base.to(F64) + torch.where(keep, xb.to(F64) * scale, zero.to(F64)), 2e-7, 1e-6, "dropout_bwd_add_f32 onto a gradient")   # <= 2 roundings
     d16 = base.to(torch.bfloat16)
     hip.call("oneprot_dropout_bwd_add_bf16", xb, d16, n, p, SEED_HI, STREAM_HI)
-    check(d16, base.to(torch.bfloat16).to(F64) + torch.where(keep, xb.to(F64) * scale, zero.to(F64)), 2 ** -8, 1e-6, "dropout_bwd_add_bf16 onto a gradient")
+    close(d16, base.to(torch.bfloat16).to(F64) + torch.where(keep, xb.to(F64) * scale, zero.to(F64)), 2 ** -8, 1e-6, "dropout_bwd_add_bf16 onto a gradient")
 
 
 def test_attention_dropout_keep_equals_reference():
@@ -555,9 +526,9 @@ def test_attention_dropout_keep_equals_reference():
 def test_gemm_tn_under_cu_reserve(M, N, K):
     """oneprot_gemm_bf16_tn with oneprot_cu_reserve 0, 16, 64 and 200 (the last reaches the 64-CU floor): the reserve changes the token splits and with them
     the summation order; dW and dbias against fp64 from the same bf16 operands, nothing written past the workspace"""
-    g = _gen(M + N + K)
-    dY = _randn((M, N), g, 0.5, dtype=torch.bfloat16)
-    X = _randn((M, K), g, 0.5, dtype=torch.bfloat16)
+    g = gen(M + N + K)
+    dY = randn((M, N), g, 0.5, dtype=torch.bfloat16)
+    X = randn((M, K), g, 0.5, dtype=torch.bfloat16)
     ref = dY.to(F64).t() @ X.to(F64)
     rb = dY.to(F64).sum(0)
     need = hip.query("oneprot_gemm_bf16_tn_workspace", N, K)
@@ -573,7 +544,7 @@ def test_gemm_tn_under_cu_reserve(M, N, K):
             hip.call("oneprot_gemm_bf16_tn", dY, X, M, N, K, N, K, dW, db, w, need, 0)
             assert bool((w[need:] == 0xA5).all()), f"reserve {reserve}: wrote past the workspace"
             # (fp32 accumulation over M products of two bf16 values: the tolerance of test_gemm_tn_large_m_every_width)
-            check(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), f"tn dW reserve {reserve}")
-            check(db, rb, 1e-4, 2e-2, f"tn dbias reserve {reserve}")
+            close(dW, ref, 1e-4, 2e-3 * math.sqrt(M / 64), f"tn dW reserve {reserve}")
+            close(db, rb, 1e-4, 2e-2, f"tn dbias reserve {reserve}")
     finally:
         hip.query("oneprot_cu_reserve", hip.cu_reserve_wanted())

@@ -24,6 +24,7 @@ import torch
 from oneprot_amd import pronet as P
 from tests import pronet_ref as R
 from tests import pronet_rng_ref as RNG
+from tests.gate import rel_l2
 from tests.pronet_fixtures import CUTOFF, large_batch, mixed_batch
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +36,6 @@ FACTOR = 4.0
 def make_tower(**kw):
     torch.manual_seed(21)
     return P.ProNet(level="backbone", num_blocks=2, hidden_channels=128, out_channels=8, **kw)
-
-
-def rel_l2(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
 def reference(sd, batch, dtype, cot, aug=None):

@@ -15,19 +15,12 @@ from oneprot_amd import hip
 from oneprot_amd import pronet as P
 from tests import pronet_ref as R
 from tests import pronet_rng_ref as RNG
+from tests.gate import close, rel_l2
 from tests.pronet_fixtures import BATCHES, CUTOFF, conv_case, large_batch, mixed_batch, restated_graph
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NR, NP = 6, 16
-
-
-def assert_close(a, ref, rtol, atol, msg=""):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    assert torch.isfinite(a).all(), msg
-    err = (a - ref).abs()
-    bad = ~(err <= atol + rtol * ref.abs())
-    assert not bad.any(), f"{msg}: {int(bad.sum())} of {bad.numel()} outside, worst |err| {float(err.max()):.3e}"
 
 
 @pytest.fixture(scope="module", params=["mixed", "one_graph", "large"])
@@ -80,7 +73,7 @@ def test_edge_features_per_element(graph):
     N = b.num_nodes
     assert deg[0] > 0 and deg[N - 1] > 0                                           # the wrap rows carry edges
     for k in range(3):
-        assert_close(g.feat[k], ref[k], 1e-4, 1e-3, f"feature{k}")
+        close(g.feat[k], ref[k], 1e-4, 1e-3, f"feature{k}")
     if b is mixed_batch():
         line = slice(int(b.ptr[5]) * 32, int(b.ptr[6]) * 32)                       # exactly collinear CA triples
         assert all(torch.isfinite(f[line]).all() for f in g.feat)
@@ -96,7 +89,7 @@ def test_edge_features_with_euler_noise(graph):
     plain = R.edge_features(b.coords_ca, b.coords_n, b.coords_c, nbr, deg, NR, NP, CUTOFF)
     assert float((ref[1] - plain[1]).abs().max()) > 1e-2                           # the noise is visible at this tolerance
     for k in range(3):
-        assert_close(g.feat[k], ref[k], 1e-4, 1e-3, f"feature{k} with noise")
+        close(g.feat[k], ref[k], 1e-4, 1e-3, f"feature{k} with noise")
     g2 = P.Graph(b.to(DEV), CUTOFF, 32, P.feature_constants(NR, NP).to(DEV), NR, NP, euler=(seed, stream))
     assert all(torch.equal(u, v) for u, v in zip(g.feat, g2.feat))
 
@@ -193,9 +186,9 @@ def _edge_conv_check(N, h, F):
     worst = lambda x, ref: float((x.double().cpu() - ref).abs().max())                   # noqa: E731
     print(f"edge conv N {N} h {h} F {F} E {E}: worst |err| m {worst(m, m_ref.detach()):.2e} (atol {tol_m:.2e})  da {worst(da, a64.grad):.2e} (atol {tol_da:.2e})  "
           f"dWfT {worst(dW, W64.grad):.2e} (atol {tol_w:.2e})")
-    assert_close(m, m_ref, 1e-4, tol_m, "m")
-    assert_close(da, a64.grad, 1e-4, tol_da, "da")
-    assert_close(dW, W64.grad, 1e-4, tol_w, "dWfT")
+    close(m, m_ref, 1e-4, tol_m, "m")
+    close(da, a64.grad, 1e-4, tol_da, "da")
+    close(dW, W64.grad, 1e-4, tol_w, "dWfT")
     assert (m[torch.as_tensor(deg == 0)] == 0).all() and (da[N - 1] == 0).all()
     again = run()
     assert all(torch.equal(u, v) for u, v in zip((m, da, dW), again))
@@ -260,14 +253,14 @@ def _row_ops_check(b):
     hip.call("oneprot_pronet_embed_fwd", z.to(DEV), bb.to(DEV), W.to(DEV), bias.to(DEV), x0, f32, N, h)
     inp = torch.cat([torch.nn.functional.one_hot(z, 26).double(), bb.double()], dim=1)
     assert torch.equal(f32.cpu().double(), inp.float().double())
-    assert_close(x0, inp @ W.double().t() + bias.double(), 1e-4, 1e-3, "embedding")
+    close(x0, inp @ W.double().t() + bias.double(), 1e-4, 1e-3, "embedding")
     # sum pooling and its backward
     x = torch.randn(N, h, generator=gen)
     y = torch.empty(G, h, device=DEV)
     hip.call("oneprot_segment_sum_f32", x.to(DEV), b.ptr.to(DEV, torch.int32), y, G, h)
     ref = torch.zeros(G, h, dtype=torch.float64).index_add(0, b.batch, x.double())
     assert seg in (300, 1100)
-    assert_close(y, ref, 1e-4, 1e-3 * math.sqrt(seg / 64), "segment sum")
+    close(y, ref, 1e-4, 1e-3 * math.sqrt(seg / 64), "segment sum")
     dy, dx = torch.randn(G, h, generator=gen), torch.empty(N, h, device=DEV)
     hip.call("oneprot_segment_sum_bwd_f32", dy.to(DEV), b.batch.to(DEV, torch.int32), dx, N, h)
     assert torch.equal(dx.cpu(), dy[b.batch])
@@ -287,13 +280,13 @@ def _row_ops_check(b):
         z64 = (zz.double() + bias.double()).requires_grad_()
         out = fn(z64) + res.double()
         assert torch.equal(zd.cpu(), (zz + bias))                                   # the pre-activation, in place
-        assert_close(wide[:, h:2 * h], out, 1e-4, 1e-3, f"act {act}")
+        close(wide[:, h:2 * h], out, 1e-4, 1e-3, f"act {act}")
         assert (wide[:, :h] == 0).all() and (wide[:, 2 * h:] == 0).all()
         g = torch.randn(N, 3 * h, generator=gen)
         out.backward(g[:, h:2 * h].double())
         dz, gd = torch.empty(N, h, device=DEV), g.to(DEV)
         hip.call("oneprot_pronet_act_bwd", gd.data_ptr() + 4 * h, zd, dz, N, h, 3 * h, act)
-        assert_close(dz, z64.grad, 1e-4, 1e-3, f"act' {act}")
+        close(dz, z64.grad, 1e-4, 1e-3, f"act' {act}")
 
 
 @pytest.mark.parametrize("M, n, k", [(1, 128, 128), (8, 8, 128), (129, 64, 32), (475, 128, 384), (8193, 128, 128), (8193, 128, 32), (8193, 100, 70),
@@ -320,17 +313,12 @@ def test_wgrad_blocked_over_rows(M, n, k):
         ref, lost = dz.double().t() @ x.double(), dz[:-1].double().t() @ x[:-1].double()
         e32, err, gap = rel_l2(dz.t() @ x, ref), rel_l2(dW, ref), rel_l2(lost, ref)
         print(f"wgrad M {M} n {n} k {k} {label}: rel-L2 hip {err:.2e}  fp32 torch {e32:.2e}  ratio {err / max(e32, 1e-30):.2f}; without the last row the reference moves by {gap:.2e}")
-        assert_close(dW, ref, 1e-4, 1e-3 * math.sqrt(M / 64), f"dW {label}")
+        close(dW, ref, 1e-4, 1e-3 * math.sqrt(M / 64), f"dW {label}")
         assert err <= 4 * max(e32, 2.0 ** -25), (label, err, e32)                       # 2^-25: one rounding, where torch's own sum happens to be exact
         assert M == 1 or (gap > 4 * max(e32, 2.0 ** -25) and rel_l2(dW, lost) > 4 * max(e32, 2.0 ** -25)), (label, gap)      # the bound sees one lost row
         assert torch.equal(dW, run())
     with pytest.raises(hip.HipKernelError):                                             # a short workspace is refused before any launch
         hip.call("oneprot_wgrad_f32", x.to(DEV), x.to(DEV), torch.empty(k, k, device=DEV), torch.empty(16, dtype=torch.uint8, device=DEV), 4, M, k, k)
-
-
-def rel_l2(a, ref):
-    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
-    return float((a - ref).norm() / ref.norm().clamp_min(1e-300))
 
 
 def test_noise_add_and_the_plain_calls():
@@ -341,7 +329,7 @@ def test_noise_add_and_the_plain_calls():
     hip.call("oneprot_clipped_normal_add_f32", xd, y, x.numel(), 0.025, 0.1, seed, stream)
     noise = RNG.node_noise(x.shape, seed, stream)
     assert float(noise.abs().max()) <= 0.1 and abs(float(noise.mean())) < 1e-3 and 0.02 < float(noise.std()) < 0.026
-    assert_close(y, x.double() + noise, 0.0, 1e-5, "x + noise")                      # the sum's own fp32 rounding is 2.4e-7 at |x| <= 4; the normals agree far below 1e-5
+    close(y, x.double() + noise, 0.0, 1e-5, "x + noise")                      # the sum's own fp32 rounding is 2.4e-7 at |x| <= 4; the normals agree far below 1e-5
     y2 = torch.empty_like(y)
     hip.call("oneprot_clipped_normal_add_f32", xd, y2, x.numel(), 0.025, 0.1, seed, stream)
     assert torch.equal(y, y2)

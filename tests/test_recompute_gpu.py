@@ -2,8 +2,6 @@
 with `k`-layer segments recomputed inside the backward.  The recompute pass issues the forward's own launches on the forward's own inputs, so every
 comparison below is torch.equal -- features, loss and every gradient -- never a tolerance."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -11,6 +9,7 @@ import torch
 from oneprot_amd import hip
 from oneprot_amd.esm import recompute_plan
 from oneprot_amd.packing import PackedTokens
+from tests.cases import esm_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -41,12 +40,7 @@ def _ffn2(monkeypatch, mode):
 
 
 def _esm_dir(tmp, shape):
-    layers, hidden, heads, ffn = SHAPES[shape]
-    path = os.path.join(str(tmp), shape)
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(dict(model_type="esm", vocab_size=33, hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=ffn), f)
-    return path
+    return esm_dir(tmp, shape, *SHAPES[shape])
 
 
 def _row(n, L, gen):

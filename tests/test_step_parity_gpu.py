@@ -13,41 +13,15 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import oneprot_oracle as O  # noqa: E402
+from tests.cases import esm_dir_from_cfg, golden_pair_module  # noqa: E402,F401
+from tests.gate import cos_sim  # noqa: E402
 
 DEV = "cuda"
 
 
-def _write_cfg(tmp, cfg, name):
-    path = os.path.join(tmp, name)
-    os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "config.json"), "w") as f:
-        json.dump(dict(model_type="esm", vocab_size=cfg["vocab"], hidden_size=cfg["hidden"], num_hidden_layers=cfg["layers"],
-                       num_attention_heads=cfg["heads"], intermediate_size=cfg["ffn"], pad_token_id=cfg["pad"], mask_token_id=cfg["mask"],
-                       layer_norm_eps=cfg["eps"], token_dropout=True, position_embedding_type="rotary", emb_layer_norm_before=False), f)
-    return path
-
-
-def _cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a @ b) / (a.norm() * b.norm() + 1e-30))
-
-
 def _build(golden_dir, tag, tmp_path, frozen_seq=False):
-    os.environ.update(RANK="0", WORLD_SIZE="1", ONEPROT_ALLOW_RANDOM_INIT="1")
-    from src.models.components.sequence_encoder import SequenceEncoder
-    from src.models.components.struct_token_encoder import StructTokenEncoder
-    from src.models.oneprot_module import OneProtLitModule
-    from oneprot_amd.optim import FusedAdam
-    g = torch.load(os.path.join(golden_dir, f"esm_pair_{tag}.pt"), weights_only=False)
-    cfg = g["cfg"]
-    p = _write_cfg(str(tmp_path), cfg, "esm")
-    seq = SequenceEncoder(p, output_dim=cfg["output_dim"], pooling_type="mean", proj_type="mlp", use_lora=False, frozen=frozen_seq)
-    st = StructTokenEncoder(p, output_dim=cfg["output_dim"], pooling_type="mean", proj_type="linear", use_logit_scale=True, learnable_logit_scale=False)
-    seq.load_state_dict(g["sd_seq"], strict=True)        # exact key compatibility with the reference's state dict
-    st.load_state_dict(g["sd_st"], strict=True)
-    module = OneProtLitModule(components={"sequence": seq, "struct_token": st}, optimizer=functools.partial(FusedAdam, lr=1e-3, weight_decay=0.0),
-                              loss_fn="CLIP", use_l1_regularization=True, local_loss=True, gather_with_grad=True).to(DEV)
-    return g, module
+    os.environ.update(ONEPROT_ALLOW_RANDOM_INIT="1")
+    return golden_pair_module(golden_dir, tag, tmp_path, frozen_seq)
 
 
 @pytest.mark.parametrize("tag", ["hd16", "hd32", "hd24"])
@@ -99,14 +73,14 @@ def test_training_substep_vs_reference(golden_dir, tag, tmp_path):
             continue
         if ref.abs().max() < 1e-7:
             continue
-        c = _cos(grads[k], ref)
+        c = cos_sim(grads[k], ref)
         worst = min(worst, (c, k))
         n += 1
     assert n > 30
     if os.environ.get("ONEPROT_TEST_VERBOSE"):
         for k, ref in g["grads"].items():
             if k in grads and ref.abs().max() >= 1e-7:
-                print(f"{_cos(grads[k], ref):.5f} {float(ref.norm()):.3e} {k}")
+                print(f"{cos_sim(grads[k], ref):.5f} {float(ref.norm()):.3e} {k}")
     # every tensor >= 0.98; tensors carrying a non-negligible share of the gradient (norm >= 1 % of the largest) >= 0.999;
     # the whole gradient as one vector >= 0.9999.  (Tiny q/k gradients are differences of nearly equal bf16-rounded
     # terms, dS = P*(dP - delta), hence the looser per-tensor floor; observed worst 0.989 at |g| = 1e-2 vs 1e+1.)
@@ -115,9 +89,9 @@ def test_training_substep_vs_reference(golden_dir, tag, tmp_path):
     keys = [k for k, ref in g["grads"].items() if k in grads and ref.abs().max() >= 1e-7]
     for k in keys:
         if float(g["grads"][k].norm()) >= 0.01 * big:
-            assert _cos(grads[k], g["grads"][k]) > 0.999, k
+            assert cos_sim(grads[k], g["grads"][k]) > 0.999, k
     allg = torch.cat([grads[k].flatten() for k in keys]); allr = torch.cat([g["grads"][k].flatten() for k in keys])
-    assert _cos(allg, allr) > 0.9999
+    assert cos_sim(allg, allr) > 0.9999
     # post-Adam weights: step-1 update is lr*sign-ish; compare against the reference's updated tensors
     coef = min(1.0, 1.0 / (float(g["grad_total_norm"]) + 1e-6))
     for enc_name, after, gpref in (("sequence", g["sd_seq_after"], "seq."), ("struct_token", g["sd_st_after"], "st.")):
@@ -172,11 +146,11 @@ def test_seqsim_substep_applies_the_sequence_encoder_twice(golden_dir, tmp_path)
     keys = [k for k, v in ref["grads"].items() if k in grads and v.abs().max() >= 1e-7]
     assert len(keys) > 30
     allg = torch.cat([grads[k].flatten() for k in keys]); allr = torch.cat([ref["grads"][k].flatten() for k in keys])
-    assert _cos(allg, allr) > 0.9999, _cos(allg, allr)
+    assert cos_sim(allg, allr) > 0.9999, cos_sim(allg, allr)
     big = max(float(ref["grads"][k].norm()) for k in keys)
     for k in keys:
         if float(ref["grads"][k].norm()) >= 0.01 * big:
-            assert _cos(grads[k], ref["grads"][k]) > 0.999, (k, _cos(grads[k], ref["grads"][k]))
+            assert cos_sim(grads[k], ref["grads"][k]) > 0.999, (k, cos_sim(grads[k], ref["grads"][k]))
     sd = {k: v.cpu() for k, v in module.network["sequence"].state_dict().items()}
     for k, v in ref["new_params"].items():
         assert (sd[k[4:]] - v).abs().max() < 2.1e-3, k
@@ -352,7 +326,7 @@ def test_trainable_text_encoder_gradients_vs_reference(golden_dir, tmp_path):
         assert k in got, k
         if float(ref.norm()) < 1e-6:
             continue
-        c = _cos(got[k], ref)
+        c = cos_sim(got[k], ref)
         assert c > 0.98, (k, c)
         if float(ref.norm()) > 0.05 * max(float(v.norm()) for v in g["grads"].values()):
             assert c > 0.999, (k, c)
@@ -363,7 +337,7 @@ def test_trainable_text_encoder_gradients_vs_reference(golden_dir, tmp_path):
     unused = [r for r in range(cfg["vocab"]) if r not in set(g["ids"].flatten().tolist())]
     assert float(wg[unused].abs().max()) == 0.0
     allg = torch.cat([got[k].flatten() for k in g["grads"]]); allr = torch.cat([v.flatten() for v in g["grads"].values()])
-    assert _cos(allg, allr) > 0.9995
+    assert cos_sim(allg, allr) > 0.9995
 
 
 def test_trainable_text_encoder_train_mode_dropout_gradients_vs_oracle(golden_dir, tmp_path):
@@ -407,14 +381,14 @@ def test_trainable_text_encoder_train_mode_dropout_gradients_vs_oracle(golden_di
     for k, ref in refs.items():
         if float(ref.norm()) < 1e-6:
             continue
-        c = _cos(got[k], ref)
+        c = cos_sim(got[k], ref)
         assert c > 0.98, (k, c)
         if float(ref.norm()) > 0.05 * big:
             assert c > 0.999, (k, c)
         n += 1
     assert n >= 38
     allg = torch.cat([got[k].flatten() for k in refs]); allr = torch.cat([v.flatten() for v in refs.values()])
-    assert _cos(allg, allr) > 0.9995
+    assert cos_sim(allg, allr) > 0.9995
 
 
 def test_bert_base_shape_trainable_substep_vs_oracle():
@@ -471,7 +445,7 @@ def test_bert_base_shape_trainable_substep_vs_oracle():
     assert abs(float(module.last_grad_norm) - float(ref["grad_total_norm"])) / float(ref["grad_total_norm"]) < 2e-2
     for k, v in grads.items():
         r = ref["grads"]["mod.transformer." + k]
-        assert _cos(v, r) > 0.98, (k, _cos(v, r))
+        assert cos_sim(v, r) > 0.98, (k, cos_sim(v, r))
 
 
 @pytest.mark.parametrize("frozen_seq", [True, False])
@@ -593,7 +567,7 @@ def test_esm2_35m_shape_train_step_vs_oracle():
     for k, v in grads.items():
         r = ref["grads"]["mod.transformer." + k]
         if float(r.norm()) > 1e-6:
-            assert _cos(v, r) > 0.98, (k, _cos(v, r))
+            assert cos_sim(v, r) > 0.98, (k, cos_sim(v, r))
 
 
 def test_lora_sequence_encoder_vs_oracle():
@@ -651,14 +625,14 @@ def test_lora_sequence_encoder_vs_oracle():
         for ti, t in enumerate(("query", "key", "value")):
             for which, got in (("A", tr.lora_A.grad[i, ti]), ("B", tr.lora_B.grad[i, ti])):
                 ref = osd[f"{P}{i}.attention.self.{t}.lora_{which}.default.weight"].grad
-                assert _cos(got.cpu(), ref) > 0.98, (i, t, which, _cos(got.cpu(), ref))
+                assert cos_sim(got.cpu(), ref) > 0.98, (i, t, which, cos_sim(got.cpu(), ref))
     gflat = tr.flat.grad
     idx = tr._lora_bias_index
     mask = torch.zeros_like(gflat, dtype=torch.bool); mask[idx] = True
     assert float(gflat[~mask].abs().max()) == 0.0                                   # frozen base weights, LayerNorm gains: no gradient
     for name in ("encoder.layer.0.attention.self.query.bias", "encoder.layer.3.intermediate.dense.bias", "encoder.layer.5.LayerNorm.bias", "encoder.emb_layer_norm_after.bias"):
         ref = osd["transformer.base_model.model." + name].grad
-        assert _cos(tr.view(name, gflat).cpu(), ref) > 0.98, name
+        assert cos_sim(tr.view(name, gflat).cpu(), ref) > 0.98, name
     opt.step()
     after = tr.flat.detach()
     assert torch.equal(after[~mask], before[~mask]) and not torch.equal(after[mask], before[mask])
@@ -739,14 +713,14 @@ def test_lora_dropout_two_branch_sequence_encoder_vs_oracle():
         for ti, t in enumerate(("query", "key", "value")):
             for which, got in (("A", tr.lora_A.grad[i, ti]), ("B", tr.lora_B.grad[i, ti])):
                 ref = osd[f"{P}{i}.attention.self.{t}.lora_{which}.default.weight"].grad
-                assert _cos(got.cpu(), ref) > 0.98, (i, t, which, _cos(got.cpu(), ref))
+                assert cos_sim(got.cpu(), ref) > 0.98, (i, t, which, cos_sim(got.cpu(), ref))
     gflat = tr.flat.grad
     idx = tr._lora_bias_index
     mask = torch.zeros_like(gflat, dtype=torch.bool); mask[idx] = True
     assert float(gflat[~mask].abs().max()) == 0.0
     for name in ("encoder.layer.0.attention.self.query.bias", "encoder.layer.3.intermediate.dense.bias", "encoder.layer.5.LayerNorm.bias"):
         ref = osd["transformer.base_model.model." + name].grad
-        assert _cos(tr.view(name, gflat).cpu(), ref) > 0.98, name
+        assert cos_sim(tr.view(name, gflat).cpu(), ref) > 0.98, name
     # a second train-mode call draws new masks; eval mode is deterministic and equals the oracle without masks
     with torch.no_grad():
         f2 = enc(ids.to(DEV)).cpu()
@@ -794,7 +768,7 @@ def test_lora_text_encoder_vs_oracle(golden_dir, tmp_path, lora_dropout):
         for ti, t in enumerate(("query", "key", "value")):
             for which, got in (("A", tr.lora_A.grad[i, ti]), ("B", tr.lora_B.grad[i, ti])):
                 ref = osd[f"transformer.base_model.model.encoder.layer.{i}.attention.self.{t}.lora_{which}.default.weight"].grad
-                assert _cos(got.cpu(), ref) > 0.98, (i, t, which)
+                assert cos_sim(got.cpu(), ref) > 0.98, (i, t, which)
 
 
 def test_max_length_sequences_vs_oracle():
@@ -841,7 +815,7 @@ def test_mixed_batch_round_robin(golden_dir, tmp_path):
     from src.models.oneprot_module import OneProtLitModule
     g = torch.load(os.path.join(golden_dir, "esm_pair_hd16.pt"), weights_only=False)
     tb = torch.load(os.path.join(golden_dir, "bert_text.pt"), weights_only=False)
-    p = _write_cfg(str(tmp_path), g["cfg"], "esm")
+    p = esm_dir_from_cfg(str(tmp_path), g["cfg"], "esm")
     pb = os.path.join(str(tmp_path), "bert"); os.makedirs(pb)
     c = tb["cfg"]
     with open(os.path.join(pb, "config.json"), "w") as f:
@@ -921,7 +895,7 @@ def test_attention1d_pooling_and_learnable_logit_scale(tmp_path, frozen):
     os.environ.update(RANK="0", WORLD_SIZE="1", ONEPROT_ALLOW_RANDOM_INIT="1")
     from src.models.components.sequence_encoder import SequenceEncoder
     cfg = dict(vocab=33, hidden=1280, layers=1, heads=20, ffn=256, pad=1, mask=32, eps=1e-5)
-    p = _write_cfg(str(tmp_path), cfg, "esm1280")
+    p = esm_dir_from_cfg(str(tmp_path), cfg, "esm1280")
     torch.manual_seed(5)
     enc = SequenceEncoder(p, output_dim=64, pooling_type="attention1d", proj_type="linear", use_logit_scale=True, learnable_logit_scale=True, use_lora=False,
                           frozen=frozen)
@@ -948,7 +922,7 @@ def test_attention1d_pooling_and_learnable_logit_scale(tmp_path, frozen):
     (got * tgt.to(DEV)).sum().backward()
     cs = torch.nn.functional.cosine_similarity(got.detach().cpu(), ref.detach(), dim=-1)
     assert cs.min() > 0.999, cs
-    assert _cos(enc.pooling.layer.weight.grad.cpu(), leaf["pooling.layer.weight"].grad) > 0.99
+    assert cos_sim(enc.pooling.layer.weight.grad.cpu(), leaf["pooling.layer.weight"].grad) > 0.99
     assert abs(enc.pooling.layer.bias.grad.item() - leaf["pooling.layer.bias"].grad.item()) < 2e-2 * (abs(leaf["pooling.layer.bias"].grad.item()) + 1e-3)
     # d loss / d log_logit_scale = sum_b features_b . tgt_b: three terms of magnitude |features_b| |tgt_b| ~ 14.29 x 8 each that largely cancel (here
     # to ~6.8), so the tolerance is stated on the terms, not on the cancelled sum: 1e-3 relative feature error (the bf16 compute path's level; the
@@ -956,14 +930,14 @@ def test_attention1d_pooling_and_learnable_logit_scale(tmp_path, frozen):
     gs, rs_ = enc.norm[1].log_logit_scale.grad.item(), leaf["norm.1.log_logit_scale"].grad.item()
     term_scale = float((ref.detach().norm(dim=-1) * tgt.norm(dim=-1)).sum())
     assert abs(gs - rs_) < 1e-3 * term_scale, (gs, rs_, term_scale)
-    assert _cos(enc.proj[1].weight.grad.cpu(), leaf["proj.1.weight"].grad) > 0.999
+    assert cos_sim(enc.proj[1].weight.grad.cpu(), leaf["proj.1.weight"].grad) > 0.999
     if frozen:
         assert enc.transformer.flat.grad is None
     else:
         gq = enc.transformer.view("encoder.layer.0.attention.self.value.weight", enc.transformer.flat.grad).cpu()
-        assert _cos(gq, leaf["transformer.encoder.layer.0.attention.self.value.weight"].grad) > 0.99
+        assert cos_sim(gq, leaf["transformer.encoder.layer.0.attention.self.value.weight"].grad) > 0.99
         ge = enc.transformer.view("encoder.emb_layer_norm_after.weight", enc.transformer.flat.grad).cpu()
-        assert _cos(ge, leaf["transformer.encoder.emb_layer_norm_after.weight"].grad) > 0.99
+        assert cos_sim(ge, leaf["transformer.encoder.emb_layer_norm_after.weight"].grad) > 0.99
 
 
 def test_struct_encoder_adapter_vs_reference(golden_dir):
@@ -1011,7 +985,7 @@ def test_arena_gradient_buffer_is_not_recycled_under_a_live_reference(tmp_path):
     from src.models.components.sequence_encoder import SequenceEncoder
     cfg = dict(vocab=33, hidden=64, layers=2, heads=4, ffn=128, pad=1, mask=32, eps=1e-5)
     torch.manual_seed(11)
-    enc = SequenceEncoder(_write_cfg(str(tmp_path), cfg, "esm64"), output_dim=16, pooling_type="mean", proj_type="linear", use_lora=False, frozen=False).to(DEV)
+    enc = SequenceEncoder(esm_dir_from_cfg(str(tmp_path), cfg, "esm64"), output_dim=16, pooling_type="mean", proj_type="linear", use_lora=False, frozen=False).to(DEV)
     ids = torch.randint(4, 24, (3, 19), generator=torch.Generator().manual_seed(3)).to(DEV)
     flat = enc.transformer.flat
     enc(ids).sum().backward()

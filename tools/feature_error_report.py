@@ -1,14 +1,16 @@
 """Per-fixture error report of the HIP encoder vs the reference goldens (embedding output, layer-0 output): shows that the bf16
 error per feature is the same for head_dim 16 / 32 / 24(padded).  Run on a GPU box: python tools/feature_error_report.py"""
 import os, sys, tempfile, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
-import test_step_parity_gpu as T
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tests.cases import golden_pair_module
 from pathlib import Path
-gd = "/root/repo/tests/golden"
+os.environ["ONEPROT_ALLOW_RANDOM_INIT"] = "1"
+gd = os.path.join(ROOT, "tests", "golden")
 def rel(a, b): return float((a - b).norm() / b.norm())
 for tag in ("hd16", "hd32", "hd24"):
     tmp = Path(tempfile.mkdtemp())
-    g, module = T._build(gd, tag, tmp)
+    g, module = golden_pair_module(gd, tag, tmp)
     tr = module.network["sequence"].transformer
     ids = g["seq_ids"].cuda()
     with torch.no_grad():
