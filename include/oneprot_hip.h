@@ -471,6 +471,33 @@ int oneprot_msa_tokenize(const void* msa_bytes, const int64_t* table, const int*
                          int64_t* seq_tokens, const int64_t* table_host, int64_t n_bytes, int n, int k_max, int R_max, int Lt_max, int Ls_max,
                          int max_length, int64_t T_pad, int cls_id, int pad_id, int eos_id, void* stream);
 
+/* ---------------- text input (ref src/data/datasets/text_dataset.py:25,51: `AutoTokenizer.from_pretrained(text_tokenizer)` and its call with
+ * `padding=True, truncation=True`, HF's fast BERT tokenizer) ------------------------------------------------------------------------------------------
+ * BertNormalizer + BertPreTokenizer + WordPiece(max_input_chars_per_word = 100) + [CLS] .. [SEP] + truncation of a whole batch in one launch, one
+ * work-group per text, integer arithmetic only, no atomics (csrc/wordpiece.hip; the rule is stated once in DESIGN.md section 7 and is
+ * oneprot_amd.text_data.BertWordPieceTokenizer.encode_all on the host).  All state lives in LDS, so there is no workspace and no size query.
+ * text_bytes: the texts' UTF-8 bytes, concatenated, n_bytes long; offsets int64 [n_texts + 1] on the device (text b is bytes
+ * [offsets[b], offsets[b + 1])) and offsets_host the same numbers in host memory, from which the call validates.
+ * The normalisation table has two levels: norm_index int32 [0x1100] gives the block of code point c as norm_index[c >> 8], and
+ * norm_entries int32 [n_blocks, 256] its entry: bits 23-24 the number of characters it becomes (0: dropped), bits 21-22 the kind of that character
+ * (0 part of a word, 1 a word of its own: punctuation and CJK, 2 space) and bits 0-20 its code point when that number is 1, or bits 0-20 an index into
+ * norm_pool int32 [n_pool] (code point | kind << 21 per character) when it is 2 or 3.
+ * The vocabulary is an open-addressing table: vocab_slots int32 [n_slots, 4] = {key, first character in vocab_chars, length | keyspace << 16, id},
+ * 16-byte aligned, n_slots a power of two, id -1 in an empty slot; vocab_chars int32 [n_vocab_chars] the pieces' code points; keyspace 1 holds the
+ * "##" pieces without their prefix.  key = fmix32(h ^ length * 0x9e3779b1 ^ (keyspace ? 0x85ebca6b : 0)) with h = h * 0x01000193 + c + 1 (mod 2^32)
+ * over the characters and fmix32 MurmurHash3's finaliser; a piece lives at the first free slot from key & (n_slots - 1) upwards.  A hit is verified
+ * against the stored characters.  max_piece_chars: the length of the longest piece (1 .. 100), which bounds the greedy search.
+ * ids int32 [n_texts, max_length]: cls_id, the first max_length - 2 pieces, sep_id, then pad_id; lengths int32 [n_texts] the ids before the padding.
+ * Refused with -1 before any launch: a NULL pointer, n_texts outside 1 .. ONEPROT_WORDPIECE_MAX_TEXTS, max_length outside 2 ..
+ * ONEPROT_WORDPIECE_MAX_LENGTH, offsets_host that decrease or leave [0, n_bytes], n_slots no power of two or below 2, n_blocks outside 1 .. 0x1100,
+ * n_pool or n_vocab_chars below 1, max_piece_chars outside 1 .. 100, a negative special id, vocab_slots not 16-byte aligned. */
+#define ONEPROT_WORDPIECE_MAX_TEXTS 1048576
+#define ONEPROT_WORDPIECE_MAX_LENGTH 65535
+int oneprot_wordpiece_encode(const void* text_bytes, const int64_t* offsets, const int* norm_index, const int* norm_entries, const int* norm_pool,
+                             const int* vocab_slots, const int* vocab_chars, int* ids, int* lengths, const int64_t* offsets_host, int64_t n_bytes,
+                             int n_texts, int n_blocks, int n_pool, int n_slots, int n_vocab_chars, int max_piece_chars, int max_length, int cls_id,
+                             int sep_id, int unk_id, int pad_id, void* stream);
+
 /* ---------------- ProNet tower (ref src/models/components/struct_graph_encoder.py:5-42 plugs in dig.threedgraph.method.ProNet; the arithmetic is the
  * published model's, Wang et al. 2023, restated: DESIGN.md section 7, tests/pronet_ref.py is the oracle) ----------------------------------------------
  * N nodes of n_graphs graphs in one batch, a graph's nodes contiguous: graph_ptr int32 [n_graphs + 1], batch int32 [N].  Edges are stored by target in a
