@@ -677,7 +677,28 @@ size_t oneprot_gbt_split_workspace(int F, int level, int kc);
 int oneprot_gbt_split(const int64_t* hist, const float* cuts, const int* ncuts, const void* feat_keep, const int* expo, int* tree_feat, int* tree_bin, float* tree_thr,
                       float* tree_leaf, void* gain_bytes, void* workspace, size_t workspace_bytes, int F, int max_bin, int level, int kc, int tree_nodes,
                       float min_child_weight, float gamma, float reg_alpha, float reg_lambda, float learning_rate, void* stream);
-/* pos [kc, N]: a row in a node of this level that split moves to child 2 p + 1 (bin <= tree_bin) or 2 p + 2; every other row stays */
+/* Levels 6 .. 8 of a one-output fit (ref saprot_fit_reg.py:26-32 with max_depth 7 .. 9, as configs/saprot_sweep_xgboost_reg.yaml asks): the rows in node
+   order, and the level's histograms and split search a group of nodes [node0, node0 + nodes) at a time, so that a level need not fit memory at once.
+   oneprot_gbt_node_keys: keys[i] = pos[i] - (2^level - 1) for a row in a node of the level, the sentinel 2^level for every other row.  The caller sorts them
+   (oneprot_sort_i32, level + 1 key bits, values NULL) into sorted_keys and order.  oneprot_gbt_node_seg: seg int32 [2^level + 1], seg[n] = the first position
+   of sorted_keys that holds a key >= n (seg[2^level]: where the sentinel rows begin). */
+int oneprot_gbt_node_keys(const int* pos, int* keys, int64_t N, int level, void* stream);
+int oneprot_gbt_node_seg(const int* sorted_keys, int* seg, int64_t N, int level, void* stream);
+/* hist int64 [nodes, F, max_bin, 2] (g, h), indexed by the local node n - node0, overwritten: the sums of gq / hq [N] over the rows of node n.  Rows of nodes
+   outside the group, sentinel rows, rows with g = h = 0 and bins >= max_bin add nothing.  The launch is a function of the shapes alone: work-group x takes
+   2047 consecutive positions of `order`.  tile_features: the features of an LDS tile (a power of two <= 64; the tile holds 64 / tile_features consecutive
+   nodes), 0 for the library's choice per level; it cannot change a bit of the result.  oneprot_gbt_hist_nodes_bytes: the bytes of `nodes` nodes. */
+size_t oneprot_gbt_hist_nodes_bytes(int F, int max_bin, int nodes);
+int oneprot_gbt_hist_nodes(const void* bins, const int* gq, const int* hq, const int* order, const int* sorted_keys, const int* seg, int64_t* hist, int64_t N, int F,
+                           int max_bin, int level, int node0, int nodes, int tile_features, void* stream);
+/* oneprot_gbt_split for one output and the nodes [node0, node0 + nodes) of a level 0 .. 8, on the same device code: hist and the workspace's records are indexed
+   by the local node, the tree arrays [tree_nodes] and gain_bytes by the heap id 2^level - 1 + node0 + n.  With node0 = 0 and nodes = 2^level it writes what
+   oneprot_gbt_split writes with kc = 1, bit for bit. */
+size_t oneprot_gbt_split_nodes_workspace(int F, int nodes);
+int oneprot_gbt_split_nodes(const int64_t* hist, const float* cuts, const int* ncuts, const void* feat_keep, const int* expo, int* tree_feat, int* tree_bin, float* tree_thr,
+                            float* tree_leaf, void* gain_bytes, void* workspace, size_t workspace_bytes, int F, int max_bin, int level, int node0, int nodes,
+                            int tree_nodes, float min_child_weight, float gamma, float reg_alpha, float reg_lambda, float learning_rate, void* stream);
+/* pos [kc, N]: a row in a node of this level (0 .. 8) that split moves to child 2 p + 1 (bin <= tree_bin) or 2 p + 2; every other row stays */
 int oneprot_gbt_partition(const void* bins, const int* tree_feat, const int* tree_bin, int* pos, int64_t N, int F, int level, int kc, int tree_nodes, void* stream);
 /* margin[i, k0 + kk] += tree_leaf[kk, pos[kk, i]] for the kc outputs of a chunk: every row, kept or dropped (margin fp32 [N, K]) */
 int oneprot_gbt_update(float* margin, const int* pos, const float* tree_leaf, int64_t N, int K, int k0, int kc, int tree_nodes, void* stream);

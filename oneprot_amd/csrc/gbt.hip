@@ -12,13 +12,25 @@
 // LDS tile of the histogram kernel: 64 (node, feature) slots x max_bin bins x {g, h} x int32 = 128 KB at max_bin 256, of the CU's 160 KB: one work-group of
 // sixteen waves per CU.  Level d has 2^d nodes, so a tile holds 64 >> d features of every node of the level; a wave's 64 lanes read 64 >> d consecutive
 // feature bytes of 2^d rows, and their LDS adds land in different features' (or nodes') bins.
+//
+// Levels 6 .. 8 (max_depth 7 .. 9, one output: XGBRegressor) have more nodes than the tile has slots, and at 1,280 features and 256 bins more bytes than the
+// histogram budget.  There the rows are put in node order once per level (k_gbt_node_keys -> the stable radix sort of metrics.hip -> k_gbt_node_seg), and
+// k_gbt_hist_nodes builds a group of nodes at a time: a work-group takes a run of GBT_ROWS consecutive positions of the order and walks the consecutive
+// nodes it meets, nt nodes x ft features (nt ft = 64) in the same LDS tile with the same int32 atomics, flushing whenever it leaves the tile's node span -- so
+// the bound of GBT_ROWS rows per counter between two flushes holds as before, and a larger node is the sum of several work-groups' flushes.  The split search
+// of a group is the two kernels of a level with a node offset (one body each, two launchers); partition, update and predict know no level limit but the
+// tree's size.  The rule is the same at every depth; levels 0 .. 5 run the kernels and launches they always ran.
 #include "philox.h"
 #include "../../include/oneprot_hip.h"
 
 #define GBT_FRAC 20
 #define GBT_ROWS 2047
 #define GBT_HIST_THREADS 1024    // the LDS tile admits one work-group per CU: sixteen waves share it, so that the CU has loads in flight while others add
-#define GBT_MAX_LEVEL 5          // max_depth <= 6: levels 0 .. 5 are histogrammed
+#define GBT_MAX_LEVEL 5          // levels 0 .. 5 (max_depth <= 6) are histogrammed by k_gbt_hist, which keeps every node of a level in one LDS tile
+#define GBT_DEEP_MAX_LEVEL 8     // levels 6 .. 8 (max_depth 7 .. 9, one output) are histogrammed by k_gbt_hist_nodes over the rows in node order, a node group at a time
+#define GBT_TILE_LOG2_L6 3       // features of a k_gbt_hist_nodes tile at levels 6, 7, 8 (log2): 8 features x 8 nodes, the fastest of the seven shapes at every
+#define GBT_TILE_LOG2_L7 3       // one of the three levels
+#define GBT_TILE_LOG2_L8 3
 typedef unsigned long long ull_t;
 typedef long long ll_t;
 enum { GO_LOGISTIC = 0, GO_SQUARED = 1, GO_SOFTMAX = 2 };
@@ -191,6 +203,87 @@ __global__ void __launch_bounds__(GBT_HIST_THREADS) k_gbt_hist(const unsigned ch
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// levels 6 .. 8 (K = 1): the rows in node order.  key = node of the level, or the sentinel 2^level for a row that stopped at a shallower leaf; the stable radix
+// sort of csrc/metrics.hip orders the rows by key; seg [2^level + 1] holds each node's lower bound in the sorted keys (seg[2^level]: where the sentinels begin).
+__global__ void __launch_bounds__(256) k_gbt_node_keys(const int* __restrict__ pos, int* __restrict__ keys, int64_t N, int level) {
+  const int L = 1 << level;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+    const int p = pos[i] - (L - 1);
+    keys[i] = (unsigned)p < (unsigned)L ? p : L;
+  }
+}
+__global__ void __launch_bounds__(256) k_gbt_node_seg(const int* __restrict__ skeys, int* __restrict__ seg, int64_t N, int level) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n > (1 << level)) return;
+  int64_t lo = 0, hi = N;                                      // first position with skeys[position] >= n
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (skeys[mid] < n) lo = mid + 1; else hi = mid;
+  }
+  seg[n] = (int)lo;
+}
+
+// hist of a node group [node0, node0 + nodes) of a deep level.  Work-group (x, y) = run x of GBT_ROWS consecutive positions of `order`, feature tiles y, y + gridDim.y, ...
+// of ft = 2^ftl features: the grid is a function of the shapes alone.  The LDS tile is k_gbt_hist's, [nt][ft][B][2] int32 with nt ft = 64: the work-group walks the
+// spans of nt consecutive nodes that its run meets (found through seg, clipped to the run), adds the span's rows, and flushes the non-zero counters with int64
+// global atomics before the next span and at the end -- so a counter never takes more than GBT_ROWS rows between two flushes, and a node larger than a run is
+// the sum of several work-groups' flushes.  Rows of nodes outside the group, sentinel rows, rows with g = h = 0 and bins >= B add nothing; a run that lies
+// wholly outside the group returns after reading its first and last key.  Every index read from device memory (seg, keys, order, bins) is checked before it
+// addresses anything.
+__global__ void __launch_bounds__(GBT_HIST_THREADS) k_gbt_hist_nodes(const unsigned char* __restrict__ bins, const int* __restrict__ gq, const int* __restrict__ hq,
+                                                        const int* __restrict__ order, const int* __restrict__ skeys, const int* __restrict__ seg, ll_t* __restrict__ hist,
+                                                        int64_t N, int F, int B, int level, int node0, int nodes, int ftl) {
+  extern __shared__ int lds[];
+  const int tid = threadIdx.x;
+  const int L = 1 << level, ft = 1 << ftl, ntl = 6 - ftl, nt = 1 << ntl;
+  const int64_t p0 = (int64_t)blockIdx.x * GBT_ROWS, p1 = p0 + GBT_ROWS < N ? p0 + GBT_ROWS : N;
+  if (p0 >= p1) return;
+  const int kfirst = skeys[p0], klast = skeys[p1 - 1];
+  const int lo = kfirst > node0 ? kfirst : node0, hi = klast < node0 + nodes - 1 ? klast : node0 + nodes - 1;      // the group's nodes this run can hold (hi < L: no sentinel)
+  if (lo > hi || lo < 0) return;                               // the same for every thread: before any barrier
+  const int entries = 128 * B;
+  for (int e = tid; e < entries; e += GBT_HIST_THREADS) lds[e] = 0;
+  __syncthreads();
+  const int fi = tid & (ft - 1), rs = tid >> ftl, rstep = GBT_HIST_THREADS >> ftl;
+  const int tiles = (F + ft - 1) >> ftl;
+  for (int tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
+    const int f0 = tile << ftl, f = f0 + fi;
+    for (int s = lo >> ntl; s <= (hi >> ntl); ++s) {
+      const int n0 = s << ntl;                                 // the span's first node; n0 + nt <= L
+      int64_t qs = seg[n0], qe = seg[n0 + nt];
+      qs = qs > p0 ? qs : p0;
+      qe = qe < p1 ? qe : p1;
+      if (qs >= qe) continue;                                  // (the same for every thread: seg is read-only here)
+      if (f < F) {
+        for (int64_t q = qs + rs; q < qe; q += rstep) {
+          const int k = skeys[q];
+          if ((unsigned)(k - n0) >= (unsigned)nt || (unsigned)(k - node0) >= (unsigned)nodes) continue;
+          const int r = order[q];
+          if ((unsigned)r >= (unsigned)N) continue;
+          const int g = gq[r], h = hq[r];
+          if ((g | h) == 0) continue;
+          const int b = bins[(size_t)r * F + f];
+          if (b >= B) continue;
+          const int idx = ((((k - n0) << ftl) + fi) * B + b) * 2;
+          if (g) atomicAdd(&lds[idx], g);
+          if (h) atomicAdd(&lds[idx + 1], h);
+        }
+      }
+      __syncthreads();
+      for (int e = tid; e < entries; e += GBT_HIST_THREADS) {
+        const int v = lds[e];
+        if (v == 0) continue;
+        lds[e] = 0;                                            // ready for the next span
+        const int c = e & 1, b = (e >> 1) % B, slot = (e >> 1) / B;
+        const int ff = f0 + (slot & (ft - 1)), n = n0 + (slot >> ftl) - node0;          // ff < F and 0 <= n < nodes: only such rows were added
+        atomicAdd((ull_t*)(hist + (((size_t)n * F + ff) * B + b) * 2 + c), (ull_t)(ll_t)v);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // split, in two launches.  The node's totals are the sums over all bins of a feature, the left sums the running prefix.  Gains in fp64 from the int64 sums;
 // best = largest gain, then lowest feature, then lowest cut.
 __device__ __forceinline__ double gbt_thr(double G, double alpha) {
@@ -229,11 +322,12 @@ __device__ __forceinline__ ll_t gbt_wave_scan(ll_t v, int lane) {
   }
   return v;
 }
-__global__ void __launch_bounds__(256) k_gbt_split_scan(const ll_t* __restrict__ hist, const int* __restrict__ ncuts, const unsigned char* __restrict__ feat_keep,
-                                                        const int* __restrict__ expo, GbtRec* __restrict__ rec, int F, int B, int level, double mcw, double alpha, double lambda) {
-  const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6), node = blockIdx.y, kk = blockIdx.z, L = 1 << level;
+// (the body is shared by the launch of a whole level, LH = 2^level nodes per output, and the launch of a node group of a deep level, LH = the group's nodes)
+__device__ __forceinline__ void gbt_split_scan_body(const ll_t* __restrict__ hist, const int* __restrict__ ncuts, const unsigned char* __restrict__ feat_keep,
+                                                    const int* __restrict__ expo, GbtRec* __restrict__ rec, int F, int B, int LH, double mcw, double alpha, double lambda) {
+  const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6), node = blockIdx.y, kk = blockIdx.z;
   if (f >= F) return;                                          // a whole wave; the kernel has no work-group barrier
-  const size_t slot = ((size_t)kk * L + node) * F + f;
+  const size_t slot = ((size_t)kk * LH + node) * F + f;
   const ll_t* Hf = hist + slot * B * 2;
   const int nc = ncuts[f];
   const double sg = ldexp(1.0, expo[kk] - GBT_FRAC), sh = ldexp(1.0, -GBT_FRAC);
@@ -280,16 +374,25 @@ __global__ void __launch_bounds__(256) k_gbt_split_scan(const ll_t* __restrict__
     rec[slot] = r;
   }
 }
+__global__ void __launch_bounds__(256) k_gbt_split_scan(const ll_t* __restrict__ hist, const int* __restrict__ ncuts, const unsigned char* __restrict__ feat_keep,
+                                                        const int* __restrict__ expo, GbtRec* __restrict__ rec, int F, int B, int level, double mcw, double alpha, double lambda) {
+  gbt_split_scan_body(hist, ncuts, feat_keep, expo, rec, F, B, 1 << level, mcw, alpha, lambda);
+}
+__global__ void __launch_bounds__(256) k_gbt_split_scan_nodes(const ll_t* __restrict__ hist, const int* __restrict__ ncuts, const unsigned char* __restrict__ feat_keep,
+                                                              const int* __restrict__ expo, GbtRec* __restrict__ rec, int F, int B, int nodes, double mcw, double alpha, double lambda) {
+  gbt_split_scan_body(hist, ncuts, feat_keep, expo, rec, F, B, nodes, mcw, alpha, lambda);
+}
 
 // stage 2: one work-group per (output, node): the ordered arg-max over the features' records (gain, then lowest feature, then lowest cut), and the node's entries
-__global__ void __launch_bounds__(256) k_gbt_split(const GbtRec* __restrict__ rec, const float* __restrict__ cuts, const int* __restrict__ expo, int* __restrict__ tree_feat,
-                                                   int* __restrict__ tree_bin, float* __restrict__ tree_thr, float* __restrict__ tree_leaf, double* __restrict__ gain_out, int F, int B,
-                                                   int level, int NN, double gamma, double alpha, double lambda, double lr) {
+// (LH: the nodes per output of rec; nid0: the heap id of rec's node 0 -- 2^level - 1 for a whole level, 2^level - 1 + node0 for a node group)
+__device__ __forceinline__ void gbt_split_body(const GbtRec* __restrict__ rec, const float* __restrict__ cuts, const int* __restrict__ expo, int* __restrict__ tree_feat,
+                                               int* __restrict__ tree_bin, float* __restrict__ tree_thr, float* __restrict__ tree_leaf, double* __restrict__ gain_out, int F, int B,
+                                               int LH, int nid0, int NN, double gamma, double alpha, double lambda, double lr) {
   __shared__ double s_gain[256];
   __shared__ int s_f[256], s_j[256];
   __shared__ ll_t s_GL[256], s_HL[256];
-  const int tid = threadIdx.x, node = blockIdx.x, kk = blockIdx.y, L = 1 << level;
-  const GbtRec* R = rec + ((size_t)kk * L + node) * F;
+  const int tid = threadIdx.x, node = blockIdx.x, kk = blockIdx.y;
+  const GbtRec* R = rec + ((size_t)kk * LH + node) * F;
   const double sg = ldexp(1.0, expo[kk] - GBT_FRAC), sh = ldexp(1.0, -GBT_FRAC);
   GbtBest best = {0.0, 0x7fffffff, 0x7fffffff, 0, 0};
   for (int f = tid; f < F; f += 256) {
@@ -312,7 +415,7 @@ __global__ void __launch_bounds__(256) k_gbt_split(const GbtRec* __restrict__ re
   const bool valid = best.f != 0x7fffffff;
   const ll_t G = R[0].G, H = R[0].H;                           // the node's totals: every row is in exactly one bin of every feature
   const size_t o = (size_t)kk * NN;
-  const int nid = L - 1 + node, lc = 2 * nid + 1;
+  const int nid = nid0 + node, lc = 2 * nid + 1;
   const bool split = valid && best.gain > (gamma > 0.0 ? gamma : 0.0);
   if (gain_out) gain_out[o + nid] = valid ? best.gain : -__builtin_inf();
   tree_leaf[o + nid] = (float)(lr * gbt_weight((double)G * sg, (double)H * sh, alpha, lambda));
@@ -325,6 +428,16 @@ __global__ void __launch_bounds__(256) k_gbt_split(const GbtRec* __restrict__ re
     tree_feat[o + nid] = -1; tree_bin[o + nid] = 0; tree_thr[o + nid] = 0.f;
     tree_feat[o + lc] = -1; tree_feat[o + lc + 1] = -1; tree_leaf[o + lc] = 0.f; tree_leaf[o + lc + 1] = 0.f;
   }
+}
+__global__ void __launch_bounds__(256) k_gbt_split(const GbtRec* __restrict__ rec, const float* __restrict__ cuts, const int* __restrict__ expo, int* __restrict__ tree_feat,
+                                                   int* __restrict__ tree_bin, float* __restrict__ tree_thr, float* __restrict__ tree_leaf, double* __restrict__ gain_out, int F, int B,
+                                                   int level, int NN, double gamma, double alpha, double lambda, double lr) {
+  gbt_split_body(rec, cuts, expo, tree_feat, tree_bin, tree_thr, tree_leaf, gain_out, F, B, 1 << level, (1 << level) - 1, NN, gamma, alpha, lambda, lr);
+}
+__global__ void __launch_bounds__(256) k_gbt_split_nodes(const GbtRec* __restrict__ rec, const float* __restrict__ cuts, const int* __restrict__ expo, int* __restrict__ tree_feat,
+                                                         int* __restrict__ tree_bin, float* __restrict__ tree_thr, float* __restrict__ tree_leaf, double* __restrict__ gain_out, int F, int B,
+                                                         int nodes, int nid0, int NN, double gamma, double alpha, double lambda, double lr) {
+  gbt_split_body(rec, cuts, expo, tree_feat, tree_bin, tree_thr, tree_leaf, gain_out, F, B, nodes, nid0, NN, gamma, alpha, lambda, lr);
 }
 
 // partition: a row in a node of this level that split moves to the left child iff bin <= cut index
@@ -454,8 +567,70 @@ extern "C" int oneprot_gbt_split(const int64_t* hist, const float* cuts, const i
   return launch_status();
 }
 
+// ---- levels 6 .. 8: node order, histogram and split search of a node group
+static bool gbt_deep_level(int level) { return level > GBT_MAX_LEVEL && level <= GBT_DEEP_MAX_LEVEL; }
+static bool gbt_group(int level, int node0, int nodes) { return gbt_deep_level(level) && node0 >= 0 && nodes >= 1 && node0 + nodes <= (1 << level); }
+
+extern "C" int oneprot_gbt_node_keys(const int* pos, int* keys, int64_t N, int level, void* stream) {
+  if (!pos || !keys || N < 1 || N > (1 << 24) || !gbt_deep_level(level)) return OP_EINVAL;
+  hipLaunchKernelGGL(k_gbt_node_keys, dim3(gbt_grid(N)), dim3(256), 0, (hipStream_t)stream, pos, keys, N, level);
+  return launch_status();
+}
+
+extern "C" int oneprot_gbt_node_seg(const int* sorted_keys, int* seg, int64_t N, int level, void* stream) {
+  if (!sorted_keys || !seg || N < 1 || N > (1 << 24) || !gbt_deep_level(level)) return OP_EINVAL;
+  hipLaunchKernelGGL(k_gbt_node_seg, dim3(((1 << level) + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, sorted_keys, seg, N, level);
+  return launch_status();
+}
+
+// the tile of k_gbt_hist_nodes per level, log2 of its features (the nodes of a tile are 64 over that): DESIGN.md section 6 has the shapes tried
+static int gbt_tile_log2(int level) { return level == 6 ? GBT_TILE_LOG2_L6 : level == 7 ? GBT_TILE_LOG2_L7 : GBT_TILE_LOG2_L8; }
+
+extern "C" size_t oneprot_gbt_hist_nodes_bytes(int F, int max_bin, int nodes) {
+  if (F < 1 || F > 65535 || max_bin < 2 || max_bin > 256 || nodes < 1 || nodes > (1 << GBT_DEEP_MAX_LEVEL)) return 0;
+  return (size_t)nodes * (size_t)F * (size_t)max_bin * 2 * sizeof(int64_t);
+}
+
+extern "C" int oneprot_gbt_hist_nodes(const void* bins, const int* gq, const int* hq, const int* order, const int* sorted_keys, const int* seg, int64_t* hist, int64_t N, int F,
+                                      int max_bin, int level, int node0, int nodes, int tile_features, void* stream) {
+  if (!bins || !gq || !hq || !order || !sorted_keys || !seg || !hist || !gbt_shape(N, F, max_bin) || !gbt_group(level, node0, nodes)) return OP_EINVAL;
+  int ftl = gbt_tile_log2(level);
+  if (tile_features != 0) {
+    if (tile_features < 1 || tile_features > 64 || (tile_features & (tile_features - 1))) return OP_EINVAL;
+    ftl = __builtin_ctz((unsigned)tile_features);
+  }
+  const int64_t gx = (N + GBT_ROWS - 1) / GBT_ROWS, tiles = (F + (1 << ftl) - 1) >> ftl, cap = (((int64_t)1 << 22) - 1) / gx;     // below 2^22 work-groups of 1024 threads
+  const int64_t gy = tiles < cap ? (tiles < 65535 ? tiles : 65535) : (cap < 65535 ? cap : 65535);      // (gx <= 8198, so cap >= 511; a work-group strides over the tiles beyond gy)
+  const size_t lds = (size_t)128 * max_bin * sizeof(int);
+  if (hipMemsetAsync(hist, 0, oneprot_gbt_hist_nodes_bytes(F, max_bin, nodes), (hipStream_t)stream) != hipSuccess) return OP_ELAUNCH;
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)k_gbt_hist_nodes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return OP_ELAUNCH;
+  hipLaunchKernelGGL(k_gbt_hist_nodes, dim3((unsigned)gx, (unsigned)gy), dim3(GBT_HIST_THREADS), lds, (hipStream_t)stream, (const unsigned char*)bins, gq, hq, order, sorted_keys, seg,
+                     (ll_t*)hist, N, F, max_bin, level, node0, nodes, ftl);
+  return launch_status();
+}
+
+extern "C" size_t oneprot_gbt_split_nodes_workspace(int F, int nodes) {
+  if (F < 1 || F > 65535 || nodes < 1 || nodes > (1 << GBT_DEEP_MAX_LEVEL)) return 0;
+  return (size_t)nodes * (size_t)F * sizeof(GbtRec);
+}
+
+// (levels 0 .. 5 are taken too, with any group: a whole shallow level through here gives oneprot_gbt_split's bits, which the tests hold it to)
+extern "C" int oneprot_gbt_split_nodes(const int64_t* hist, const float* cuts, const int* ncuts, const void* feat_keep, const int* expo, int* tree_feat, int* tree_bin, float* tree_thr,
+                                       float* tree_leaf, void* gain_bytes, void* workspace, size_t workspace_bytes, int F, int max_bin, int level, int node0, int nodes,
+                                       int tree_nodes, float min_child_weight, float gamma, float reg_alpha, float reg_lambda, float learning_rate, void* stream) {
+  if (!hist || !cuts || !ncuts || !feat_keep || !expo || !tree_feat || !tree_bin || !tree_thr || !tree_leaf || !workspace || !gbt_shape(1, F, max_bin)) return OP_EINVAL;
+  if (level < 0 || level > GBT_DEEP_MAX_LEVEL || node0 < 0 || nodes < 1 || node0 + nodes > (1 << level) || tree_nodes < (4 << level) - 1 || !(reg_lambda >= 0.f) || !(reg_alpha >= 0.f))
+    return OP_EINVAL;
+  if (workspace_bytes < oneprot_gbt_split_nodes_workspace(F, nodes) || ((uintptr_t)workspace & 7)) return OP_EINVAL;
+  hipLaunchKernelGGL(k_gbt_split_scan_nodes, dim3((F + 3) / 4, nodes, 1), dim3(256), 0, (hipStream_t)stream, (const ll_t*)hist, ncuts, (const unsigned char*)feat_keep, expo,
+                     (GbtRec*)workspace, F, max_bin, nodes, (double)min_child_weight, (double)reg_alpha, (double)reg_lambda);
+  hipLaunchKernelGGL(k_gbt_split_nodes, dim3(nodes, 1), dim3(256), 0, (hipStream_t)stream, (const GbtRec*)workspace, cuts, expo, tree_feat, tree_bin, tree_thr, tree_leaf,
+                     (double*)gain_bytes, F, max_bin, nodes, (1 << level) - 1 + node0, tree_nodes, (double)gamma, (double)reg_alpha, (double)reg_lambda, (double)learning_rate);
+  return launch_status();
+}
+
 extern "C" int oneprot_gbt_partition(const void* bins, const int* tree_feat, const int* tree_bin, int* pos, int64_t N, int F, int level, int kc, int tree_nodes, void* stream) {
-  if (!bins || !tree_feat || !tree_bin || !pos || !gbt_shape(N, F, 2) || level < 0 || level > GBT_MAX_LEVEL || kc < 1 || kc > 65535 || tree_nodes < (4 << level) - 1) return OP_EINVAL;
+  if (!bins || !tree_feat || !tree_bin || !pos || !gbt_shape(N, F, 2) || level < 0 || level > GBT_DEEP_MAX_LEVEL || kc < 1 || kc > 65535 || tree_nodes < (4 << level) - 1) return OP_EINVAL;
   const unsigned gx = gbt_grid(N) < 65536 ? gbt_grid(N) : 65536;
   hipLaunchKernelGGL(k_gbt_partition, dim3(gx, kc), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)bins, tree_feat, tree_bin, pos, N, F, level, tree_nodes);
   return launch_status();

@@ -7,6 +7,11 @@ arrays.  `fit` reads back once (the finiteness check of X) before its final stat
 children.  Histograms of K outputs are built in chunks of outputs that fit ONEPROT_GBT_HIST_BYTES (default 1 GiB); the chunking is a pure function of (K, F,
 max_bin, max_depth, budget) and cannot change a bit of the result, because every output is built by its own work-groups and every sum is an integer sum.
 
+Depth: XGBClassifier builds max_depth 1 .. 6, XGBRegressor (one output) 1 .. 9, as the reference's regression sweep asks (3, 5, 9).  Levels 0 .. 5 keep every
+node of a level in one LDS tile; levels 6 .. 8 run through oneprot_amd/gbt_deep.py: the rows in node order once per level, then histogram -> split search per
+group of nodes (plan_node_groups: the largest power of two of nodes that fits the same budget), then one partition launch for the level.  The grouping is a
+pure function of (F, max_bin, level, budget) and cannot change a bit either.  The rule is one rule at every depth.
+
 NOT pinned: parity with xgboost, which is not installed here.  The rule is the published one (Chen & Guestrin 2016, the `hist` method,
 fixed-point histograms as gpu_hist keeps them), stated exactly in DESIGN.md section 7 and restated independently in tests/gbt_ref.py; every random draw comes
 from this library's own Philox streams.  Bit-identical between runs: gradients are integers before they are summed."""
@@ -17,11 +22,12 @@ import os
 import numpy as np
 import torch
 
-from . import downstream, hip, rng
+from . import downstream, gbt_deep, hip, rng
 
 RNG_DOMAIN_GBT = rng.DOMAINS["gbt"]
 FRAC = 20                      # fraction bits of the fixed-point gradients (csrc/gbt.hip GBT_FRAC)
-MAX_DEPTH = 6
+MAX_DEPTH = 9                  # the largest depth this module builds (XGBRegressor; every class has its own cap, `_max_depth`)
+SHALLOW_DEPTH = 6              # up to here a level's nodes share one LDS tile (levels 0 .. 5); deeper levels run through gbt_deep
 OBJECTIVES = {"binary:logistic": 0, "reg:squarederror": 1, "multi:softmax": 2}
 _KNOWN = ("n_estimators", "max_depth", "learning_rate", "objective", "booster", "tree_method", "n_jobs", "min_child_weight", "gamma", "subsample",
           "colsample_bytree", "reg_alpha", "reg_lambda", "eval_metric", "base_score", "max_bin", "random_state")
@@ -42,6 +48,19 @@ def plan_chunks(K, F, max_bin, max_depth, budget=None):
     if kc < 1:
         raise ValueError(f"ONEPROT_GBT_HIST_BYTES = {budget} does not hold one output's histogram ({per_output} bytes at depth {max_depth}, {F} features, {max_bin} bins)")
     return [(k0, min(K, k0 + kc)) for k0 in range(0, K, kc)]
+
+
+def plan_node_groups(F, max_bin, level, budget=None):
+    """[(node0, node1), ...]: the 2^level nodes of a level in consecutive groups whose histograms (F x max_bin x 16 bytes a node) fit `budget` bytes.  The group
+    size is the largest power of two that is at most min(2^level, budget // bytes of a node).  A pure function of its arguments; a budget that does not hold
+    one node raises ValueError."""
+    budget = hist_bytes_budget() if budget is None else int(budget)
+    per_node, L = F * max_bin * 16, 1 << level
+    fit = min(L, budget // per_node)
+    if fit < 1:
+        raise ValueError(f"ONEPROT_GBT_HIST_BYTES = {budget} does not hold one node's histogram ({per_node} bytes at {F} features, {max_bin} bins)")
+    g = 1 << (fit.bit_length() - 1)
+    return [(n0, n0 + g) for n0 in range(0, L, g)]
 
 
 def stream_of(local):
@@ -80,6 +99,7 @@ def build_cuts(X, max_bin):
 class _GBT:
     """what XGBClassifier and XGBRegressor share: the keywords, the round loop, the ensemble walk and the state dict"""
     _default_objective = None
+    _max_depth = SHALLOW_DEPTH
 
     def __init__(self, *, n_estimators=100, max_depth=6, learning_rate=0.3, objective=None, booster="gbtree", tree_method="auto", n_jobs=None, min_child_weight=1.0,
                  gamma=0.0, subsample=1.0, colsample_bytree=1.0, reg_alpha=0.0, reg_lambda=1.0, eval_metric=None, base_score=0.5, max_bin=256, random_state=0,
@@ -87,8 +107,8 @@ class _GBT:
         if booster is not None and booster != "gbtree":
             raise NotImplementedError(f"booster={booster!r}: only gbtree is built")
         max_depth, n_estimators, max_bin = int(max_depth), int(n_estimators), int(max_bin)
-        if not 1 <= max_depth <= MAX_DEPTH:
-            raise NotImplementedError(f"max_depth={max_depth}: 1 .. {MAX_DEPTH} are built (a level's histograms are sized for at most 32 nodes)")
+        if not 1 <= max_depth <= self._max_depth:
+            raise NotImplementedError(f"max_depth={max_depth}: {type(self).__name__} builds 1 .. {self._max_depth}")
         if n_estimators < 1:
             raise ValueError("n_estimators must be at least 1")
         if not 2 <= max_bin <= 256:
@@ -109,7 +129,7 @@ class _GBT:
         self.booster, self.tree_method, self.n_jobs, self.eval_metric = "gbtree", tree_method, n_jobs, eval_metric     # accepted and kept; nothing here depends on them
         self.kwargs = dict(kwargs)                                             # `name` and other unknown keywords, kept as xgboost keeps them
         self._state = None
-        self.train_margin_ = None
+        self.train_margin_ = self.train_pos_ = None
 
     def get_params(self):
         return {**{k: getattr(self, k) for k in _KNOWN}, **self.kwargs}
@@ -158,7 +178,13 @@ class _GBT:
             raise ValueError("fit: X holds NaN or inf")
         target, labels, K = self._targets(y, N)
         dev, D, NN, B, T = x.device, self.max_depth, self.tree_nodes, self.max_bin, self.n_estimators
-        chunks = plan_chunks(K, F, B, D)
+        DS = min(D, SHALLOW_DEPTH)                                             # levels 0 .. DS - 1 in chunks of outputs, levels DS .. D - 1 (one output) in groups of nodes
+        groups = {level: plan_node_groups(F, B, level) for level in range(DS, D)}
+        if groups and K != 1:
+            raise NotImplementedError(f"max_depth={D} with {K} outputs: levels beyond {SHALLOW_DEPTH - 1} are built for one output")
+        # a deep fit has one output: the budget sizes its node groups, and its levels 0 .. 5 take the 32 nodes of level 5 whatever the budget says (the floor
+        # of a deep fit's histogram buffer) -- plan_chunks, whose values are pinned, would refuse a budget below them
+        chunks = [(0, 1)] if groups else plan_chunks(K, F, B, D)
         cuts, ncuts, bins = build_cuts(x, B)
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
         tree_feat = torch.full((T, K, NN), -1, dtype=torch.int32, device=dev)
@@ -171,8 +197,9 @@ class _GBT:
         feat_keep = torch.empty(F, dtype=torch.uint8, device=dev)
         feat_u = i32(F)
         kc_max = max(k1 - k0 for k0, k1 in chunks)
-        hist = torch.empty(kc_max * hip.query("oneprot_gbt_hist_bytes", F, B, D - 1) // 8, dtype=torch.int64, device=dev)
-        split_ws = torch.empty(hip.query("oneprot_gbt_split_workspace", F, D - 1, kc_max), dtype=torch.uint8, device=dev)
+        deep = gbt_deep.DeepLevels(N, F, B, D, groups, dev) if groups else None
+        hist = torch.empty(max(kc_max * hip.query("oneprot_gbt_hist_bytes", F, B, DS - 1), deep.hist_bytes if deep else 0) // 8, dtype=torch.int64, device=dev)
+        split_ws = torch.empty(hip.query("oneprot_gbt_split_workspace", F, DS - 1, kc_max), dtype=torch.uint8, device=dev)
         n_keep = F if self.colsample_bytree >= 1.0 else max(1, int(math.floor(F * self.colsample_bytree)))
         obj, seed = OBJECTIVES[self.objective], self.random_state & 0xFFFFFFFFFFFFFFFF
         for t in range(T):
@@ -182,15 +209,19 @@ class _GBT:
             for k0, k1 in chunks:
                 kc = k1 - k0
                 tf, tb, tt, tl = tree_feat[t, k0:k1], tree_bin[t, k0:k1], tree_thr[t, k0:k1], tree_leaf[t, k0:k1]
-                for level in range(D):
+                for level in range(DS):
                     hip.call("oneprot_gbt_hist", bins, gq[k0:k1], hq[k0:k1], pos[k0:k1], hist, N, F, B, level, kc)
                     hip.call("oneprot_gbt_split", hist, cuts, ncuts, feat_keep, expo[k0:k1], tf, tb, tt, tl, None, split_ws, split_ws.numel(), F, B, level, kc, NN, self.min_child_weight,
                              self.gamma, self.reg_alpha, self.reg_lambda, self.learning_rate)
                     hip.call("oneprot_gbt_partition", bins, tf, tb, pos[k0:k1], N, F, level, kc, NN)
+                for level in range(DS, D):
+                    deep.run(level, hist, bins, gq, hq, pos, cuts, ncuts, feat_keep, expo, tf, tb, tt, tl, NN, self.min_child_weight, self.gamma, self.reg_alpha,
+                             self.reg_lambda, self.learning_rate)
                 hip.call("oneprot_gbt_update", margin, pos[k0:k1], tl, N, K, k0, kc, NN)
         self._state = dict(cuts=cuts, ncuts=ncuts, tree_feat=tree_feat, tree_bin=tree_bin, tree_thr=tree_thr, tree_leaf=tree_leaf)
         self.n_outputs_, self.n_features_in_ = K, F
         self.train_margin_ = margin                                            # the margin fit ended with: predict_margin of the training rows gives the same bits
+        self.train_pos_ = pos                                                  # int32 [K, N]: the heap node every row ended in, in the last round
         return self
 
     # ---- predict
@@ -257,8 +288,10 @@ class XGBClassifier(_GBT):
 
 
 class XGBRegressor(_GBT):
-    """ref saprot_fit_reg.py:26-32"""
+    """ref saprot_fit_reg.py:26-32.  One output, so depths 7 .. 9 are built too (levels 6 .. 8 in groups of nodes: oneprot_amd/gbt_deep.py), as the reference's
+    regression sweep asks (max_depth 3, 5, 9)."""
     _default_objective = "reg:squarederror"
+    _max_depth = MAX_DEPTH
 
     def predict(self, X):
         return self.predict_margin(X).squeeze(1)

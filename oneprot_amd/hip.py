@@ -9,7 +9,7 @@ parsed from it at import, so a new entry point is declared there, defined in csr
 launchers of the four widest ones and end in the same call().  sort_f32 / sort_i32 / midranks_f32 / inclusive_scan / moments / f1max are the launchers of the
 downstream-metric entry points (csrc/metrics.hip): they size and allocate the workspace, and hand back device tensors (fp64 results as views of byte buffers).
 probe_linear_fwd / probe_rownorm_act_fwd / probe_norm_act_bwd / probe_rownorm_act_bwd / probe_loss are the keyword launchers of the MLP probe's wide entry points
-(csrc/probe.hip).  The gradient-boosted tree entry points (csrc/gbt.hip, oneprot_gbt_*) are called by name from oneprot_amd/gbt.py, the text-input entry
+(csrc/probe.hip).  The gradient-boosted tree entry points (csrc/gbt.hip, oneprot_gbt_*) are called by name from oneprot_amd/gbt.py and oneprot_amd/gbt_deep.py, the text-input entry
 point (csrc/wordpiece.hip, oneprot_wordpiece_encode) from oneprot_amd/text_data.py.
 """
 import ctypes
