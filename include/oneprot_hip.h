@@ -498,6 +498,29 @@ int oneprot_wordpiece_encode(const void* text_bytes, const int64_t* offsets, con
                              int n_texts, int n_blocks, int n_pool, int n_slots, int n_vocab_chars, int max_piece_chars, int max_length, int cls_id,
                              int sep_id, int unk_id, int pad_id, void* stream);
 
+/* ---------------- graph input (ref src/data/utils/struct_graph_utils.py:31-144: `get_atom_pos`, `compute_diherals`, `calc_side_chain_embs`,
+ * `calc_bb_embs`, called once per protein by protein_to_graph) -------------------------------------------------------------------------------------------
+ * The atom records of a whole batch of G proteins to the tensors of its GraphBatch, two launches on `stream`, one thread per residue, fp32, no
+ * atomics, no workspace, nothing read back (csrc/graph_feats.hip; the rule is stated once in DESIGN.md section 7 and is the four host functions of
+ * oneprot_amd/graph_data.py).  A residue's results depend on its own atoms and on the N / CA / C of its two neighbours inside its protein only, so a
+ * protein gets the same bits alone and in any batch.
+ * atom_pos fp32 [A, 3]; atom_name4 [A]: the first four bytes of every atom name, zero padded, as one 32-bit word (numpy's `names.astype("S4")` viewed
+ * as 32-bit words; the 20 names of the nine places have at most 3 bytes, so cutting a longer name can make no match); res_atom_ptr int64 [N + 1]:
+ * residue r owns the atoms [res_atom_ptr[r], res_atom_ptr[r + 1]), possibly none; res_type_bytes uint8 [N]; graph_ptr int64 [G + 1]: protein g owns
+ * the residues [graph_ptr[g], graph_ptr[g + 1]).  res_atom_ptr_host / graph_ptr_host: the same two tables in host memory, from which the call validates.
+ * Out: x int64 [N, 1]; coords_ca / coords_n / coords_c fp32 [N, 3] (for each of N, CA, C, CB, *G, *D, *E, *Z, NH1 the LAST atom of the run whose
+ * name is in the place's set, NaN without one; a NaN component of N or C takes CA's); bb_embs fp32 [N, 6] (cos then sin of phi, psi, omega along
+ * the protein's N, CA, C chain, differences normalised; phi of a protein's first residue and psi, omega of its last are angle 0); side_chain_embs
+ * fp32 [N, 8] (sin then cos of the four torsions over N-CA-CB-G-D-E-Z); batch int64 [N]; ptr int64 [G + 1].  Wherever the host's nan_to_num chain
+ * yields angle 0 (a NaN operand, a zero middle vector, atan2(0, 0)) the outputs are exactly (sin, cos) = (0, 1).
+ * Refused with -1 before any launch: a NULL pointer, N or G below 1, N above ONEPROT_GRAPH_MAX_NODES, G above N, a table that does not start at 0 or
+ * that decreases, a graph_ptr that does not end at N, a res_atom_ptr that does not end at A. */
+#define ONEPROT_GRAPH_MAX_NODES 67108864
+int oneprot_graph_featurize(const float* atom_pos, const int* atom_name4, const int64_t* res_atom_ptr, const void* res_type_bytes,
+                            const int64_t* graph_ptr, int64_t* x, float* coords_ca, float* coords_n, float* coords_c, float* bb_embs,
+                            float* side_chain_embs, int64_t* batch, int64_t* ptr, const int64_t* res_atom_ptr_host, const int64_t* graph_ptr_host,
+                            int64_t A, int64_t N, int G, void* stream);
+
 /* ---------------- ProNet tower (ref src/models/components/struct_graph_encoder.py:5-42 plugs in dig.threedgraph.method.ProNet; the arithmetic is the
  * published model's, Wang et al. 2023, restated: DESIGN.md section 7, tests/pronet_ref.py is the oracle) ----------------------------------------------
  * N nodes of n_graphs graphs in one batch, a graph's nodes contiguous: graph_ptr int32 [n_graphs + 1], batch int32 [N].  Edges are stored by target in a

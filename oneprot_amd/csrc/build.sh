@@ -4,7 +4,7 @@
 # instantiation carries scratch (a register spill), so that a spill regression cannot reach a bench run unnoticed.
 set -e
 cd "$(dirname "$0")"
-SRCS="rowops.hip gemm_nt.hip gemm_nt8.hip gemm_nt_ln.hip gemm_tn.hip sgemm.hip attention.hip featops.hip retrieval.hip msa.hip msa_select.hip wordpiece.hip pronet.hip metrics.hip probe.hip gbt.hip"
+SRCS="rowops.hip gemm_nt.hip gemm_nt8.hip gemm_nt_ln.hip gemm_tn.hip sgemm.hip attention.hip featops.hip retrieval.hip msa.hip msa_select.hip wordpiece.hip graph_feats.hip pronet.hip metrics.hip probe.hip gbt.hip"
 HDRS="$(ls *.h) ../../include/oneprot_hip.h"      # every unit depends on every header: no list to keep by hand
 OBJS=""
 PIDS=""

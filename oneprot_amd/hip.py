@@ -10,7 +10,8 @@ launchers of the four widest ones and end in the same call().  sort_f32 / sort_i
 downstream-metric entry points (csrc/metrics.hip): they size and allocate the workspace, and hand back device tensors (fp64 results as views of byte buffers).
 probe_linear_fwd / probe_rownorm_act_fwd / probe_norm_act_bwd / probe_rownorm_act_bwd / probe_loss are the keyword launchers of the MLP probe's wide entry points
 (csrc/probe.hip).  The gradient-boosted tree entry points (csrc/gbt.hip, oneprot_gbt_*) are called by name from oneprot_amd/gbt.py and oneprot_amd/gbt_deep.py, the text-input entry
-point (csrc/wordpiece.hip, oneprot_wordpiece_encode) from oneprot_amd/text_data.py.
+point (csrc/wordpiece.hip, oneprot_wordpiece_encode) from oneprot_amd/text_data.py, the graph-input entry point (csrc/graph_feats.hip,
+oneprot_graph_featurize) from oneprot_amd/graph_data.py.
 """
 import ctypes
 import os
@@ -43,7 +44,7 @@ _RETURNS = {"int": c_int, "size_t": c_size_t, "int64_t": c_int64, "void": None}
 # Element type of a pointer argument: f = float32, h = bfloat16, l = int64, i = int32, b = uint8 workspace, * = stated by a flag argument / epilogue id.
 # A typed pointer says it itself and a void* is bf16 storage (the header's convention).  The void* that are not bf16 are named here, and nowhere else:
 _PTR_LETTER = {"float": "f", "int64_t": "l", "int": "i", "void": "h"}
-_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes", "moments_bytes", "f1_bytes", "loss_bytes", "bins", "row_keep", "feat_keep", "gain_bytes", "text_bytes"}      # by parameter name, in every entry point (fp64 results travel as bytes)
+_BYTE_PTRS = {"workspace", "sched_ws", "keep", "msa_bytes", "moments_bytes", "f1_bytes", "loss_bytes", "bins", "row_keep", "feat_keep", "gain_bytes", "text_bytes", "res_type_bytes"}      # by parameter name, in every entry point (fp64 results travel as bytes)
 _FLAG_TYPED_PTRS = {("oneprot_gemm_bf16_nt", "out0"), ("oneprot_gemm_bf16_nt", "out1"), ("oneprot_gemm_bf16_nt", "aux"),
                     ("oneprot_layernorm_fwd", "x"), ("oneprot_layernorm_bwd", "dy"), ("oneprot_layernorm_bwd", "x"),
                     ("oneprot_inclusive_scan", "x"), ("oneprot_inclusive_scan", "y"), ("oneprot_moments", "a"), ("oneprot_moments", "b"), ("oneprot_f1max", "target")}
