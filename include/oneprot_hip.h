@@ -158,6 +158,18 @@ void oneprot_cu_reserve(int cus);
 /* workspace_bytes = size of `workspace`; -1 (invalid argument) when it is smaller than oneprot_gemm_bf16_tn_workspace(N, K). */
 int oneprot_gemm_bf16_tn(const void* dY, const void* X, int64_t M, int N, int K, int ldy, int ldx, float* dW, float* dbias, void* workspace,
                          size_t workspace_bytes, int accumulate, void* stream);
+/* The weight gradient above AND a LayerNorm backward over the same M token rows of width K in one launch, on disjoint CUs: the matrix work-groups leave half of the
+   HBM rate unused, the row work-groups issue no MFMA, and neither waits for the other.  The LayerNorm half is oneprot_layernorm_bwd(dy bf16, x fp32) on
+   [M, K]: dx = (add_to ? add_to : 0) + LN'(dy) (add_to may alias dx), optional bf16 copy -- both bit-identical to that entry point, row for row -- and
+   dgamma / dbeta (optional, together) through ln_partial, at least ln_cus * 2 * K floats (oneprot_layernorm_bwd_workspace(K) bytes always suffice).
+   ln_cus: the CUs (= work-groups) of the LayerNorm role, a multiple of 8 in [8, CUs - 64]; dW / dbias are then, bit for bit, those of oneprot_gemm_bf16_tn
+   under oneprot_cu_reserve(ln_cus) (the process-wide reserve itself is not read).  Served: the 8-phase form with 256 x 320 tiles (K % 320 == 0, N % 64 == 0,
+   N >= 256), M % 32 == 0, K <= 1280; anything else returns -1 before any launch and the caller keeps the two entry points. */
+int oneprot_gemm_tn_ln_bwd_eligible(int64_t M, int N, int K);
+int oneprot_gemm_tn_ln_bwd(const void* dY, const void* X, int64_t M, int N, int K, int ldy, int ldx, float* dW, float* dbias, void* workspace,
+                           size_t workspace_bytes, int accumulate, const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                           const float* add_to, float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* ln_partial, int accumulate_param_grads,
+                           int ln_cus, void* stream);
 /* fp32 GEMM for the small head / logits contractions (ref base_encoder.py:155,159,164; loss.py:91-99):
    C[M,N] = alpha * op(A) * op(B) (+ C if accumulate);  transA: A stored [K,M]; transB: B stored [K,N] else [N,K]. */
 int oneprot_sgemm(const float* A, const float* B, float* C, int M, int N, int K, int transA, int b_is_kn, float alpha, int accumulate, void* stream);

@@ -11,6 +11,7 @@ import sys
 RULES = [
     (r"^void g8::k_gemm8<", 0),                 # every 8-phase NT GEMM instantiation (FFN-1 with one or two outputs, QKV + RoPE, dgrads, ...)
     (r"^void k_gemm_tn8<", 0),                  # 8-phase weight-gradient GEMM
+    (r"^void k_gemm_tn8_ln<", 0),               # ... with the LayerNorm-backward role on its own CUs: no scratch in either role
     (r"^void gln::k_gemm_ln", 0),               # out-projection + residual + LayerNorm
     (r"^void k_attn_fwd3<", 0),                 # persistent attention forward
     (r"^void k_attn_fwd3w<", 0),                # ... for 128-byte rows (hd 64): 256 registers; the short per-tile list of k_attn_fwd3 (round 6) spilled 20 bytes here and was not taken over

@@ -10,6 +10,7 @@
 //   * LDS rows are 256 B; 16-byte chunks are XOR-swizzled with 2*((row&3)|((row>>3)&1)<<2) so the 8 rows a half-wave
 //     transposed read touches fall in 8 different 32-byte bank slots (source-side swizzle for the LDS-DMA).
 #include "common.h"
+#include "ln_bwd_row.h"
 #include "../../include/oneprot_hip.h"
 
 #define TN_MAX_SLAB_TILES 512
@@ -308,9 +309,10 @@ extern "C" int oneprot_tn8_debug_read(unsigned long long* dst) { return hipMemcp
 #define TN8_RING 4
 
 // YC x XC = output tile (dY columns x X columns): 256 x 320 or 320 x 256
+// the work item w (split-major: split = w / tiles_all) of a launch; k_gemm_tn8 and the weight-gradient role of k_gemm_tn8_ln are this body
 template <int YC, int XC>
-__global__ void __launch_bounds__(512, 2) k_gemm_tn8(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X, int M, int N, int K, int ldy, int ldx,
-                                                     float* __restrict__ slab, float* __restrict__ bias_slab, int tiles_k, int tiles_all, int S) {
+__device__ __forceinline__ void tn8_work_item(int w, const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X, int M, int N, int K, int ldy, int ldx,
+                                              float* __restrict__ slab, float* __restrict__ bias_slab, int tiles_k, int tiles_all, int S) {
   constexpr int MT = YC / 64, NT = XC / 32;                 // 16 x 16 accumulator tiles per wave: 4 x 10 or 5 x 8
   constexpr int PY = YC * 2, PX = XC * 2;                   // LDS row pitch of the slabs (bytes)
   constexpr int UY = 32 * PY, UX = 32 * PX, UNIT = UY + UX; // 36 KB
@@ -319,10 +321,6 @@ __global__ void __launch_bounds__(512, 2) k_gemm_tn8(const bf16_t* __restrict__ 
   constexpr int NBY = PY == 640 ? 1 : 2, NBX = PX == 640 ? 2 : 4;      // gather bases per read (see the header comment)
   static_assert(MT * NT == 40 && NP == 36 && IPW == 5, "tile");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int per_xcd = gridDim.x >> 3;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int w = xcd * per_xcd + seq;                        // split-major work items, a contiguous run per XCD (see k_gemm_tn)
-  if (w >= tiles_all * S) return;
   const int split = w / tiles_all, tile = w - split * tiles_all;
   const int tn = tile / tiles_k, tk = tile - tn * tiles_k;
   const int n0 = tn * YC, k0 = tk * XC;
@@ -478,6 +476,94 @@ __global__ void __launch_bounds__(512, 2) k_gemm_tn8(const bf16_t* __restrict__ 
   }
 }
 
+template <int YC, int XC>
+__global__ void __launch_bounds__(512, 2) k_gemm_tn8(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X, int M, int N, int K, int ldy, int ldx,
+                                                     float* __restrict__ slab, float* __restrict__ bias_slab, int tiles_k, int tiles_all, int S) {
+  const int per_xcd = gridDim.x >> 3;
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int w = xcd * per_xcd + seq;                        // split-major work items, a contiguous run per XCD (see k_gemm_tn)
+  if (w >= tiles_all * S) return;
+  tn8_work_item<YC, XC>(w, dY, X, M, N, K, ldy, ldx, slab, bias_slab, tiles_k, tiles_all, S);
+}
+
+// =====================================================================================================================================
+// Weight gradient and LayerNorm backward in ONE launch, on disjoint CUs (one 512-thread work-group per CU: the 144 KB ring admits no second one).
+//   * work-groups [0, n_tn) are the work items of k_gemm_tn8<256, 320>, body and XCD decode unchanged (n_tn a multiple of 8);
+//   * work-groups [n_tn, n_tn + R) walk the token rows of the LayerNorm backward, one row per wave at a time with the loads of the next two rows already
+//     requested (one row where a row takes five float4s per lane: a third row does not fit the registers) -- 8 waves per CU instead of the 16-20 of
+//     k_layernorm_bwd, so the rows in flight cover the latency instead; row body of ln_bwd_row.h; the eight waves' dgamma / dbeta partials meet in LDS and go
+//     out as partial[role work-group][2][d].
+// The matrix role is bound by its LDS gathers and leaves half of the HBM rate unused; the row role is a pure HBM stream without one MFMA.  Neither role
+// waits for the other: no cross-work-group wait, no atomic, no polling -- a work-group that finds no CU free simply runs later.
+template <int NV>
+__global__ void __launch_bounds__(512, 2) k_gemm_tn8_ln(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ X, int M, int N, int K, int ldy, int ldx,
+                                                        float* __restrict__ slab, float* __restrict__ bias_slab, int tiles_k, int tiles_all, int S, int n_tn,
+                                                        const bf16_t* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ gamma,
+                                                        const float* __restrict__ mean_in, const float* __restrict__ rstd_in, const float* add_to, float* dx_out,
+                                                        bf16_t* __restrict__ dx_bf16, float* __restrict__ partial) {
+  constexpr int LN_AHEAD = NV <= 4 ? 2 : 1;
+  if ((int)blockIdx.x < n_tn) {
+    const int per_xcd = n_tn >> 3;
+    const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+    const int w = xcd * per_xcd + seq;
+    if (w >= tiles_all * S) return;
+    tn8_work_item<256, 320>(w, dY, X, M, N, K, ldy, ldx, slab, bias_slab, tiles_k, tiles_all, S);
+    return;
+  }
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* s_part = reinterpret_cast<float*>(smem);           // [8 waves][2][d]
+  const int T = M, d = K;                                   // the rows the weight gradient contracts over, the width of its X operand
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int rb = (int)blockIdx.x - n_tn, stride = ((int)gridDim.x - n_tn) * 8;
+  const int nv4 = d >> 2;
+  const float inv_d = 1.0f / (float)d;
+  float4 dg[NV], db[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    dg[i] = make_float4(0, 0, 0, 0);
+    db[i] = make_float4(0, 0, 0, 0);
+  }
+  float4 gm[NV];                                            // gamma stays in registers here: see LnBwdRowSrc
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+    gm[i] = lane + 64 * i < nv4 ? reinterpret_cast<const float4*>(gamma)[lane + 64 * i] : make_float4(0, 0, 0, 0);
+  LnBwdRow<NV> ring[LN_AHEAD + 1];
+  // rows row0, row0 + stride, ...; the requests run LN_AHEAD rows ahead and are clamped to the last row past the end (a few rows read for nothing per wave)
+  // instead of being skipped: see ln_bwd_row_load
+  const int row0 = rb * 8 + wave;
+  auto clamped = [&](int row, int s) { return (int)min((long long)row + (long long)s * stride, (long long)T - 1); };
+  if (row0 < T) {
+#pragma unroll
+    for (int s = 0; s < LN_AHEAD; ++s) ln_bwd_row_load(ring[s], clamped(row0, s), dy, x, mean_in, rstd_in, add_to, lane, nv4, d);
+    for (int row = row0; row < T;) {
+#pragma unroll
+      for (int s = 0; s <= LN_AHEAD; ++s) {
+        ln_bwd_row_load(ring[(s + LN_AHEAD) % (LN_AHEAD + 1)], clamped(row, LN_AHEAD), dy, x, mean_in, rstd_in, add_to, lane, nv4, d);
+        ln_bwd_row<0, NV>(LnBwdRowSrc<NV>{ring[s], gm}, row, ring[s].mean, ring[s].rstd, 1.0f, gamma, add_to != nullptr, dx_out, dx_bf16, dg, db, lane, nv4, d, inv_d);
+        row += stride;
+        if (row >= T) goto rows_done;
+      }
+    }
+  }
+rows_done:
+  if (partial) {
+    float* pw = s_part + (size_t)wave * 2 * d;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nv4) {
+        reinterpret_cast<float4*>(pw)[c] = dg[i];
+        reinterpret_cast<float4*>(pw + d)[c] = db[i];
+      }
+    }
+    __syncthreads();
+    float* pg = partial + (size_t)rb * 2 * d;
+    for (int j = threadIdx.x; j < 2 * d; j += 512)
+      pg[j] = ((s_part[j] + s_part[2 * d + j]) + (s_part[4 * d + j] + s_part[6 * d + j])) +
+              ((s_part[8 * d + j] + s_part[10 * d + j]) + (s_part[12 * d + j] + s_part[14 * d + j]));
+  }
+}
+
 // configuration of the 8-phase form for an (N, K) weight gradient: 1 = 256 x 320 tiles, 2 = 320 x 256 tiles, 0 = not eligible
 static int tn8_config(int N, int K) {
   if (K % 320 == 0 && N % 256 == 0) return 1;
@@ -607,5 +693,69 @@ extern "C" int oneprot_gemm_bf16_tn(const void* dY, const void* X, int64_t M, in
   size_t blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;
   const int bb = dbias ? (N + 255) / 256 : 0;
   hipLaunchKernelGGL(k_tn_reduce, dim3((unsigned)blocks + bb), dim3(256), 0, s, (const float*)workspace, dW, n4, n4, S, accumulate, (const float*)bias_slab, dbias, N, bb);
+  return launch_status();
+}
+
+// token splits of the fused launch when `reserve` CUs go to its LayerNorm role: those of oneprot_gemm_bf16_tn under oneprot_cu_reserve(reserve).  Where that rule
+// hands the problem to the 128 x 128 kernels (so few tokens that splits of 256 would leave most of the chip idle) the same caps hold without that floor: the
+// splits then have the boundaries the 128 x 128 kernels would use.
+static int tn8_ln_splits(int64_t M, int tiles, int reserve) {
+  int n_cu = tn8_cus_all() - reserve;
+  if (n_cu < 64) n_cu = 64;
+  int S = tn8_splits(M, tiles, n_cu, 64);
+  if (S > 0) return S;
+  S = n_cu / tiles;
+  if (S > 64) S = 64;
+  if (S > M / 256) S = (int)(M / 256);
+  return S < 1 ? 1 : S;
+}
+
+// 1 when oneprot_gemm_tn_ln_bwd serves an (M, N, K) weight gradient with its LayerNorm backward on [M, K]
+extern "C" int oneprot_gemm_tn_ln_bwd_eligible(int64_t M, int N, int K) {
+  return M > 0 && M <= 0x7fffffff && N > 0 && K > 0 && !(N & 7) && tn8_config(N, K) == 1 && M % 32 == 0 && !(K & 3) && K <= 5 * 256;
+}
+
+extern "C" int oneprot_gemm_tn_ln_bwd(const void* dY, const void* X, int64_t M, int N, int K, int ldy, int ldx, float* dW, float* dbias, void* workspace,
+                                      size_t workspace_bytes, int accumulate, const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                      const float* add_to, float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* ln_partial, int accumulate_param_grads,
+                                      int ln_cus, void* stream) {
+  if (!dY || !X || !dW || !workspace || M <= 0 || N <= 0 || K <= 0 || M > 0x7fffffff) return OP_EINVAL;
+  if ((N & 7) || (ldy & 7) || (ldx & 7) || ldy < N || ldx < K) return OP_EINVAL;
+  if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW | (uintptr_t)workspace) & 15) return OP_EINVAL;
+  if (!dy || !x || !gamma || !mean || !rstd || !dx) return OP_EINVAL;
+  if ((dgamma || dbeta) && !(dgamma && dbeta && ln_partial)) return OP_EINVAL;
+  if (((uintptr_t)dy & 7) || (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx | (uintptr_t)add_to | (uintptr_t)ln_partial) & 15) || ((uintptr_t)dx_bf16 & 7)) return OP_EINVAL;
+  // the 8-phase form with 256 x 320 tiles, whole 32-token units, rows of float4s no wider than the row body's registers, a positive role size the decode can keep
+  if (!oneprot_gemm_tn_ln_bwd_eligible(M, N, K)) return OP_EINVAL;
+  if (ln_cus < 8 || (ln_cus & 7) || ln_cus > tn8_cus_all() - 64) return OP_EINVAL;
+  if ((size_t)32 * ldy * 2 >= (1u << 31) || (size_t)32 * ldx * 2 >= (1u << 31)) return OP_EINVAL;
+  const int tiles = tn8_tiles(1, N, K);
+  const int S = tn8_ln_splits(M, tiles, ln_cus);
+  const size_t per_split = (size_t)N * K * sizeof(float) + (dbias ? (size_t)N * sizeof(float) : 0);
+  if (workspace_bytes < (size_t)S * per_split) return OP_EINVAL;
+  constexpr int LDS8 = TN8_RING * 36 * 1024;
+  static bool c8 = false;
+  if (!c8) {
+    if (hipFuncSetAttribute((const void*)k_gemm_tn8_ln<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8) != hipSuccess) return OP_ELAUNCH;
+    if (hipFuncSetAttribute((const void*)k_gemm_tn8_ln<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8) != hipSuccess) return OP_ELAUNCH;
+    if (hipFuncSetAttribute((const void*)k_gemm_tn8_ln<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8) != hipSuccess) return OP_ELAUNCH;
+    if (hipFuncSetAttribute((const void*)k_gemm_tn8_ln<5>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8) != hipSuccess) return OP_ELAUNCH;
+    c8 = true;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* bias_slab = dbias ? (float*)workspace + (size_t)S * N * K : nullptr;
+  const int n_tn = 8 * ((tiles * S + 7) / 8);
+  float* partial = dgamma ? ln_partial : nullptr;
+  const int nv = (K / 4 + 63) / 64;
+#define LAUNCH_TNLN(NV) hipLaunchKernelGGL((k_gemm_tn8_ln<NV>), dim3(n_tn + ln_cus), dim3(512), LDS8, s, (const bf16_t*)dY, (const bf16_t*)X, (int)M, N, K, ldy, ldx, (float*)workspace, \
+                                           bias_slab, K / 320, tiles, S, n_tn, (const bf16_t*)dy, x, gamma, mean, rstd, add_to, dx, (bf16_t*)dx_bf16, partial)
+  if (nv <= 2) LAUNCH_TNLN(2); else if (nv == 3) LAUNCH_TNLN(3); else if (nv == 4) LAUNCH_TNLN(4); else LAUNCH_TNLN(5);
+#undef LAUNCH_TNLN
+  const size_t n4 = ((size_t)N * K) >> 2;
+  size_t blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;
+  const int bb = dbias ? (N + 255) / 256 : 0;
+  hipLaunchKernelGGL(k_tn_reduce, dim3((unsigned)blocks + bb), dim3(256), 0, s, (const float*)workspace, dW, n4, n4, S, accumulate, (const float*)bias_slab, dbias, N, bb);
+  if (dgamma)
+    hipLaunchKernelGGL(k_ln_reduce, dim3((2 * K + 15) / 16), dim3(1024), 0, s, (const float*)ln_partial, dgamma, dbeta, ln_cus, K, accumulate_param_grads);
   return launch_status();
 }

@@ -5,6 +5,7 @@
 // one wave64 owns one row, lane l owns float4 columns l, l+64, ... so every access is a 16-byte (fp32) or
 // 8-byte (bf16) coalesced vector access and all row statistics are wave reductions (no LDS, no barriers).
 #include "common.h"
+#include "ln_bwd_row.h"
 #include "../../include/oneprot_hip.h"
 
 #define MAXV 8                 // float4s per lane -> rows up to 2048 wide
@@ -326,72 +327,9 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const void* __restrict__ 
       while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (cu[mid] <= row) lo = mid; else hi = mid - 1; }
       dyrow = lo;
     }
-    float4 xh[NV], g[NV];
-#ifndef LN_BWD_LATE_ADD
-    // the residual-gradient rows are requested together with x and dy: one exposed round trip per row instead of two (they are only needed after
-    // the two wave reductions, but a load issued there starts a second latency that the 4-5 resident waves per SIMD do not cover)
-    float4 av[NV];
-    if (add_to) {
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv4) av[i] = reinterpret_cast<const float4*>(add_to + (size_t)row * d)[c];
-      }
-    }
-#endif
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nv4) {
-        float4 xv;
-        if (X_BF16) {
-          const u32x2 p = reinterpret_cast<const u32x2*>((const bf16_t*)x + (size_t)row * d)[c];
-          xv = make_float4(bflo(p.x), bfhi(p.x), bflo(p.y), bfhi(p.y));
-        } else {
-          xv = reinterpret_cast<const float4*>((const float*)x + (size_t)row * d)[c];
-        }
-        float4 dyv;
-        if (DY_MODE == 0) {
-          const u32x2 p = reinterpret_cast<const u32x2*>((const bf16_t*)dy + (size_t)row * d)[c];
-          dyv = make_float4(bflo(p.x), bfhi(p.x), bflo(p.y), bfhi(p.y));
-        } else if (DY_MODE == 1) {
-          dyv = reinterpret_cast<const float4*>((const float*)dy + (size_t)row * d)[c];
-        } else {
-          dyv = reinterpret_cast<const float4*>((const float*)dy + dyrow * d)[c];
-          dyv.x *= w; dyv.y *= w; dyv.z *= w; dyv.w *= w;
-        }
-        xh[i] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
-        const float4 gm = reinterpret_cast<const float4*>(gamma)[c];          // (re-read per row from L1: 12 registers fewer -> one more wave per SIMD)
-        g[i] = make_float4(dyv.x * gm.x, dyv.y * gm.y, dyv.z * gm.z, dyv.w * gm.w);
-        s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
-        s2 += (g[i].x * xh[i].x + g[i].y * xh[i].y) + (g[i].z * xh[i].z + g[i].w * xh[i].w);
-        dg[i].x += dyv.x * xh[i].x; dg[i].y += dyv.y * xh[i].y; dg[i].z += dyv.z * xh[i].z; dg[i].w += dyv.w * xh[i].w;
-        db[i].x += dyv.x; db[i].y += dyv.y; db[i].z += dyv.z; db[i].w += dyv.w;
-      }
-    }
-    const float m1 = wave_sum(s1) * inv_d, m2 = wave_sum(s2) * inv_d;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nv4) {
-        float4 o;
-        o.x = rstd * (g[i].x - m1 - xh[i].x * m2);
-        o.y = rstd * (g[i].y - m1 - xh[i].y * m2);
-        o.z = rstd * (g[i].z - m1 - xh[i].z * m2);
-        o.w = rstd * (g[i].w - m1 - xh[i].w * m2);
-        if (add_to) {
-#ifdef LN_BWD_LATE_ADD
-          const float4 a = reinterpret_cast<const float4*>(add_to + (size_t)row * d)[c];
-#else
-          const float4 a = av[i];
-#endif
-          o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-        }
-        reinterpret_cast<float4*>(dx_out + (size_t)row * d)[c] = o;
-        if (dx_bf16) { u32x2 pk; pk.x = pack2bf(o.x, o.y); pk.y = pack2bf(o.z, o.w); reinterpret_cast<u32x2*>(dx_bf16 + (size_t)row * d)[c] = pk; }
-      }
-    }
+    LnBwdDirect<DY_MODE, X_BF16, NV> src{dy, x, add_to, (size_t)row, dyrow, d};
+    src.begin(lane, nv4);
+    ln_bwd_row<DY_MODE, NV>(src, row, mean, rstd, w, gamma, add_to != nullptr, dx_out, dx_bf16, dg, db, lane, nv4, d, inv_d);
   }
   if (partial) {
     float* pw = s_part + (size_t)wave * 2 * d;
@@ -413,32 +351,7 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const void* __restrict__ 
 #define LN_BWD_BLOCKS 1024      // 4 blocks per CU: 259 us against 261-273 with 2048 (half the partial matrix for k_ln_reduce), 272 with 768, 324 with 512 (tools/ab/ln_time.py)
 extern "C" size_t oneprot_layernorm_bwd_workspace(int d) { return (size_t)LN_BWD_BLOCKS * 2 * d * sizeof(float); }
 
-// dgamma_dbeta: [2][d] laid out as dgamma then dbeta (the two may be non-adjacent: pass both pointers)
-// 16 columns per block, 64 part-slices per column (1024 threads: the 2048 x 2d partial matrix is 10 MB and the kernel is bound by loads in
-// flight, not bandwidth; fixed summation order => deterministic)
-__global__ void __launch_bounds__(1024) k_ln_reduce(const float* __restrict__ partial, float* __restrict__ dgamma, float* __restrict__ dbeta, int nparts, int d, int accumulate) {
-  __shared__ float s_sl[64][17];
-  const int c = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int j = blockIdx.x * 16 + c;
-  float s = 0.f;
-  if (j < 2 * d)
-    for (int p = sl; p < nparts; p += 64) s += partial[(size_t)p * 2 * d + j];
-  s_sl[sl][c] = s;
-  __syncthreads();
-  if (sl < 4) {                       // 4 x 16 partial sums, then 4 -> 1
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += s_sl[sl * 16 + q][c];
-    s_sl[sl][c] = t;
-  }
-  __syncthreads();
-  if (sl == 0 && j < 2 * d) {
-    const float t = (s_sl[0][c] + s_sl[1][c]) + (s_sl[2][c] + s_sl[3][c]);
-    float* out = j < d ? dgamma + j : dbeta + (j - d);
-    *out = accumulate ? *out + t : t;
-  }
-}
-
+// k_ln_reduce (ln_bwd_row.h) sums the partial matrix in fixed order into dgamma / dbeta
 extern "C" int oneprot_layernorm_bwd(const void* dy, int dy_mode, const float* wrow, int L, const void* x, int x_is_bf16, const float* gamma,
                                      const float* mean, const float* rstd, const float* add_to, float* dx, void* dx_bf16, float* dgamma, float* dbeta,
                                      void* workspace, int64_t T, int d, int accumulate_param_grads, void* stream) {

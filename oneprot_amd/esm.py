@@ -484,6 +484,10 @@ class EsmTransformer(LoraArena):
         if self._padded:      # weight gradients come out in the padded-head layout and are gathered back into the arena gradient
             rowmap, colmap = self._head_pad_maps()
             gw_qkv, gb_qkv, gw_o = torch.empty(3 * dp, d, device=dev), torch.empty(3 * dp, device=dev), torch.empty(d, dp, device=dev)
+        # FFN-1 and QKV weight gradients each in one launch with the LayerNorm backward that follows their data gradient (disjoint CUs: oneprot_gemm_tn_ln_bwd).
+        # Single rank only: the CUs of the LayerNorm role on top of an all-reduce's reserve have not been measured.
+        wg_ln = (hip.wgrad_ln_wanted() and not self._lora and not self._padded and hip.cu_reserve_wanted() == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1
+                 and hip.query("oneprot_gemm_tn_ln_bwd_eligible", T, f, d) == 1 and hip.query("oneprot_gemm_tn_ln_bwd_eligible", T, 3 * dp, d) == 1)
         bounds = saved.get("bounds")
         seg_of_top = {hi - 1: (lo, hi) for lo, hi in saved["plan"][:-1]} if bounds is not None else {}
         for i in reversed(range(self.n_layers)):
@@ -495,11 +499,17 @@ class EsmTransformer(LoraArena):
             self._wgrad(g16, st["u"], T, d, f, gv(p + "output.dense.weight"), gv(p + "output.dense.bias"), ws_tn)
             hip.gemm_nt(g16, self._bf16_T[(i, "w2")], T, f, d, hip.EPI_GELU_BWD, dz, aux=st["z"])
             # ---- FFN1: z = h2 W1^T + b1
-            self._wgrad(dz, st["h2"], T, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
-            hip.gemm_nt(dz, self._bf16_T[(i, "w1")], T, d, f, hip.EPI_BF16, dh)
             # ---- LN2 (input x_mid): g += LN'(dh); also refreshes the bf16 copy g16
-            hip.layernorm_bwd(dh, 0, st["x_mid"], self.view(p + "LayerNorm.weight"), st["mean2"], st["rstd2"], g, gv(p + "LayerNorm.weight"), gv(p + "LayerNorm.bias"),
-                              ws_ln, T, d, add_to=g, dx16=g16)
+            if wg_ln:      # data gradient first, then the weight gradient beside the LayerNorm backward
+                hip.gemm_nt(dz, self._bf16_T[(i, "w1")], T, d, f, hip.EPI_BF16, dh)
+                hip.gemm_tn_ln_bwd(dz, st["h2"], T, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn, dh, st["x_mid"],
+                                   self.view(p + "LayerNorm.weight"), st["mean2"], st["rstd2"], g, gv(p + "LayerNorm.weight"), gv(p + "LayerNorm.bias"), ws_ln,
+                                   hip.wgrad_ln_cus(f), add_to=g, dx16=g16)
+            else:
+                self._wgrad(dz, st["h2"], T, f, d, gv(p + "intermediate.dense.weight"), gv(p + "intermediate.dense.bias"), ws_tn)
+                hip.gemm_nt(dz, self._bf16_T[(i, "w1")], T, d, f, hip.EPI_BF16, dh)
+                hip.layernorm_bwd(dh, 0, st["x_mid"], self.view(p + "LayerNorm.weight"), st["mean2"], st["rstd2"], g, gv(p + "LayerNorm.weight"), gv(p + "LayerNorm.bias"),
+                                  ws_ln, T, d, add_to=g, dx16=g16)
             # ---- out-proj: x_mid = x_in + ctx Wo^T + bo
             hip.gemm_tn(g16, st["ctx"], T, d, dp, gw_o if self._padded else gv(p + "attention.output.dense.weight"), gv(p + "attention.output.dense.bias"), ws_tn)
             hip.gemm_nt(g16, self._bf16_T[(i, "o")], T, dp, d, hip.EPI_BF16, dctx)
@@ -507,7 +517,8 @@ class EsmTransformer(LoraArena):
             lay.attn_bwd(st, dctx, q_scale, dqkv, ws_at, H, hd)
             # ---- QKV projection
             (o, n), (ob, nb) = self._qkv_spans(i)
-            hip.gemm_tn(dqkv, st["h1"], T, 3 * dp, d, gw_qkv if self._padded else gflat[o:o + n], gb_qkv if self._padded else gflat[ob:ob + nb], ws_tn)
+            if not wg_ln:
+                hip.gemm_tn(dqkv, st["h1"], T, 3 * dp, d, gw_qkv if self._padded else gflat[o:o + n], gb_qkv if self._padded else gflat[ob:ob + nb], ws_tn)
             if self._padded:
                 gv(p + "attention.output.dense.weight").copy_(gw_o[:, colmap])
                 gflat[o:o + n].view(3 * d, d).copy_(gw_qkv[rowmap])
@@ -516,8 +527,13 @@ class EsmTransformer(LoraArena):
             if lora_raw is not None:      # two-branch LoRA: adapter gradients, and dh += mask * (du A) / keep
                 self._lora_branch_backward(i, st["h1"], st["lora_u"], dqkv, T, saved["lora_call"], ws_tn, lora_raw, dh16=dh)
             # ---- LN1 (input x_in)
-            hip.layernorm_bwd(dh, 0, st["x_in"], self.view(p + "attention.LayerNorm.weight"), st["mean1"], st["rstd1"], g, gv(p + "attention.LayerNorm.weight"),
-                              gv(p + "attention.LayerNorm.bias"), ws_ln, T, d, add_to=g, dx16=g16)
+            if wg_ln:
+                hip.gemm_tn_ln_bwd(dqkv, st["h1"], T, 3 * dp, d, gflat[o:o + n], gflat[ob:ob + nb], ws_tn, dh, st["x_in"], self.view(p + "attention.LayerNorm.weight"),
+                                   st["mean1"], st["rstd1"], g, gv(p + "attention.LayerNorm.weight"), gv(p + "attention.LayerNorm.bias"), ws_ln,
+                                   hip.wgrad_ln_cus(3 * dp), add_to=g, dx16=g16)
+            else:
+                hip.layernorm_bwd(dh, 0, st["x_in"], self.view(p + "attention.LayerNorm.weight"), st["mean1"], st["rstd1"], g, gv(p + "attention.LayerNorm.weight"),
+                                  gv(p + "attention.LayerNorm.bias"), ws_ln, T, d, add_to=g, dx16=g16)
             saved["layers"][i] = st = None      # release this layer's activations
             if bounds is not None:
                 bounds.pop(i, None)      # ... and, under its bottom layer, the segment's boundary record

@@ -5,8 +5,8 @@ raises.  torch is used only as the owner of device memory and streams (tensor.da
 
 The header is the single source of the ABI: the ctypes signatures (_SIGS) and the expected element type of every pointer argument (_PTR_DTYPES) are
 parsed from it at import, so a new entry point is declared there, defined in csrc/, and needs nothing here unless one of its void* is not bf16
-(_BYTE_PTRS / _FLAG_TYPED_PTRS).  call(name, *positional) launches any entry point; gemm_nt / gemm_tn / layernorm_fwd / layernorm_bwd are keyword
-launchers of the four widest ones and end in the same call().  sort_f32 / sort_i32 / midranks_f32 / inclusive_scan / moments / f1max are the launchers of the
+(_BYTE_PTRS / _FLAG_TYPED_PTRS).  call(name, *positional) launches any entry point; gemm_nt / gemm_tn / layernorm_fwd / layernorm_bwd / gemm_tn_ln_bwd are keyword
+launchers of the widest ones and end in the same call().  sort_f32 / sort_i32 / midranks_f32 / inclusive_scan / moments / f1max are the launchers of the
 downstream-metric entry points (csrc/metrics.hip): they size and allocate the workspace, and hand back device tensors (fp64 results as views of byte buffers).
 probe_linear_fwd / probe_rownorm_act_fwd / probe_norm_act_bwd / probe_rownorm_act_bwd / probe_loss are the keyword launchers of the MLP probe's wide entry points
 (csrc/probe.hip).  The gradient-boosted tree entry points (csrc/gbt.hip, oneprot_gbt_*) are called by name from oneprot_amd/gbt.py and oneprot_amd/gbt_deep.py, the text-input entry
@@ -224,6 +224,30 @@ def layernorm_fwd(x, gamma, beta, T, d, eps, *, y16=None, y32=None, mean=None, r
 def layernorm_bwd(dy, dy_mode, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, T, d, *, wrow=None, L=0, x_is_bf16=0, add_to=None, dx16=None, accumulate=0):
     """dy_mode 0: dy bf16 [T,d]; 1: fp32 [T,d]; 2: dy[t] = dy[t // L] * wrow[t].  dx = (add_to or 0) + LN'(dy), dx16 its optional bf16 copy."""
     call("oneprot_layernorm_bwd", dy, dy_mode, wrow, L, x, x_is_bf16, gamma, mean, rstd, add_to, dx, dx16, dgamma, dbeta, ws, T, d, accumulate)
+
+
+def gemm_tn_ln_bwd(dY, X, M, N, K, dW, dbias, ws, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws_ln, ln_cus, *, add_to=None, dx16=None):
+    """gemm_tn(dY, X) and layernorm_bwd(dy bf16, x fp32) on the same M rows of width K in one launch, `ln_cus` CUs given to the LayerNorm rows; ws_ln: the
+    bytes of oneprot_layernorm_bwd_workspace(K)"""
+    call("oneprot_gemm_tn_ln_bwd", dY, X, M, N, K, N, K, dW, dbias, ws, ws.numel(), 0, dy, x, gamma, mean, rstd, add_to, dx, dx16, dgamma, dbeta, ws_ln.view(torch.float32), 0,
+         ln_cus)
+
+
+# CUs of the LayerNorm role of oneprot_gemm_tn_ln_bwd by the weight gradient's N at K = 640: the fastest fused launch of tools/ab/wgrad_ln_ab.py
+# (profiles/wgrad_ln_ab.txt: FFN-1 554 us at 64 against 656 for the two launches, QKV 470 us at 80 against 562); other shapes: 64
+WGRAD_LN_CUS = {2560: 64, 1920: 80}
+
+
+def wgrad_ln_wanted():
+    """ONEPROT_WGRAD_LN=1 / 0: the FFN-1 and QKV weight gradients of a trainable ESM layer in one launch with the LayerNorm backward that follows their data
+    gradient (single rank, no CU reserve).  Default: on (4.9 ms of the cfg-2 step); 0 keeps the separate launches (A/B runs, tests)."""
+    return os.environ.get("ONEPROT_WGRAD_LN", "1") != "0"
+
+
+def wgrad_ln_cus(N):
+    """ONEPROT_WGRAD_LN_CUS=<n> (A/B runs), else the measured choice for this weight gradient"""
+    v = os.environ.get("ONEPROT_WGRAD_LN_CUS")
+    return int(v) if v else WGRAD_LN_CUS.get(N, 64)
 
 
 def _workspace(query_name, like, *shape):

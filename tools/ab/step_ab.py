@@ -47,6 +47,8 @@ CONFIGS = {
     "out-projection + LN: four-wave form": (lambda: Q("oneprot_gemm_ln_form", 1), lambda: Q("oneprot_gemm_ln_form", 0)),
     "ONEPROT_FUSED_LN=0 (out-projection, then LayerNorm)": (env("ONEPROT_FUSED_LN", "0"), env("ONEPROT_FUSED_LN", None)),
     "ONEPROT_FFN2_LN=0 (FFN-2, then LayerNorm)": (env("ONEPROT_FFN2_LN", "0"), env("ONEPROT_FFN2_LN", None)),
+    "ONEPROT_WGRAD_LN=1 (FFN-1 / QKV weight gradient beside the LayerNorm backward)": (env("ONEPROT_WGRAD_LN", "1"), env("ONEPROT_WGRAD_LN", None)),
+    "ONEPROT_WGRAD_LN=0 (weight gradient, then LayerNorm backward)": (env("ONEPROT_WGRAD_LN", "0"), env("ONEPROT_WGRAD_LN", None)),
     "tiles from the work queues": (dyn(True), dyn(False)),
     "weight-gradient GEMM with a 16-CU reserve": (lambda: Q("oneprot_cu_reserve", 16), lambda: Q("oneprot_cu_reserve", 0)),
     "work queues + 16-CU reserve (the multi-rank defaults)": (lambda: (dyn(True)(), Q("oneprot_cu_reserve", 16)), lambda: (dyn(False)(), Q("oneprot_cu_reserve", 0))),
