@@ -362,6 +362,11 @@ int oneprot_sim_pair_dot(const float* S, const float* M, float* diag, int N, int
    rank_row[i] += #{ j : S_i . M_j > diag[i] } (complete for the slab's rows); rank_col[j] += #{ i in slab : S_i . M_j > diag[j] } (partial: summed over
    the slabs of a whole pass it is complete).  Strict >, int32 counts added with integer atomics (deterministic); the caller zeroes both before the first slab. */
 int oneprot_sim_rank(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, void* stream);
+/* oneprot_sim_rank with tie counts from the same tile values: rank_row / rank_col receive exactly what oneprot_sim_rank adds, and
+   tie_row[i] += #{ j != i : S_i . M_j == diag[i] }, tie_col[j] += #{ i != j, i in slab : S_i . M_j == diag[j] } (the matching pair is left out by its index,
+   not by its value; rows and columns past N count nothing).  rank + tie is the pessimistic rank.  The caller zeroes all four before the first slab. */
+int oneprot_sim_rank_ties(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, int* tie_row, int* tie_col,
+                          void* stream);
 /* The k largest Q_i . Db_j over the N database rows for each of the nq queries (ref eval.py:158-184 ranks every row the same way): scores fp32 [nq, k]
    descending, indices int64 [nq, k]; equal scores in ascending database index.  1 <= k <= min(N, 256); finite inputs.  workspace: at least
    oneprot_sim_topk_workspace(nq, N, k) bytes (0 for invalid arguments), 8-byte aligned: [splits, nq, k] partial lists, never O(nq * N). */

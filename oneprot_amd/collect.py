@@ -9,7 +9,7 @@ which is what downstream.load_data reads (with output_dir = <emb_dir>/<model_typ
                          tokens with <eos> kept.  graph_data.tokenize_sequences (one byte, one id) is NOT this rule and stays as it is.
   read_task_csv          the reference's four label types from a CSV, by header, on Python's csv module.
   plan_batches           the UNIQUE sequences of a split in canonical order (token count, then bytes), filled greedily into token budgets.
-  embed_sequences        every batch of the plan as one PackedTokens stream through the towers' existing kernels; the next batch's ids are staged from pinned
+  embed_sequences        (run_plan) every batch of the plan as one PackedTokens stream through the towers' existing kernels; the next batch's ids are staged from pinned
                          memory on a copy stream while the current one runs; nothing is read back per batch.  This module indexes, gathers and concatenates rows
                          and computes nothing on them.
   collect_task / main    the reference's two steps (shards, then the combined file) and its config keys; `--run` does both in one go.
@@ -319,6 +319,21 @@ def embed_sequences(encoder, sequences, kind, max_length=MAX_LENGTH, max_tokens=
         raise hip.HipKernelError("OneProt HIP path needs CUDA(ROCm) tensors; there is no CPU fallback (move the encoder to the device)")
     hip.lib()                                                   # HipLibraryMissing before any device work
     plan = plan_sequences(sequences, max_length, max_tokens, max_seqs, tokenizer)
+    tr = getattr(encoder, "transformer", encoder)
+    if kind == "oneprot":
+        forward = encoder
+    else:
+        def forward(p):
+            x, _ = tr.run_layers(p, save=False)
+            return layout.of(tr, p).pool_fwd(tr, x, _MeanMode, False)[0]
+    return run_plan(encoder, forward, plan, dev, timings)
+
+
+def run_plan(encoder, forward, plan, dev, timings=None):
+    """fp32 [N, D] on `dev`: every batch of `plan` (plan_sequences' dict: uniq, inverse, flat / off, batches, pad_id) as one PackedTokens stream through
+    forward(p) -> [len(batch), D], written into a resident [U, D] buffer and gathered to the rows of plan["inverse"].  The next batch's ids are staged from
+    pinned memory on a copy stream while the current one runs; nothing is read back.  `encoder` is put in eval mode, under no_grad, and its modules'
+    training flags are put back afterwards.  embed_sequences and evaluate.embed_modalities (any tokenizer, any pad id) both end here."""
     uniq, inverse, flat, off, batches, pad_id = (plan[k] for k in ("uniq", "inverse", "flat", "off", "batches", "pad_id"))
     lengths = np.diff(off)
     order = np.fromiter((i for b in batches for i in b), dtype=np.int64, count=len(uniq))
@@ -331,14 +346,13 @@ def embed_sequences(encoder, sequences, kind, max_length=MAX_LENGTH, max_tokens=
     np.cumsum([len(b) for b in batches], out=bounds[1:])
     rank = np.empty(len(uniq), dtype=np.int64)
     rank[order] = np.arange(len(uniq))
-    tr = getattr(encoder, "transformer", encoder)
     flags = [(m, m.training) for m in encoder.modules()]
     main, copy_stream = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
     out = None
     encoder.eval()
     try:
         with torch.no_grad(), torch.cuda.device(dev):
-            rows = torch.empty(len(sequences), dtype=torch.int64, pin_memory=True)
+            rows = torch.empty(len(inverse), dtype=torch.int64, pin_memory=True)
             rows.copy_(torch.from_numpy(rank[inverse]))
             rows = rows.to(dev, non_blocking=True)
             staged = _stage(c_flat, c_off, int(bounds[0]), int(bounds[1]), dev, copy_stream, pad_id)
@@ -350,11 +364,7 @@ def embed_sequences(encoder, sequences, kind, max_length=MAX_LENGTH, max_tokens=
                 if timings is not None:
                     timings.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                     timings[-1][0].record(main)
-                if kind == "oneprot":
-                    feats = encoder(p)
-                else:
-                    x, _ = tr.run_layers(p, save=False)
-                    feats = layout.of(tr, p).pool_fwd(tr, x, _MeanMode, False)[0]
+                feats = forward(p)
                 if out is None:
                     out = torch.empty(len(uniq), feats.shape[1], dtype=torch.float32, device=dev)
                 out[int(bounds[b]):int(bounds[b + 1])] = feats
@@ -387,17 +397,21 @@ def load_model(cfg, model_cfg, device="cuda"):
     if name == "esm2":
         from .esm import EsmTransformer
         return EsmTransformer.from_pretrained(cfg["esm_model"], add_pooling_layer=False).to(device).eval(), "esm2"
+    return load_module(model_cfg.get("config_path"), model_cfg.get("ckpt_path"), plain_state_dict=bool(cfg.get("huggingface"))).network["sequence"].to(device).eval(), "oneprot"
+
+
+def load_module(config_path, ckpt_path=None, plain_state_dict=False):
+    """the whole module of a run: `config_path` composed, its `model` instantiated, `ckpt_path` (None: no weights are loaded) loaded strictly -- the
+    ["state_dict"] of a Lightning checkpoint, or the file itself when plain_state_dict.  On the host; load_model here and evaluate.load_custom_model move it."""
     from . import config as config_mod
-    path = model_cfg.get("config_path")
-    if not path or not os.path.exists(path):
-        raise FileNotFoundError(f"Model config file not found: {path}")
-    composed = config_mod.compose(os.path.dirname(os.path.abspath(path)), os.path.basename(path))
+    if not config_path or not os.path.exists(config_path):
+        raise FileNotFoundError(f"Model config file not found: {config_path}")
+    composed = config_mod.compose(os.path.dirname(os.path.abspath(config_path)), os.path.basename(config_path))
     model = config_mod.instantiate(composed["model"])
-    ckpt = model_cfg.get("ckpt_path")
-    if ckpt is not None:
-        sd = torch.load(ckpt, map_location="cpu", weights_only=True)
-        model.load_state_dict(sd if cfg.get("huggingface") else sd["state_dict"], strict=True)
-    return model.network["sequence"].to(device).eval(), "oneprot"
+    if ckpt_path is not None:
+        sd = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+        model.load_state_dict(sd if plain_state_dict else sd["state_dict"], strict=True)
+    return model
 
 
 def _dirs(cfg, model_cfg, task, csv_file):

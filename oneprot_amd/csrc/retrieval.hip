@@ -1,5 +1,5 @@
 // Retrieval at database scale (ref retrieval_metric.py:83-102, eval.py:158-184): the similarity tile S . M^T is formed on the matrix pipe and consumed
-// in registers -- compared against the diagonal and counted (oneprot_sim_rank), or offered to a running k-best list (oneprot_sim_topk) -- so the N x N
+// in registers -- compared against the diagonal and counted (oneprot_sim_rank; oneprot_sim_rank_ties also counts equality), or offered to a running k-best list (oneprot_sim_topk) -- so the N x N
 // matrix is never written.  The contraction is the fp32-input MFMA v_mfma_f32_32x32x2_f32: fp32 operands, and per output element the k-ordered fmaf chain
 // acc = fmaf(a_k, b_k, acc) from k = 0 upwards, which is the chain k_sgemm (sgemm.hip) computes with alpha = 1.  Ranks therefore equal those of
 // oneprot_sgemm + oneprot_diag_rank bit for bit (tests/test_retrieval_gpu.py demands torch.equal), and so do top-k scores.
@@ -113,13 +113,17 @@ __global__ void __launch_bounds__(256) k_sim_pair_dot(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------- ranks
 // One 128 x 128 tile per block.  Blocks are numbered so that 16 row tiles x all column tiles form a group with the row tile running fastest: the blocks
 // in flight together share a few megabytes of S and M rows.
-template <bool VEC>
+// TIES (oneprot_sim_rank_ties): next to every `v > diag` count the same tile value is compared `v == diag` and counted the same way into tie_row / tie_col,
+// the matching pair (global row == global column) left out by its index.  Without TIES the added lines do not exist: the kernel is oneprot_sim_rank's as before.
+template <bool VEC, bool TIES>
 __global__ void __launch_bounds__(256) k_sim_rank(const float* __restrict__ S, const float* __restrict__ M, const float* __restrict__ diag, int N, int D, int row0, int rows,
-                                                  int nrt, int nct, int* __restrict__ rank_row, int* __restrict__ rank_col) {
+                                                  int nrt, int nct, int* __restrict__ rank_row, int* __restrict__ rank_col, int* __restrict__ tie_row,
+                                                  int* __restrict__ tie_col) {
   __shared__ __attribute__((aligned(16))) float sA[128 * SIM_LD];
   __shared__ __attribute__((aligned(16))) float sB[SIM_TN * SIM_LD];
   __shared__ float sDr[128];
   __shared__ int sCr[128], sCc[128];
+  __shared__ int sTr[TIES ? 128 : 1], sTc[TIES ? 128 : 1];
   constexpr int GR = 16;
   const int per_group = GR * nct, group = blockIdx.x / per_group, rem = blockIdx.x % per_group;
   const int gr_rows = min(GR, nrt - group * GR);
@@ -128,9 +132,11 @@ __global__ void __launch_bounds__(256) k_sim_rank(const float* __restrict__ S, c
   const int rend = row0 + rows, r0 = row0 + rt * 128, c0 = ct_ * SIM_TN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave & 1, wc = wave >> 1, h = lane >> 5;
   if (tid < 128) { sDr[tid] = r0 + tid < rend ? diag[r0 + tid] : 0.f; sCr[tid] = 0; sCc[tid] = 0; }
+  if (TIES && tid < 128) { sTr[tid] = 0; sTc[tid] = 0; }
   f32x16 acc[2][2];
-  sim_tile<2, VEC>(S, r0, rend, M, c0, N, D, sA, sB, acc);      // its barriers also publish sDr / sCr / sCc
+  sim_tile<2, VEC>(S, r0, rend, M, c0, N, D, sA, sB, acc);      // its barriers also publish sDr / sCr / sCc (and sTr / sTc)
   int ccol[2] = {0, 0};
+  int tcol[2] = {0, 0};
   float dcol[2];
   bool vcol[2];
 #pragma unroll
@@ -139,6 +145,7 @@ __global__ void __launch_bounds__(256) k_sim_rank(const float* __restrict__ S, c
     vcol[ct] = j < N;
     dcol[ct] = vcol[ct] ? diag[j] : 0.f;
   }
+  const int jrel = c0 + wc * 64 + (lane & 31) - r0;      // TIES: column j of ct is the matching pair of tile row `row` when row == jrel + 32 ct
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -157,16 +164,37 @@ __global__ void __launch_bounds__(256) k_sim_rank(const float* __restrict__ S, c
       }
       if (lane == 0 && lo) atomicAdd(&sCr[wr * 64 + mt * 32 + sim_reg_row(reg, 0)], lo);
       if (lane == 32 && hi) atomicAdd(&sCr[wr * 64 + mt * 32 + sim_reg_row(reg, 1)], hi);
+      if constexpr (TIES) {
+        int tlo = 0, thi = 0;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          const float v = acc[mt][ct][reg];
+          const bool other = vrow && vcol[ct] && row != jrel + 32 * ct;      // in range on both sides (the zero padding past N / the slab is no tie of a zero diagonal) and not the pair itself
+          const unsigned long long m = __ballot(other && v == drow);
+          tlo += __popc((unsigned)m);
+          thi += __popc((unsigned)(m >> 32));
+          tcol[ct] += (other && v == dcol[ct]) ? 1 : 0;
+        }
+        if (lane == 0 && tlo) atomicAdd(&sTr[wr * 64 + mt * 32 + sim_reg_row(reg, 0)], tlo);
+        if (lane == 32 && thi) atomicAdd(&sTr[wr * 64 + mt * 32 + sim_reg_row(reg, 1)], thi);
+      }
     }
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)
     if (ccol[ct]) atomicAdd(&sCc[wc * 64 + ct * 32 + (lane & 31)], ccol[ct]);
+  if constexpr (TIES) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+      if (tcol[ct]) atomicAdd(&sTc[wc * 64 + ct * 32 + (lane & 31)], tcol[ct]);
+  }
   __syncthreads();
   if (tid < 128) {
     if (sCr[tid] && r0 + tid < rend) atomicAdd(&rank_row[r0 + tid], sCr[tid]);
+    if constexpr (TIES) { if (sTr[tid] && r0 + tid < rend) atomicAdd(&tie_row[r0 + tid], sTr[tid]); }
   } else {
     const int c = tid - 128;
     if (sCc[c] && c0 + c < N) atomicAdd(&rank_col[c0 + c], sCc[c]);
+    if constexpr (TIES) { if (sTc[c] && c0 + c < N) atomicAdd(&tie_col[c0 + c], sTc[c]); }
   }
 }
 
@@ -289,14 +317,29 @@ extern "C" int oneprot_sim_pair_dot(const float* S, const float* M, float* diag,
   return launch_status();
 }
 
-extern "C" int oneprot_sim_rank(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, void* stream) {
+static int sim_rank_launch(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, int* tie_row, int* tie_col,
+                           void* stream) {
   if (!S || !M || !diag || !rank_row || !rank_col || N <= 0 || D <= 0 || row0 < 0 || rows <= 0 || row0 > N - rows) return OP_EINVAL;
   const int nrt = (rows + 127) / 128, nct = (N + SIM_TN - 1) / SIM_TN, groups = (nrt + 15) / 16;
   const int64_t blocks = (int64_t)groups * 16 * nct;        // (the last group's spare numbers return at once)
   if (blocks > 0x7fffffff) return OP_EINVAL;                // a slab this large: the caller passes fewer rows per call
-  if (sim_vec_ok(S, M, D)) hipLaunchKernelGGL(k_sim_rank<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, S, M, diag, N, D, row0, rows, nrt, nct, rank_row, rank_col);
-  else hipLaunchKernelGGL(k_sim_rank<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, S, M, diag, N, D, row0, rows, nrt, nct, rank_row, rank_col);
+  const dim3 grid((unsigned)blocks), block(256);
+  const bool vec = sim_vec_ok(S, M, D);
+#define SIM_RANK_GO(V, T) hipLaunchKernelGGL((k_sim_rank<V, T>), grid, block, 0, (hipStream_t)stream, S, M, diag, N, D, row0, rows, nrt, nct, rank_row, rank_col, tie_row, tie_col)
+  if (tie_row) { if (vec) SIM_RANK_GO(true, true); else SIM_RANK_GO(false, true); }
+  else { if (vec) SIM_RANK_GO(true, false); else SIM_RANK_GO(false, false); }
+#undef SIM_RANK_GO
   return launch_status();
+}
+
+extern "C" int oneprot_sim_rank(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, void* stream) {
+  return sim_rank_launch(S, M, diag, N, D, row0, rows, rank_row, rank_col, nullptr, nullptr, stream);
+}
+
+extern "C" int oneprot_sim_rank_ties(const float* S, const float* M, const float* diag, int N, int D, int row0, int rows, int* rank_row, int* rank_col, int* tie_row,
+                                     int* tie_col, void* stream) {
+  if (!tie_row || !tie_col) return OP_EINVAL;
+  return sim_rank_launch(S, M, diag, N, D, row0, rows, rank_row, rank_col, tie_row, tie_col, stream);
 }
 
 // query tiles x database splits: enough blocks to fill the chip twice over when there are few queries, at most 64 lists to merge per query

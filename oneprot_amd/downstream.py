@@ -227,3 +227,37 @@ def load_data(cfg):
         out[f"{partition}_emb"] = emb.cpu().numpy()
         out[f"{partition}_target"] = target.cpu().numpy()
     return out
+
+
+def save_results_to_csv(results, cfg):
+    """ref src/utils/downstream.py:62-118 on Python's csv module: one row appended to <results_dir>/downstream_results/<task>_<downstream model>_results.csv
+    (the header only when the file is new).  Columns: model_type, every `test_*` result, then the other results, downstream_model, task_name, threshold and
+    one `param_<key>` per key of cfg.downstream_model but `_target_`; every cell padded to 20 characters, numbers as %.3f.  Returns the file's path."""
+    import csv
+    dm = cfg["downstream_model"]
+    row = dict(results)
+    row.update(model_type=cfg["model_type"], downstream_model=dm["name"], task_name=cfg["task_name"], threshold=cfg["threshold"])
+    for param, value in dm.items():
+        if param != "_target_":
+            row[f"param_{param}"] = value
+    first = ["model_type"] + [c for c in row if c.startswith("test_")]
+    columns = first + [c for c in row if c not in first]
+    width = 20
+
+    def cell(value):
+        return (f"{value:.3f}" if isinstance(value, (int, float, np.number)) else str(value)).ljust(width)
+
+    out_dir = os.path.join(str(cfg["results_dir"]), "downstream_results")
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, f"{cfg['task_name']}_{dm['name']}_results.csv")
+    new = not os.path.exists(path)
+    with open(path, "w" if new else "a", newline="") as f:
+        writer = csv.writer(f)
+        if new:
+            writer.writerow([c.ljust(width) for c in columns])
+        writer.writerow([cell(row[c]) for c in columns])
+    print(f"Results appended to {path}")
+    print("\nResults:")
+    for c in columns:
+        print(f"{c.ljust(30)}: {cell(row[c])}")
+    return path

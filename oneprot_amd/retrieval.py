@@ -6,7 +6,8 @@ fmaf chain that `oneprot_sgemm` computes, so `pair_ranks` returns the ranks of `
 
 Tie rules, both paths:
   * ranks count strict `>`: rank[i] is the number of candidates whose similarity is strictly greater than the matching pair's.  A candidate that ties with
-    the matching pair does not push it down -- the optimistic rank, as `oneprot_diag_rank` counts it.
+    the matching pair does not push it down -- the optimistic rank, as `oneprot_diag_rank` counts it.  `pair_ranks(..., ties=True)` returns, next to it, how
+    many other candidates tie with the matching pair exactly (same tile values, `==`); rank + ties is the pessimistic rank (`bound="pessimistic"`).
   * top-k orders by descending score and breaks ties by ascending database index, so the result is fully defined.
 
 Inputs are fp32 device tensors [rows, D]; CPU tensors raise HipKernelError (there is no fallback).  Scores are expected to be finite."""
@@ -32,9 +33,10 @@ def default_slab_rows(N, D):
     return max(128, min(N, rows // 128 * 128))
 
 
-def pair_ranks(s, m, slab_rows=None):
+def pair_ranks(s, m, slab_rows=None, ties=False):
     """(rank_row, rank_col), int32 [N] on the device: rank_row[i] = #{j : s_i . m_j > s_i . m_i} (s -> m retrieval), rank_col[j] = #{i : s_i . m_j > s_j . m_j}
-    (m -> s).  `slab_rows` rows of s per launch (default: sized by work); the result does not depend on it."""
+    (m -> s).  `slab_rows` rows of s per launch (default: sized by work); the result does not depend on it.  ties=True: (rank_row, rank_col, tie_row, tie_col),
+    tie_row[i] = #{j != i : s_i . m_j == s_i . m_i} and tie_col likewise, counted by oneprot_sim_rank_ties on the very tile values the ranks are counted on."""
     s, m = _features(s, "pair_ranks: s"), _features(m, "pair_ranks: m")
     if s.shape != m.shape:
         raise ValueError(f"pair_ranks: s {tuple(s.shape)} and m {tuple(m.shape)} must have the same shape")
@@ -46,9 +48,14 @@ def pair_ranks(s, m, slab_rows=None):
     hip.call("oneprot_sim_pair_dot", s, m, diag, N, D)
     rr = torch.zeros(N, dtype=torch.int32, device=s.device)
     rc = torch.zeros(N, dtype=torch.int32, device=s.device)
+    if not ties:
+        for row0 in range(0, N, step):
+            hip.call("oneprot_sim_rank", s, m, diag, N, D, row0, min(step, N - row0), rr, rc)
+        return rr, rc
+    tr, tc = torch.zeros_like(rr), torch.zeros_like(rc)
     for row0 in range(0, N, step):
-        hip.call("oneprot_sim_rank", s, m, diag, N, D, row0, min(step, N - row0), rr, rc)
-    return rr, rc
+        hip.call("oneprot_sim_rank_ties", s, m, diag, N, D, row0, min(step, N - row0), rr, rc, tr, tc)
+    return rr, rc, tr, tc
 
 
 def topk(queries, database, k):
@@ -68,20 +75,38 @@ def topk(queries, database, k):
     return scores, indices
 
 
-def metrics_from_ranks(rank_row, rank_col, ks):
-    """the dict of ref retrieval_metric.py:95-102 from the two rank vectors: floor(median) + 1 and R@k = mean(rank < k), both directions"""
+BOUNDS = ("optimistic", "pessimistic")
+
+
+def _host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def metrics_from_ranks(rank_row, rank_col, ks, ties=None, bound="optimistic"):
+    """the dict of ref retrieval_metric.py:95-102 from the two rank vectors: floor(median) + 1 and R@k = mean(rank < k), both directions.  bound
+    "pessimistic" takes rank + ties (ties = (tie_row, tie_col) of pair_ranks(..., ties=True)): every candidate that ties with the matching pair is ahead of it."""
+    if bound not in BOUNDS:
+        raise ValueError(f"metrics_from_ranks: bound {bound!r}; one of {', '.join(BOUNDS)}")
+    if bound == "pessimistic" and ties is None:
+        raise ValueError("metrics_from_ranks: the pessimistic bound needs ties = (tie_row, tie_col)")
     out = {}
-    for name, ranks in (("seq_to_mod", rank_row), ("mod_to_seq", rank_col)):
-        r = ranks.cpu().numpy() if isinstance(ranks, torch.Tensor) else np.asarray(ranks)
+    for d, (name, ranks) in enumerate((("seq_to_mod", rank_row), ("mod_to_seq", rank_col))):
+        r = _host(ranks)
+        if bound == "pessimistic":
+            r = r.astype(np.int64) + _host(ties[d])
         out[f"{name}_median_rank"] = float(np.floor(np.median(r)) + 1)
         for k in ks:
             out[f"{name}_R@{k}"] = float(np.mean(r < k))
     return out
 
 
-def retrieval_table(embeddings, ks=(1, 10, 100, 500), normalize=False, slab_rows=None):
+def retrieval_table(embeddings, ks=(1, 10, 100, 500), normalize=False, slab_rows=None, bound="optimistic", tie_rows=None):
     """ref eval.py:158-184 `calculate_retrieval_metrics`: {f"{mod1}-{mod2}": metrics} for every unordered pair of modalities, in insertion order.  The
-    embeddings are the encoders' outputs (already L2-normalised); normalize=True runs them through oneprot_l2norm_fwd first."""
+    embeddings are the encoders' outputs (already L2-normalised); normalize=True runs them through oneprot_l2norm_fwd first.  bound "pessimistic": ranks
+    + tie counts (oneprot_sim_rank_ties).  tie_rows: a dict that receives {pair: (rows with a tie s -> m, rows with a tie m -> s)}; asking for it, like the
+    pessimistic bound, runs the tie-counting kernel, whose ranks are those of the plain one."""
+    if bound not in BOUNDS:
+        raise ValueError(f"retrieval_table: bound {bound!r}; one of {', '.join(BOUNDS)}")
     feats = {}
     for name, x in embeddings.items():
         x = _features(x, f"retrieval_table: {name}")
@@ -91,9 +116,18 @@ def retrieval_table(embeddings, ks=(1, 10, 100, 500), normalize=False, slab_rows
             x = y
         feats[name] = x
     names = list(feats)
+    want_ties = bound == "pessimistic" or tie_rows is not None
     table = {}
     for a in range(len(names)):
         for b in range(a + 1, len(names)):
-            rr, rc = pair_ranks(feats[names[a]], feats[names[b]], slab_rows=slab_rows)
-            table[f"{names[a]}-{names[b]}"] = metrics_from_ranks(rr, rc, ks)
+            pair = f"{names[a]}-{names[b]}"
+            if not want_ties:
+                rr, rc = pair_ranks(feats[names[a]], feats[names[b]], slab_rows=slab_rows)
+                table[pair] = metrics_from_ranks(rr, rc, ks)
+                continue
+            rr, rc, tr, tc = pair_ranks(feats[names[a]], feats[names[b]], slab_rows=slab_rows, ties=True)
+            tr, tc = _host(tr), _host(tc)
+            table[pair] = metrics_from_ranks(rr, rc, ks, ties=(tr, tc), bound=bound)
+            if tie_rows is not None:
+                tie_rows[pair] = (int((tr > 0).sum()), int((tc > 0).sum()))
     return table
